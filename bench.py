@@ -8,11 +8,14 @@ The device-resident hipGraph replay rate, two edits in flight and batch-N are re
 Image-parallel over N GPUs: every rank edits its own items with a full replica; no collective inside the timed region
 except the bracketing barriers.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        # N > 1 without a launcher: spawns its own N ranks
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N > 1 without a launcher: spawns its own N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (dominant kernel + UNet forward, fp16 MFMA
-bound, HIP-event timed) and `cpu_baseline` (oracle/ fp32 restatement timed on this host, rank 0, N=1 only)."""
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the configuration).  `--full` adds everything else measured after the timed steps: the
+named extras (device-resident replay, edits in flight, batch N), `roofline` (dominant kernel + UNet forward, fp16 MFMA bound,
+HIP-event timed), per-stage and host-side times, and `cpu_baseline` (oracle/ fp32 restatement timed on this host, rank 0, N=1 only).
+`--dump-outputs DIR` writes what the last timed step returned (the edited 1024^2 RGB image) as DIR/edited_image.npy, float32."""
 import argparse
 import csv
 import json
@@ -351,13 +354,20 @@ def main():
     ap.add_argument("--strength", type=float, default=0.5)
     ap.add_argument("--guidance", type=float, default=1.5)
     ap.add_argument("--weights", default="f16", choices=["f16", "f8e4m3"], help="f8e4m3: BASELINE config 5 (separate config, never the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (skip the device-resident / in-flight / batch extras)")
-    ap.add_argument("--in-flight", type=int, default=2, help="extras: edits in flight per GPU (independent hipGraph slots on separate streams)")
-    ap.add_argument("--batch", type=int, default=0, help="extras: also time N images per device job (BASELINE config 'batch=8'); reported as "
+    ap.add_argument("--full", action="store_true", help="after the headline also measure the extras, the roofline, per-stage and host-side "
+                                                        "times and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: headline + roofline only (skip the device-resident / in-flight / batch extras)")
+    ap.add_argument("--in-flight", type=int, default=2, help="--full extras: edits in flight per GPU (independent hipGraph slots on separate streams)")
+    ap.add_argument("--batch", type=int, default=0, help="--full extras: also time N images per device job (BASELINE config 'batch=8'); reported as "
                                                          "batched_images_per_sec, never as `value`")
     ap.add_argument("--no-graph", action="store_true", help="issue the launches eagerly instead of replaying the captured hipGraph")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.batch > 1 and not args.full:
+        ap.error("--batch is an extra: it is measured with --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -440,6 +450,52 @@ def main():
     log(f"timed region: {elapsed:.3f}s for {args.steps} serial PIL-in -> PIL-out edits")
     evals, nb = pipe.last_stats["unet_evals"], pipe.last_stats["cfg_batch"]
     value = args.steps * world / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_img)
+
+    full = full_measurements(args, editor, work, edit, barrier, world, rank, evals, nb) if args.full else {}
+
+    if rank == 0:
+        fl = flops.image_flops(cfgs, evals, nb)
+        out = {
+            "metric": "PIE-Bench images/sec @1024^2 SSD-1B fp16 4-step", "value": round(value, 4), "unit": "images/sec",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16" if args.weights == "f16" else ("e4m3 x e4m3 on the block-scaled MFMA (fp32 accumulate) for the transformer-block projections of the UNet / ControlNet: "
+                                                                           "e4m3 weights with per-channel scales, e4m3 activations written by LayerNorm / attention / GEGLU / GroupNorm at calibrated power-of-two scales (saturating, NaN kept); "
+                                                                           "e4m3 weights x f16 activations for their other GEMMs / convs; f16 elsewhere"),
+            "data": "synthetic (seeded PIE-Bench-shaped 512^2 images, real PIE-Bench prompts, seeded random-init weights, stand-in tokenizer)",
+            "timed_region": "K serial FastEditor.edit() calls on K different items, PIL in -> PIL out, timer placed as run_batch.py:208-221 "
+                            "(includes LANCZOS, Canny, tokenise, RNG, H2D, the device graph, D2H, PIL); excludes model load and image decode",
+            "config": {"workload": f"{args.model} fp16 + ControlNet-Canny({args.controlnet}) LCM img2img, num_inference_steps=4, "
+                                   f"strength={args.strength}, guidance={args.guidance}, 1024x1024, batch=1 image per GPU, one edit at a time",
+                       "unet_preset": cfgs["unet"]["name"], "controlnet_preset": cfgs["controlnet"]["name"],
+                       "unet_evals": evals, "cfg_batch": nb, "parallelism": f"image-parallel x{world}",
+                       "launch": "eager" if args.no_graph else "hipGraph replay", "weights": args.weights, "fp8_activation_scales": fp8_scales,
+                       "tflop_per_image": round(fl["total"] / 1e12, 2)},
+            "per_rank_seconds": [round(x, 4) for x in per_rank],
+            "dist_backend": None if dist is None else dist.get_backend(),
+        }
+        out.update(full)
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, image):
+    """What the timed path returned in its last step, as a caller receives it (the PIL RGB image), stored as float32 HWC."""
+    os.makedirs(out_dir, exist_ok=True)
+    arr = np.asarray(image, dtype=np.float32)
+    np.save(os.path.join(out_dir, "edited_image.npy"), arr)
+    log(f"outputs of the last timed step written to {out_dir}: edited_image.npy {arr.shape} float32")
+
+
+def full_measurements(args, editor, work, edit, barrier, world, rank, evals, nb):
+    """Everything `--full` measures beyond the headline, after the timed steps (named keys of the result line, never `value`)."""
+    from fie_amd import flops
+    pipe = editor.pipe
+    cfgs = pipe.cfgs
+    total = args.warmup + args.steps
 
     # ---- extras (named keys, never `value`): device-resident hipGraph replay, two edits in flight, batch N
     extras = {}
@@ -551,57 +607,37 @@ def main():
         setattr(o, n, fn)
     log(f"stage ms: { {k: round(v, 1) for k, v in stage.items()} }; host ms/edit { {k: round(v, 1) for k, v in marks.items()} } of {e2e_ms:.1f}")
 
-    if rank == 0:
-        out = {
-            "metric": "PIE-Bench images/sec @1024^2 SSD-1B fp16 4-step", "value": round(value, 4), "unit": "images/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16" if args.weights == "f16" else ("e4m3 x e4m3 on the block-scaled MFMA (fp32 accumulate) for the transformer-block projections of the UNet / ControlNet: "
-                                                                           "e4m3 weights with per-channel scales, e4m3 activations written by LayerNorm / attention / GEGLU / GroupNorm at calibrated power-of-two scales (saturating, NaN kept); "
-                                                                           "e4m3 weights x f16 activations for their other GEMMs / convs; f16 elsewhere"),
-            "data": "synthetic (seeded PIE-Bench-shaped 512^2 images, real PIE-Bench prompts, seeded random-init weights, stand-in tokenizer)",
-            "timed_region": "K serial FastEditor.edit() calls on K different items, PIL in -> PIL out, timer placed as run_batch.py:208-221 "
-                            "(includes LANCZOS, Canny, tokenise, RNG, H2D, the device graph, D2H, PIL); excludes model load and image decode",
-            "config": {"workload": f"{args.model} fp16 + ControlNet-Canny({args.controlnet}) LCM img2img, num_inference_steps=4, "
-                                   f"strength={args.strength}, guidance={args.guidance}, 1024x1024, batch=1 image per GPU, one edit at a time",
-                       "unet_preset": cfgs["unet"]["name"], "controlnet_preset": cfgs["controlnet"]["name"],
-                       "unet_evals": evals, "cfg_batch": nb, "parallelism": f"image-parallel x{world}",
-                       "launch": "eager" if args.no_graph else "hipGraph replay", "weights": args.weights, "fp8_activation_scales": fp8_scales,
-                       "tflop_per_image": round(fl["total"] / 1e12, 2)},
-            # the dominant problem (top row of profiles/r04_per_shape_roofline.md), HIP-event timed above on cold weights; the second kernel,
-            # the per-class table of the committed kernel trace and the whole UNet forward (every launch between the events bracketing
-            # unet.encode + unet.decode, alone on one stream, replayed from a hipGraph) are priced beside it
-            "roofline": {"bound": "mfma", "kernel": dominant["kernel"], "shape": dominant["shape"],
-                         "achieved": dominant["achieved"], "peak": PEAK_F16_DENSE_TFLOPS, "unit": "TFLOP/s",
-                         "frac": dominant["frac"], "traffic": dominant["traffic_mb_per_launch"],
-                         "traffic_unit": "MB/launch, fabric side: 2 x FETCH_SIZE + WRITE_SIZE of separate rocprofv3 --pmc passes",
-                         "traffic_source": dominant["traffic_source"],
-                         "avg_us": dominant["avg_us"], "launches": dominant["launches"], "weight_copies": dominant["weight_copies"],
-                         "avg_us_what": "HIP events on the launch stream, the weight matrix rotated over > 256 MB of copies: the in-network (cold-weight) duration",
-                         "algorithmic_gflop_per_launch": dominant["algorithmic_gflop_per_launch"],
-                         "algorithmic_mb_per_launch": dominant["algorithmic_mb_per_launch"],
-                         "second": second,
-                         "second_what": "largest problem of the kernel family with the largest share of device time (M = 2048 x N = 1280 projections on the small ring tiles)",
-                         "class_table": classes, "class_table_source": classes_src,
-                         "class_table_what": "kernel classes of one edit, largest first: launches, kernel ms, share, aggregate rate, fraction of the bound (2.5 PF MFMA / 8 TB/s HBM); from the committed rocprofv3 kernel trace, not measured in this run",
-                         "unet_forward": {"what": f"{cfgs['unet']['name']}, batch {nb}, random inputs", "achieved": round(unet_tflops, 2),
-                                          "frac": round(unet_tflops / PEAK_F16_DENSE_TFLOPS, 4),
-                                          "algorithmic_tflop": round(fl["unet"] * nb / 1e12, 3), "ms": round(unet_ms_per_fwd, 3)}},
-            "stage_ms": {k: round(v, 2) for k, v in stage.items()},
-            "stage_ms_what": "eager single pass with HIP events (includes the host's per-launch cost on chains of small kernels: CLIP)",
-            "stage_graph_ms": stage_graphs,
-            "stage_graph_ms_what": "every stage as its own single-stream hipGraph, replayed: device time + algorithmic TFLOP/s; the production graph also overlaps CLIP || VAE encode and UNet encoder || ControlNet trunk",
-            "host_ms_per_edit": {k: round(v, 2) for k, v in marks.items()},
-            "image_tflops": round(image_tflops, 2),
-            "per_rank_seconds": [round(x, 4) for x in per_rank],
-            "dist_backend": None if dist is None else dist.get_backend(),
-        }
-        out.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(editor, cfgs, (first_inp, first_ctrl, first_prompt), evals, nb, args.strength, args.guidance)
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    out = {
+        # the dominant problem (top row of profiles/r04_per_shape_roofline.md), HIP-event timed above on cold weights; the second kernel,
+        # the per-class table of the committed kernel trace and the whole UNet forward (every launch between the events bracketing
+        # unet.encode + unet.decode, alone on one stream, replayed from a hipGraph) are priced beside it
+        "roofline": {"bound": "mfma", "kernel": dominant["kernel"], "shape": dominant["shape"],
+                     "achieved": dominant["achieved"], "peak": PEAK_F16_DENSE_TFLOPS, "unit": "TFLOP/s",
+                     "frac": dominant["frac"], "traffic": dominant["traffic_mb_per_launch"],
+                     "traffic_unit": "MB/launch, fabric side: 2 x FETCH_SIZE + WRITE_SIZE of separate rocprofv3 --pmc passes",
+                     "traffic_source": dominant["traffic_source"],
+                     "avg_us": dominant["avg_us"], "launches": dominant["launches"], "weight_copies": dominant["weight_copies"],
+                     "avg_us_what": "HIP events on the launch stream, the weight matrix rotated over > 256 MB of copies: the in-network (cold-weight) duration",
+                     "algorithmic_gflop_per_launch": dominant["algorithmic_gflop_per_launch"],
+                     "algorithmic_mb_per_launch": dominant["algorithmic_mb_per_launch"],
+                     "second": second,
+                     "second_what": "largest problem of the kernel family with the largest share of device time (M = 2048 x N = 1280 projections on the small ring tiles)",
+                     "class_table": classes, "class_table_source": classes_src,
+                     "class_table_what": "kernel classes of one edit, largest first: launches, kernel ms, share, aggregate rate, fraction of the bound (2.5 PF MFMA / 8 TB/s HBM); from the committed rocprofv3 kernel trace, not measured in this run",
+                     "unet_forward": {"what": f"{cfgs['unet']['name']}, batch {nb}, random inputs", "achieved": round(unet_tflops, 2),
+                                      "frac": round(unet_tflops / PEAK_F16_DENSE_TFLOPS, 4),
+                                      "algorithmic_tflop": round(fl["unet"] * nb / 1e12, 3), "ms": round(unet_ms_per_fwd, 3)}},
+        "stage_ms": {k: round(v, 2) for k, v in stage.items()},
+        "stage_ms_what": "eager single pass with HIP events (includes the host's per-launch cost on chains of small kernels: CLIP)",
+        "stage_graph_ms": stage_graphs,
+        "stage_graph_ms_what": "every stage as its own single-stream hipGraph, replayed: device time + algorithmic TFLOP/s; the production graph also overlaps CLIP || VAE encode and UNet encoder || ControlNet trunk",
+        "host_ms_per_edit": {k: round(v, 2) for k, v in marks.items()},
+        "image_tflops": round(image_tflops, 2),
+    }
+    out.update(extras)
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(editor, cfgs, (first_inp, first_ctrl, first_prompt), evals, nb, args.strength, args.guidance)
+    return out
 
 
 if __name__ == "__main__":

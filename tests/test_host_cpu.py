@@ -126,6 +126,15 @@ def test_bench_reads_the_pmc_record_of_the_tile_it_ran(tmp_path):
     assert bench.pmc_traffic("any kernel (tile code 1)", 8, 8, 8, path=str(single)) == (round((2 * 1000.0 + 48.0) * 1024 / 1e6, 1), ["x.csv"])
 
 
+def test_bench_dump_outputs_stores_the_returned_image_as_float32(tmp_path):
+    """bench.py --dump-outputs DIR: the PIL image the last timed edit returned, as DIR/edited_image.npy, float32 HWC, values unchanged."""
+    import bench
+    a = np.random.default_rng(0).integers(0, 256, (16, 24, 3), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "d"), Image.fromarray(a))
+    b = np.load(tmp_path / "d" / "edited_image.npy")
+    assert b.dtype == np.float32 and b.shape == (16, 24, 3) and np.array_equal(b, a)
+
+
 @pytest.mark.parametrize("geglu", [False, True])
 def test_layernorm_fold_tables_reproduce_layernorm_plus_linear(geglu):
     """The algebra behind fie_gemm_ln_f16 (hip.fold_layernorm_tables), on the CPU in float64: rstd * (x Wf^T - mean * S) + b' against LayerNorm -> Linear
