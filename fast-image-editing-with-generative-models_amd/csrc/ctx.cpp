@@ -22,7 +22,7 @@ void fie_set_error(const char* fmt, ...) {
 
 void fie_oplog_append(fie_ctx* ctx, const void* fn, dim3 grid, dim3 block, unsigned lds) {
     const char* name = hipKernelNameRefByPtr(fn, ctx->stream);
-    char line[512];
+    char line[768];
     snprintf(line, sizeof(line), "%s|%u|%u|%u|%s", name ? name : "?", grid.x * grid.y * grid.z, block.x * block.y * block.z, lds, ctx->op_desc);
     ctx->oplog->push_back(line);
     ctx->op_desc[0] = 0;
@@ -204,6 +204,7 @@ int fie_ctx_destroy(fie_ctx* ctx) {
     if (ctx && ctx->tune_buf) (void)hipFree(ctx->tune_buf);
     if (ctx && ctx->tune_flush) (void)hipFree(ctx->tune_flush);
     if (ctx) delete ctx->oplog;
+    if (ctx) delete ctx->tune_cands;
     delete ctx;                       // registered programs are owned by the caller (fie_program_destroy)
     return FIE_OK;
 }

@@ -81,7 +81,8 @@ struct fie_ctx {
     char last_kernel[128] = "";
     fie_program* recording = nullptr;                 // launches are appended here while set (fie_program_begin / _end)
     std::vector<std::string>* oplog = nullptr;        // fie_debug_oplog: one line per launch (kernel symbol, grid, block, LDS, the op's own description)
-    char op_desc[192] = "";                           // FIE_DESC: description of the op whose next launch is logged (consumed by that launch)
+    char op_desc[384] = "";                           // FIE_DESC: description of the op whose next launch is logged (consumed by that launch)
+    std::vector<std::string>* tune_cands = nullptr;   // fie_debug_tune_candidates: one "key rule=code cands=..." line per tunable GEMM / conv launch
     std::map<std::string, fie_program*> graphs;       // fie_graph_register: "unet_forward", "vae_decode", ...
     std::map<std::string, fie_step_cache> step_caches;   // by model prefix (graphs.cpp)
     std::map<std::string, fie_weight> weights;        // fie_weights_register: what the C++ graph walks (graphs.cpp: fie_vae_decode_f16) look up

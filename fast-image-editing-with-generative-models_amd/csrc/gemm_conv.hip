@@ -786,11 +786,21 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
     snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "%s<%dx%d> (%s, tile code %d)", code >= 90 ? "gemm3_kernel+prefetch" : code >= 80 ? "gemm8_kernel" : code == 77 ? "conv_thin_kernel" : code >= 71 && code <= 76 ? (code == 71 || code == 73 ? "conv_halo_kernel" : "conv_halo2_kernel") : code >= 40 ? "gemm3_kernel" : "gemm_kernel",
              t->bm, t->bn, MODE == 1 ? "conv3x3" : "gemm", code);
     if (split > 1) snprintf(ctx->last_kernel + strlen(ctx->last_kernel) - 1, 24, ", split-K %d)", split);
-    if (MODE == 1)
-        FIE_DESC(ctx, "conv M=%d N=%d K=%d in=%dx%dx%d s%d u%d%s%s code=%d flop=%.0f", a.M * (a.oscat == 2 ? 4 : 1), a.N, a.K, a.H, a.W, a.Cin, a.stride, a.ups,
-                 a.taps2 ? " up2x-parity" : "", a.A2 ? " +1x1" : "", code + 10000 * (split > 1 ? split : 0), 2.0 * a.M * a.N * a.K * (a.oscat == 2 ? 4 : 1));
-    else
-        FIE_DESC(ctx, "gemm M=%d N=%d K=%d act=%d%s%s%s code=%d flop=%.0f", a.M, a.N, a.K, a.act, a.res ? " +res" : "", a.ln_tab ? " +ln" : "", a.w_scale ? (a.a_scale != 0.f ? " a8w8" : " w8") : "", code + 10000 * (split > 1 ? split : 0), 2.0 * a.M * a.N * a.K);
+    if (ctx->oplog) {
+        // after the flop token: what it takes to rebuild the call (tools/launch_problems.py): batch, padding, side inputs and the A1|A2 seam, the parity
+        // view, weight / activation precision, and the epilogue (bias, row bias, residual, act, scale, GroupNorm partial sums, f8 output, LN / GN folds)
+        char rebuild[256];
+        snprintf(rebuild, sizeof(rebuild), " | b=%d pad=%d C2=%d C3=%d K1=%d parity=%d w8=%d bias=%d rowbias=%d rpb=%d res=%d act=%d scale=%.9g gn=%d gnrows=%d f8out=%d ln=%d gna=%d",
+                 MODE == 1 ? a.M / (a.OH * a.OW) : 1, MODE == 1 && !a.taps2 && a.pt == 0 ? 1 : 0, a.C2x, a.C3x, a.K1, a.taps2, a.w_scale ? (a.a_scale != 0.f ? 2 : 1) : 0,
+                 a.bias != nullptr, a.rowbias != nullptr, a.rowbias ? a.rows_per_batch : 0, a.res != nullptr, a.act, (double)a.scale, a.gn_partial ? a.gn_G : 0,
+                 a.gn_partial ? a.gn_rows : 0, a.out_f8, a.ln_tab != nullptr, a.gna_tab != nullptr);
+        if (MODE == 1)
+            FIE_DESC(ctx, "conv M=%d N=%d K=%d in=%dx%dx%d s%d u%d%s%s code=%d flop=%.0f%s", a.M * (a.oscat == 2 ? 4 : 1), a.N, a.K, a.H, a.W, a.Cin, a.stride, a.ups,
+                     a.taps2 ? " up2x-parity" : "", a.A2 ? " +1x1" : "", code + 10000 * (split > 1 ? split : 0), 2.0 * a.M * a.N * a.K * (a.oscat == 2 ? 4 : 1), rebuild);
+        else
+            FIE_DESC(ctx, "gemm M=%d N=%d K=%d act=%d%s%s%s code=%d flop=%.0f%s", a.M, a.N, a.K, a.act, a.res ? " +res" : "", a.ln_tab ? " +ln" : "", a.w_scale ? (a.a_scale != 0.f ? " a8w8" : " w8") : "",
+                     code + 10000 * (split > 1 ? split : 0), 2.0 * a.M * a.N * a.K, rebuild);
+    }
     if (x8) {
         snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm3x8_kernel<%dx%d> (gemm, fp8 activations x fp8 weights, tile code %d%s", t->bm, t->bn, code, split > 1 ? "" : ")");
         if (split > 1) snprintf(ctx->last_kernel + strlen(ctx->last_kernel), 24, ", split-K %d)", split);
@@ -857,7 +867,8 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
 // ---- per-shape autotune (fie_gemm_autotune): the first eager launch of a shape times every eligible tile on a scratch output
 // and remembers the fastest; later launches (and stream captures, which never tune) use the remembered code.  The candidates
 // differ in tile shape, ring depth and blocks per CU; every im2col tile accumulates K in the same order, so the choice among them does not change
-// the result (the halo-resident conv, code 72, sums chunk-major and a split-K code in slices: those two move the last f16 bit).  Selection by
+// the result (the halo-resident conv, code 72, sums chunk-major and a split-K code in slices: those two move the last f16 bit).  Checked bit for bit,
+// the 256x256 phased codes (81) included, at every problem one edit of the four product configurations runs (tests/test_launch_table_gpu.py, pass 3).  Selection by
 // measurement instead of by rule: which tile wins depends on how the grid quantises onto 256 CUs
 // and on whether two blocks share a CU (their epilogues and DMA issue overlap), see DESIGN.md.
 // Every timed launch sees what a launch inside the network sees: weights COLD (the 256 MB Infinity Cache is flushed by a
@@ -867,47 +878,16 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
 // (tools/cold_weights.py).
 constexpr size_t kFlushBytes = 384u << 20;
 
+// What the tuner times besides the rule's code `guess`, in timing order: plain tile codes, then split-K encodings code + 10000 * s (s = 2..4).
+// autotune below times exactly this list; fie_debug_tune_candidates reports it (tests/test_launch_table_gpu.py runs every entry at the product's shapes).
 template <int MODE>
-int autotune(fie_ctx* ctx, GemmArgs& a, int guess, bool dma_ok) {
+std::vector<int> tune_candidates(const fie_ctx* ctx, const GemmArgs& a, int guess) {
     static const int kRing[] = {43, 46, 42, 44, 51, 52, 54, 96, 81, 63, 47, 48, 64, 72};      // 47 (128x96): FIE_TUNE_47=0 leaves it out
     static const bool use47 = !(getenv("FIE_TUNE_47") && getenv("FIE_TUNE_47")[0] == '0');
     static const int kW8[] = {43, 42, 62, 52, 54};
     static const int kX8[] = {43, 42, 47, 51, 52, 54, 62, 63};
-    const size_t bytes = (size_t)a.M * (a.oscat ? 4 : 1) * (size_t)a.ldc * sizeof(half_t);     // a parity conv scatters its M rows over 4 M output rows
-    if (bytes > ctx->tune_bytes) {
-        if (ctx->tune_buf) (void)hipFree(ctx->tune_buf);
-        ctx->tune_buf = nullptr;
-        ctx->tune_bytes = 0;
-        if (hipMalloc(&ctx->tune_buf, bytes) != hipSuccess) { (void)hipGetLastError(); return guess; }
-        ctx->tune_bytes = bytes;
-    }
-    if (!ctx->tune_flush && hipMalloc(&ctx->tune_flush, kFlushBytes) != hipSuccess) { (void)hipGetLastError(); ctx->tune_flush = nullptr; return guess; }
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return guess;
-    (void)hipDeviceSynchronize();                          // nothing else on the device while the candidates are timed
-    GemmArgs t = a;
-    t.C = static_cast<half_t*>(ctx->tune_buf);           // a residual that aliases C is still read from the caller's buffer
+    std::vector<int> out;
     auto blocks = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-    auto time_of = [&](int code, int split = 1) -> float {
-        float ms[7];
-        for (int rep = -1; rep < 7; ++rep) {               // rep -1: untimed (first use of the kernel)
-            (void)hipMemsetAsync(ctx->tune_flush, rep & 1, kFlushBytes, ctx->stream);
-            if ((size_t)a.a1_bytes <= kFlushBytes) (void)hipMemcpyAsync(ctx->tune_flush, a.A1, (size_t)a.a1_bytes, hipMemcpyDeviceToDevice, ctx->stream);
-            if (a.A2 && a.A2 != a.A1 && (size_t)a.a2_bytes <= kFlushBytes) (void)hipMemcpyAsync(ctx->tune_flush, a.A2, (size_t)a.a2_bytes, hipMemcpyDeviceToDevice, ctx->stream);
-            (void)hipEventRecord(e0, ctx->stream);
-            if (run_code<MODE>(ctx, t, code, -1, dma_ok, split) != FIE_OK) return 1e30f;
-            (void)hipEventRecord(e1, ctx->stream);
-            if (hipEventSynchronize(e1) != hipSuccess) return 1e30f;
-            if (rep >= 0) (void)hipEventElapsedTime(&ms[rep], e0, e1);
-        }
-        std::sort(ms, ms + 7);
-        return (ms[2] + ms[3] + ms[4]) / 3.f;              // mean of the middle three of seven
-    };
-    static const bool verbose = getenv("FIE_TUNE_VERBOSE") && getenv("FIE_TUNE_VERBOSE")[0] == '1';
-    const float t_guess = time_of(guess);
-    if (verbose) fprintf(stderr, "[fie tune] %s M=%d N=%d K=%d: rule %d %.1f us", MODE == 1 ? "conv" : "gemm", a.M, a.N, a.K, guess, t_guess * 1e3f);
-    int best = guess;
-    float t_best = t_guess * 0.97f;                          // a challenger has to win by 3 %
     const bool x8 = a.w_scale && a.a_scale != 0.f;
     const int* cand = x8 ? kX8 : a.w_scale ? kW8 : kRing;
     const int ncand = x8 ? 8 : a.w_scale ? 5 : 14;
@@ -928,9 +908,7 @@ int autotune(fie_ctx* ctx, GemmArgs& a, int guess, bool dma_ok) {
         if (x8 && (c == 62 || c == 51) && 2 * blocks(c == 62 ? 256 : 128, 128) < ctx->num_cus) continue;
         if (c == 81 && MODE == 1 && a.A2) continue;            // side inputs: ring kernels only
         if (c == 72 && (MODE != 1 || !fie_conv_halo_ok(a) || 2 * (int64_t)(a.M / 256) * ((a.N + 127) / 128) < ctx->num_cus)) continue;
-        const float tc = time_of(c);
-        if (verbose) fprintf(stderr, ", %d %.1f", c, tc * 1e3f);
-        if (tc < t_best) { t_best = tc; best = c; }
+        out.push_back(c);
     }
     // split-K: big tiles whose grid leaves CUs idle (the M = 2048 class: 80 tiles of 256x128 on 256 CUs) with the K-steps of a tile dealt
     // to 2-4 blocks, reduced in the launch (gemm_common.h: splitk_reduce).  Changes the fp32 summation order, so unlike the tile choice
@@ -948,11 +926,57 @@ int autotune(fie_ctx* ctx, GemmArgs& a, int guess, bool dma_ok) {
             for (int sp = 2; sp <= 4; ++sp) {
                 if (nb * sp > (int64_t)ctx->num_cus * c.per_cu * 21 / 20) break;
                 if (splitk_fit(ctx, a, c.code, c.bm, c.bn, sp) != sp) continue;
-                const float tc = time_of(c.code, sp);
-                if (verbose) fprintf(stderr, ", %d/s%d %.1f", c.code, sp, tc * 1e3f);
-                if (tc < t_best) { t_best = tc; best = c.code + 10000 * sp; }
+                out.push_back(c.code + 10000 * sp);
             }
         }
+    }
+    return out;
+}
+
+template <int MODE>
+int autotune(fie_ctx* ctx, GemmArgs& a, int guess, bool dma_ok) {
+    const size_t bytes = (size_t)a.M * (a.oscat ? 4 : 1) * (size_t)a.ldc * sizeof(half_t);     // a parity conv scatters its M rows over 4 M output rows
+    if (bytes > ctx->tune_bytes) {
+        if (ctx->tune_buf) (void)hipFree(ctx->tune_buf);
+        ctx->tune_buf = nullptr;
+        ctx->tune_bytes = 0;
+        if (hipMalloc(&ctx->tune_buf, bytes) != hipSuccess) { (void)hipGetLastError(); return guess; }
+        ctx->tune_bytes = bytes;
+    }
+    if (!ctx->tune_flush && hipMalloc(&ctx->tune_flush, kFlushBytes) != hipSuccess) { (void)hipGetLastError(); ctx->tune_flush = nullptr; return guess; }
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return guess;
+    (void)hipDeviceSynchronize();                          // nothing else on the device while the candidates are timed
+    GemmArgs t = a;
+    t.C = static_cast<half_t*>(ctx->tune_buf);           // a residual that aliases C is still read from the caller's buffer
+    auto time_of = [&](int code, int split = 1) -> float {
+        float ms[7];
+        for (int rep = -1; rep < 7; ++rep) {               // rep -1: untimed (first use of the kernel)
+            (void)hipMemsetAsync(ctx->tune_flush, rep & 1, kFlushBytes, ctx->stream);
+            if ((size_t)a.a1_bytes <= kFlushBytes) (void)hipMemcpyAsync(ctx->tune_flush, a.A1, (size_t)a.a1_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+            if (a.A2 && a.A2 != a.A1 && (size_t)a.a2_bytes <= kFlushBytes) (void)hipMemcpyAsync(ctx->tune_flush, a.A2, (size_t)a.a2_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+            (void)hipEventRecord(e0, ctx->stream);
+            if (run_code<MODE>(ctx, t, code, -1, dma_ok, split) != FIE_OK) return 1e30f;
+            (void)hipEventRecord(e1, ctx->stream);
+            if (hipEventSynchronize(e1) != hipSuccess) return 1e30f;
+            if (rep >= 0) (void)hipEventElapsedTime(&ms[rep], e0, e1);
+        }
+        std::sort(ms, ms + 7);
+        return (ms[2] + ms[3] + ms[4]) / 3.f;              // mean of the middle three of seven
+    };
+    static const bool verbose = getenv("FIE_TUNE_VERBOSE") && getenv("FIE_TUNE_VERBOSE")[0] == '1';
+    const float t_guess = time_of(guess);
+    if (verbose) fprintf(stderr, "[fie tune] %s M=%d N=%d K=%d: rule %d %.1f us", MODE == 1 ? "conv" : "gemm", a.M, a.N, a.K, guess, t_guess * 1e3f);
+    int best = guess;
+    float t_best = t_guess * 0.97f;                          // a challenger has to win by 3 %
+    for (const int enc : tune_candidates<MODE>(ctx, a, guess)) {
+        const int c = enc % 10000, sp = enc / 10000 > 1 ? enc / 10000 : 1;
+        const float tc = time_of(c, sp);
+        if (verbose) {
+            if (sp > 1) fprintf(stderr, ", %d/s%d %.1f", c, sp, tc * 1e3f);
+            else fprintf(stderr, ", %d %.1f", c, tc * 1e3f);
+        }
+        if (tc < t_best) { t_best = tc; best = enc; }
     }
     if (verbose) fprintf(stderr, " -> %d\n", best);
     (void)hipEventDestroy(e0);
@@ -996,11 +1020,24 @@ int launch(fie_ctx* ctx, GemmArgs& a) {
     if (ctx->force_tile) { decode(ctx->force_tile); pinned = true; }
     // at most 16 output channels (conv_out of the VAE / UNet, the conditioning embedding's first convs): the direct-load strip kernel of conv_thin.hip,
     // by rule and without the tuner (one kernel family; profiles/r04_conv_thin.md).  fie_debug_tune_exclude("77") is the A/B switch.
+    const fie_tune_key key{MODE, a.M, a.N, a.K, a.K1, MODE == 1 ? a.stride * 2 + a.ups + 8 * a.taps2 + 16 * (a.A2 != nullptr) + 32 * (a.A3 != nullptr) : 0, a.w_scale == nullptr ? 0 : a.a_scale != 0.f ? 2 : 1};
+    // fie_debug_tune_candidates: "rule, then every candidate" of a launch the tuner could decide, in the key format of fie_gemm_autotune_report; the rule's code runs
+    auto note_candidates = [&](int rule, const std::vector<int>& cands) {
+        char line[256];
+        int n = snprintf(line, sizeof(line), "%s M=%d N=%d K=%d K1=%d geom=%d w8=%d rule=%d cands=", MODE == 1 ? "conv" : "gemm", key.M, key.N, key.K, key.K1, key.geom, key.w8, rule);
+        for (size_t i = 0; i < cands.size() && n < (int)sizeof(line) - 8; ++i) n += snprintf(line + n, sizeof(line) - n, i ? ",%d" : "%d", cands[i]);
+        ctx->tune_cands->push_back(line);
+    };
     if (MODE == 1 && !pinned && !ctx->gemm_probe && fie_conv_thin_ok(a) && a.M >= 131072 &&      // (the 128x128-latent conv_outs, K 2880 / 4608 on few strips: the ring tiles are faster)
-        std::find(std::begin(ctx->tune_exclude), std::end(ctx->tune_exclude), 77) == std::end(ctx->tune_exclude))
+        std::find(std::begin(ctx->tune_exclude), std::end(ctx->tune_exclude), 77) == std::end(ctx->tune_exclude)) {
+        if (ctx->tune_cands) note_candidates(77, {});      // by rule, never tuned
         return run_code<MODE>(ctx, a, 77, 0, dma_ok, 1);
+    }
+    if (ctx->tune_cands && !pinned && !ctx->gemm_probe) {
+        note_candidates(code, dma_ok ? tune_candidates<MODE>(ctx, a, code) : std::vector<int>{});
+        return run_code<MODE>(ctx, a, code, order, dma_ok, split);
+    }
     if (ctx->autotune && !pinned && dma_ok && !ctx->gemm_probe) {      // 1: tune shapes not met before, 2: remembered shapes only
-        const fie_tune_key key{MODE, a.M, a.N, a.K, a.K1, MODE == 1 ? a.stride * 2 + a.ups + 8 * a.taps2 + 16 * (a.A2 != nullptr) + 32 * (a.A3 != nullptr) : 0, a.w_scale == nullptr ? 0 : a.a_scale != 0.f ? 2 : 1};
         auto it = ctx->tuned.find(key);
         if (it != ctx->tuned.end()) {
             decode(it->second);
@@ -1217,6 +1254,28 @@ int fie_debug_gemm_stamps(fie_ctx* ctx, void* buf) {
 }
 
 const char* fie_debug_last_gemm_kernel(fie_ctx* ctx) { return ctx ? ctx->last_kernel : ""; }
+
+// While on, every GEMM / conv launch the tuner could decide appends "gemm|conv M= N= K= K1= geom= w8= rule=<code> cands=<c1>,<c2>,..." (the list
+// tune_candidates gives: what autotune would time besides the rule) and runs the rule's code instead of tuning or looking up a remembered choice; the
+// thin-conv rule appears as "rule=77 cands=" (empty).  _read copies the newline-joined lines and returns their length (cap 0: size query).
+int fie_debug_tune_candidates(fie_ctx* ctx, int on) {
+    FIE_REQUIRE(ctx != nullptr, "fie_debug_tune_candidates: ctx is NULL");
+    delete ctx->tune_cands;
+    ctx->tune_cands = on ? new std::vector<std::string>() : nullptr;
+    return FIE_OK;
+}
+
+int64_t fie_debug_tune_candidates_read(fie_ctx* ctx, char* buf, int64_t cap) {
+    if (!ctx || !ctx->tune_cands) return 0;
+    int64_t n = 0;
+    for (const std::string& l : *ctx->tune_cands) n += (int64_t)l.size() + 1;
+    if (buf && cap > n) {
+        char* q = buf;
+        for (const std::string& l : *ctx->tune_cands) { memcpy(q, l.data(), l.size()); q += l.size(); *q++ = '\n'; }
+        *q = 0;
+    }
+    return n;
+}
 
 // The one-shot GroupNorm target (fie_gn_stats_target) is taken -- and the context disarmed -- at the very TOP of every GEMM / conv entry,
 // before any argument check can return: a call that fails validation must not leave it armed for an unrelated later launch (whose M

@@ -127,6 +127,8 @@ SIGNATURES = {
     "fie_debug_oplog": [_P, _I],
     "fie_debug_oplog_mark": [_P, _c.c_char_p],
     "fie_debug_oplog_read": [_P, _c.c_char_p, _L],
+    "fie_debug_tune_candidates": [_P, _I],
+    "fie_debug_tune_candidates_read": [_P, _c.c_char_p, _L],
 }
 
 _lib = None
@@ -152,7 +154,7 @@ def lib():
         for name, args in SIGNATURES.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
-            fn.restype = _L if name in ("fie_groupnorm_workspace_bytes", "fie_canny_workspace_bytes", "fie_time_embed_workspace_bytes", "fie_gn_stats_bytes", "fie_debug_oplog_read", "fie_vae_decode_workspace_bytes",
+            fn.restype = _L if name in ("fie_groupnorm_workspace_bytes", "fie_canny_workspace_bytes", "fie_time_embed_workspace_bytes", "fie_gn_stats_bytes", "fie_debug_oplog_read", "fie_debug_tune_candidates_read", "fie_vae_decode_workspace_bytes",
                                        "fie_vae_encode_workspace_bytes", "fie_clip_text_workspace_bytes", "fie_unet_workspace_bytes", "fie_controlnet_workspace_bytes",
                                        "fie_unet_step_cache_bytes") else _I
         _lib.fie_last_error.restype = ctypes.c_char_p
@@ -473,6 +475,23 @@ class Context:
         buf = ctypes.create_string_buffer(int(n) + 16)
         lib().fie_debug_oplog_read(self.h, buf, len(buf))
         return [l for l in buf.value.decode().split("\n") if l]
+
+    def tune_candidates(self, on=True):
+        """While on, GEMM / conv launches the tuner could decide run the rule's code and report what the tuner would time (include/fie.h:
+        fie_debug_tune_candidates); tune_candidates_read() returns [(key, rule, [candidates])], key in the format of autotune_report."""
+        _chk(lib().fie_debug_tune_candidates(self.h, int(on)))
+
+    def tune_candidates_read(self):
+        n = lib().fie_debug_tune_candidates_read(self.h, None, 0)
+        buf = ctypes.create_string_buffer(int(n) + 16)
+        lib().fie_debug_tune_candidates_read(self.h, buf, len(buf))
+        out = []
+        for line in buf.value.decode().split("\n"):
+            if line:
+                key, rest = line.split(" rule=")
+                rule, cands = rest.split(" cands=")
+                out.append((key, int(rule), [int(c) for c in cands.split(",") if c]))
+        return out
 
     def gemm_stamps(self, buf):
         """Device int32 tensor [tiles * waves * 8] the stamped ring kernels (tile codes 97 / 98) write their cycle sums to; None detaches."""
