@@ -332,7 +332,9 @@ def register_pipeline(pipe):
 @torch.no_grad()
 def run_edit(pipe, job, step_cache=True):
     """The device side of one edit (pipe.run_device's job, one image) with EVERY model call going through a C-ABI forward: the call sequence a
-    non-Python host would issue for the pipeline call at /root/reference/src/pipeline.py:261-272.  Returns the u8 HWC image on the device."""
+    non-Python host would issue for the pipeline call at /root/reference/src/pipeline.py:261-272.  Returns the u8 HWC image on the device.
+    A masked job (pipe.prepare(..., mask_image=...)) takes the masked entries: fie_latent_prep_src, fie_lcm_step_masked and, with the
+    paste-back, fie_pixels_out_composite_* (INTEGRATION.md, "Mask-restricted edits")."""
     ctx = pipe.ctx
     dev = ctx.device
     h, w = job["hw"]
@@ -347,7 +349,12 @@ def run_edit(pipe, job, step_cache=True):
     sf = pipe.cfgs["vae"]["scaling_factor"]
     latents = torch.empty((hw, 4), device=dev, dtype=torch.float32)
     model_in = torch.empty((nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
-    ctx.latent_prep(moments, job["noises"][0], job["noises"][1], hw, sf, steps[0]["sqrt_ab"], steps[0]["sqrt_1mab"], latents, model_in)
+    mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")
+    if mask_lat is None:
+        ctx.latent_prep(moments, job["noises"][0], job["noises"][1], hw, sf, steps[0]["sqrt_ab"], steps[0]["sqrt_1mab"], latents, model_in)
+    else:
+        z0 = torch.empty((hw, 4), device=dev, dtype=torch.float32)
+        ctx.latent_prep_src(moments, job["noises"][0], job["noises"][1], hw, sf, steps[0]["sqrt_ab"], steps[0]["sqrt_1mab"], latents, model_in, z0)
     cond = ctx.pixels_in(job["ctl_u8"], False).repeat(nb, 1, 1, 1).contiguous()       # upstream runs the ControlNet on the duplicated control image
     decode_in = torch.empty((1, lh, lw, 8), device=dev, dtype=ctx.dtype)
     if step_cache:                      # what does not change over the steps (text K / V, conditioning embedding) is computed by the first forward only
@@ -358,10 +365,16 @@ def run_edit(pipe, job, step_cache=True):
         downs, mid = controlnet_forward(pipe.controlnet, pre + "controlnet.", model_in, t_dev, text, pooled, job["time_ids"], cond, job["cn_scale"])
         eps = unet_forward(pipe.unet, pre + "unet.", model_in, t_dev, text, pooled, job["time_ids"], downs, mid)
         z = None if st["last"] else job["noises"][next_noise]
-        ctx.lcm_step(eps, nb, job["guidance"], latents, z, hw, st["sqrt_ab"], st["sqrt_1mab"], st["c_skip"], st["c_out"], st["sqrt_ab_prev"],
-                     st["sqrt_1mab_prev"], model_in, 1.0 / sf, decode_in)
+        if mask_lat is None:
+            ctx.lcm_step(eps, nb, job["guidance"], latents, z, hw, st["sqrt_ab"], st["sqrt_1mab"], st["c_skip"], st["c_out"], st["sqrt_ab_prev"],
+                         st["sqrt_1mab_prev"], model_in, 1.0 / sf, decode_in)
+        else:
+            ctx.lcm_step_masked(eps, nb, job["guidance"], latents, z, hw, st["sqrt_ab"], st["sqrt_1mab"], st["c_skip"], st["c_out"],
+                                st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in, 1.0 / sf, decode_in, mask_lat[0], z0, job["noises"][1])
         next_noise += 1
     if step_cache:
         step_cache_end(pipe.unet, pre + "unet.")
         step_cache_end(pipe.controlnet, pre + "controlnet.")
+    if mask_px is not None:
+        return ctx.pixels_out_composite(vae_decode(pipe.vae, decode_in), job["img_u8"], mask_px[0])
     return ctx.pixels_out(vae_decode(pipe.vae, decode_in))

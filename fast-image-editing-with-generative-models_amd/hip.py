@@ -104,6 +104,14 @@ SIGNATURES = {
     "fie_canny_workspace_bytes": [_I, _I],
     "fie_canny_rgb_device_u8": [_P, _P, _I, _I, _I, _I, _P, _P, _c.POINTER(_I)],
     "fie_resize_rgb_u8": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P],
+    "fie_resize_l_u8": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P],
+    "fie_mask_prep": [_P, _P, _I, _I, _P, _I, _P, _P],
+    "fie_latent_prep_src": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I, _P],
+    "fie_latent_prep_src_f32": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I, _P],
+    "fie_lcm_step_masked": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P, _P, _P, _P],
+    "fie_lcm_step_masked_f32": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P, _P, _P, _P],
+    "fie_pixels_out_composite_f16_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
+    "fie_pixels_out_composite_f32_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
     "fie_debug_force_tile": [_P, _I],
     "fie_debug_attn_variant": [_P, _I],
     "fie_debug_gn_onepass": [_P, _I],
@@ -900,11 +908,17 @@ class Context:
         return out
 
     def resize_lanczos(self, rgb_u8, out_h, out_w):
-        """u8 [H, W, 3] device tensor -> u8 [out_h, out_w, 3], bit-exact with PIL's `resize(..., Image.LANCZOS)`."""
-        from . import resize
+        """u8 [H, W, 3] device tensor -> u8 [out_h, out_w, 3], bit-exact with PIL's `resize(..., Image.LANCZOS)`.  A u8 [H, W] tensor
+        (a mode-L mask) -> u8 [out_h, out_w] through the one-band kernels (fie_resize_l_u8)."""
         self.sync_stream()
-        h, w, _ = rgb_u8.shape
         assert rgb_u8.dtype == torch.uint8 and rgb_u8.is_contiguous()
+        if rgb_u8.dim() == 2:
+            return self._resize(rgb_u8, rgb_u8.shape[0], rgb_u8.shape[1], out_h, out_w, (), lib().fie_resize_l_u8)
+        h, w, _ = rgb_u8.shape
+        return self._resize(rgb_u8, h, w, out_h, out_w, (3,), lib().fie_resize_rgb_u8)
+
+    def _resize(self, src, h, w, out_h, out_w, chan, entry):
+        from . import resize
         tabs = []
         for n_in, n_out in ((w, out_w), (h, out_h)):
             key = (n_in, n_out)
@@ -912,10 +926,37 @@ class Context:
                 kk, bounds, ks = resize.coefficients(n_in, n_out)
                 self._resize_tables[key] = (torch.from_numpy(kk).to(self.device), torch.from_numpy(bounds).to(self.device), ks)
             tabs.append(self._resize_tables.get(key) if n_in != n_out else (None, None, 0))
-        out = torch.empty((out_h, out_w, 3), device=rgb_u8.device, dtype=torch.uint8)
-        tmp = torch.empty((h, out_w, 3), device=rgb_u8.device, dtype=torch.uint8) if (h != out_h and w != out_w) else None
+        out = torch.empty((out_h, out_w) + chan, device=src.device, dtype=torch.uint8)
+        tmp = torch.empty((h, out_w) + chan, device=src.device, dtype=torch.uint8) if (h != out_h and w != out_w) else None
         (kx, bx, ksx), (ky, by, ksy) = tabs
-        _chk(lib().fie_resize_rgb_u8(self.h, _p(rgb_u8), h, w, _p(out), out_h, out_w, _p(kx), _p(bx), ksx, _p(ky), _p(by), ksy, _p(tmp)))
+        _chk(entry(self.h, _p(src), h, w, _p(out), out_h, out_w, _p(kx), _p(bx), ksx, _p(ky), _p(by), ksy, _p(tmp)))
+        return out
+
+    def mask_prep(self, mask_l, blur=0.0):
+        """Edit-size u8 [H, W] mask on the device (white = edit) -> (mask_px f32 [H, W], mask_lat u8 [H/8 * W/8]): one launch of
+        fie_mask_prep.  mask_px is the binary mask L >= 128, or with blur = r > 0 its Gaussian feather (fie_amd/mask.py: gaussian_taps)."""
+        from . import mask as hmask
+        self.sync_stream()
+        h, w = mask_l.shape
+        assert mask_l.dtype == torch.uint8 and mask_l.is_contiguous()
+        cache = self.__dict__.setdefault("_mask_taps", {})
+        key = float(blur)
+        if key not in cache:
+            cache[key] = torch.from_numpy(hmask.gaussian_taps(key)).to(self.device)
+        taps = cache[key]
+        m_px = torch.empty((h, w), device=self.device, dtype=torch.float32)
+        m_lat = torch.empty(((h // 8) * (w // 8),), device=self.device, dtype=torch.uint8)
+        _chk(lib().fie_mask_prep(self.h, _p(mask_l), h, w, _p(taps), (taps.numel() - 1) // 2, _p(m_px), _p(m_lat)))
+        return m_px, m_lat
+
+    def pixels_out_composite(self, x_nhwc, source_u8, mask_px):
+        """pixels_out() with the paste-back: the source bytes where mask_px == 0, the decoded ones where it is 1, the rounded blend between."""
+        self.sync_stream()
+        _, h, w, ld = x_nhwc.shape
+        assert source_u8.shape == (h, w, 3) and mask_px.shape == (h, w) and source_u8.is_contiguous() and mask_px.is_contiguous()
+        out = self._alloc((h, w, 3), torch.uint8)
+        _chk((lib().fie_pixels_out_composite_f32_u8 if self.f32 else lib().fie_pixels_out_composite_f16_u8)(
+            self.h, _p(x_nhwc), ld, h, w, _p(source_u8), _p(mask_px), _p(out)))
         return out
 
     def canny_device(self, rgb_u8, low=100, high=200):
@@ -960,6 +1001,23 @@ class Context:
         self.sync_stream()
         _chk((lib().fie_latent_prep_f32 if self.f32 else lib().fie_latent_prep)(self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab),
                                    float(sqrt_1mab), _p(latents), _p(model_in), model_in.shape[0]))
+
+    def latent_prep_src(self, moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in, z0):
+        """latent_prep() that also stores the clean source latent z0 (f32 [hw, 4]) for a masked edit."""
+        self.sync_stream()
+        _chk((lib().fie_latent_prep_src_f32 if self.f32 else lib().fie_latent_prep_src)(
+            self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab), float(sqrt_1mab), _p(latents), _p(model_in),
+            model_in.shape[0], _p(z0)))
+
+    def lcm_step_masked(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
+                        inv_sf, decode_in, mask_lat, z0, noise_init):
+        """lcm_step() followed, in the same pass, by the blend of a masked edit: latent pixels with mask_lat == 0 take
+        sab_p z0 + s1mab_p noise_init (z0 on the last step, noise None)."""
+        self.sync_stream()
+        _chk((lib().fie_lcm_step_masked_f32 if self.f32 else lib().fie_lcm_step_masked)(
+            self.h, _p(eps), eps.shape[-1], nb, float(guidance), _p(latents), _p(noise), hw, float(sab_t), float(s1mab_t), float(c_skip),
+            float(c_out), float(sab_p), float(s1mab_p), _p(model_in), model_in.shape[0] if model_in is not None else 0, float(inv_sf),
+            _p(decode_in), _p(mask_lat), _p(z0), _p(noise_init)))
 
     def lcm_step(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
                  inv_sf, decode_in):

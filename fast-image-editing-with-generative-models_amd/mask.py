@@ -1,0 +1,111 @@
+"""Host side of mask-restricted edits: mask conversion, argument checks, the feather's Gaussian taps and the
+PIE-Bench run-length code.  Device-free, so all of it runs (and is tested) on the CPU; the device side is csrc/mask.hip.
+
+A mask marks the region to edit in white.  Accepted forms: a PIL image of any mode (taken through `.convert("L")`), or a uint8 / bool
+[H, W] numpy array (bool True = 255)."""
+import math
+
+import numpy as np
+from PIL import Image
+
+MAX_BLUR = 21          # radius ceil(3 r) <= 64: the LDS bound of fie_mask_prep
+
+
+def to_l_array(mask, size=None):
+    """mask -> uint8 [H, W] numpy array (mode L).  `size` (width, height): the size the mask must have (the source image's)."""
+    if isinstance(mask, Image.Image):
+        a = np.asarray(mask.convert("L"))
+    elif isinstance(mask, np.ndarray):
+        if mask.ndim != 2:
+            raise ValueError(f"mask array must be [H, W], got shape {mask.shape}")
+        if mask.dtype == np.bool_:
+            a = mask.astype(np.uint8) * 255
+        elif mask.dtype == np.uint8:
+            a = mask
+        else:
+            raise TypeError(f"mask array dtype {mask.dtype}: uint8 or bool")
+    else:
+        raise TypeError(f"mask of type {type(mask).__name__}: a PIL image or a uint8 / bool numpy array")
+    if size is not None and (a.shape[1], a.shape[0]) != tuple(size):
+        raise ValueError(f"mask size {(a.shape[1], a.shape[0])} differs from the image size {tuple(size)}")
+    return np.array(a, dtype=np.uint8, order="C")             # a writable copy (PIL arrays are read-only)
+
+
+def check_args(mask_blur, paste_back, have_mask=True):
+    """The argument rules of a masked edit; returns mask_blur as a float."""
+    try:
+        r = float(mask_blur)
+    except (TypeError, ValueError):
+        raise ValueError(f"mask_blur={mask_blur!r}: a number") from None
+    if not (0.0 <= r <= MAX_BLUR):
+        raise ValueError(f"mask_blur={mask_blur!r}: must lie in [0, {MAX_BLUR}]")
+    if r > 0 and not have_mask:
+        raise ValueError("mask_blur needs a mask")
+    if r > 0 and not paste_back:
+        raise ValueError("mask_blur feathers the paste-back: it needs paste_back=True")
+    return r
+
+
+def blur_radius(r):
+    return int(math.ceil(3.0 * r)) if r > 0 else 0
+
+
+def gaussian_taps(r):
+    """f32 [2R + 1]: exp(-k^2 / (2 r^2)) for k = -R .. R, R = ceil(3 r), normalised to sum 1 (in float64, then rounded); [1.0] for r = 0."""
+    R = blur_radius(r)
+    if R == 0:
+        return np.ones(1, np.float32)
+    k = np.arange(-R, R + 1, dtype=np.float64)
+    g = np.exp(-k * k / (2.0 * r * r))
+    return (g / g.sum()).astype(np.float32)
+
+
+def feather_numpy(binary, r):
+    """The separable feather restated (f32, horizontal pass then vertical, taps summed in order, clamp-to-edge borders)."""
+    taps = gaussian_taps(r)
+    R = (len(taps) - 1) // 2
+    m = np.asarray(binary, np.float32)
+    if R == 0:
+        return m.copy()
+    h, w = m.shape
+    p = np.pad(m, ((0, 0), (R, R)), mode="edge")
+    acc = np.zeros((h, w), np.float32)
+    for k in range(2 * R + 1):
+        acc = acc + taps[k] * p[:, k:k + w]
+    p = np.pad(acc, ((R, R), (0, 0)), mode="edge")
+    out = np.zeros((h, w), np.float32)
+    for k in range(2 * R + 1):
+        out = out + taps[k] * p[k:k + h, :]
+    return out
+
+
+def rle_decode(encoded, shape=(512, 512)):
+    """PIE-Bench `mask` field -> uint8 [H, W] (255 = edit).  The code is a flat list [start, length, start, length, ...] of runs of ones
+    over the row-major array (0-based starts; a run is clipped at the array's end); as the benchmark's own decoder does, the 1-pixel
+    border is then set to one."""
+    enc = [int(v) for v in encoded]
+    if len(enc) % 2:
+        raise ValueError(f"run-length mask has an odd number of entries ({len(enc)})")
+    h, w = shape
+    n = h * w
+    flat = np.zeros(n, np.uint8)
+    for start, length in zip(enc[0::2], enc[1::2]):
+        if start < 0 or length < 0 or start >= n:
+            raise ValueError(f"run ({start}, {length}) outside the {h}x{w} mask")
+        flat[start:start + min(length, n - start)] = 1
+    m = flat.reshape(h, w)
+    m[0, :] = m[-1, :] = 1
+    m[:, 0] = m[:, -1] = 1
+    return m * np.uint8(255)
+
+
+def rle_encode(mask):
+    """uint8 / bool [H, W] (non-zero = edit) -> the flat [start, length, ...] list rle_decode reads."""
+    flat = (np.asarray(mask).reshape(-1) != 0).astype(np.int8)
+    d = np.diff(np.concatenate([[0], flat, [0]]))
+    starts = np.flatnonzero(d == 1)
+    ends = np.flatnonzero(d == -1)
+    out = []
+    for s, e in zip(starts, ends):
+        out += [int(s), int(e - s)]
+    return out

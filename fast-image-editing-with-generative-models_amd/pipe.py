@@ -12,6 +12,7 @@ import torch
 from PIL import Image
 
 from . import cabi, hip
+from . import mask as hmask
 from .clip import ClipText, eos_positions
 from .lcm import LCMSchedule
 from .nn import ControlNet, UNet
@@ -127,14 +128,35 @@ class HipImg2ImgPipeline:
         return torch.cat([pl, pg], dim=1), pooled
 
     def prepare(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
-                num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None):
+                num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
+                mask_image=None, mask_blur=0, paste_back=True):
         """`image` / `control_image`: PIL images, or u8 [H, W, 3] tensors already on the device (FastEditor.edit keeps the
-        resized source and its device-side Canny map in HBM instead of bouncing them through PIL)."""
+        resized source and its device-side Canny map in HBM instead of bouncing them through PIL).  `mask_image` (additive, diffusers'
+        name): restricts the edit to its white region -- a PIL image, a uint8 / bool [H, W] array, or a u8 [H, W]
+        device tensor, at the image's size; `mask_blur` feathers and `paste_back` (default) enables the paste-back of the source."""
         return self._prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, generator)
+                             controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back)
+
+    def _mask_job(self, mask_image, mask_blur, paste_back, h, w):
+        """Mask tensors of one image: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back).  The mask is
+        binarised / downsampled / feathered on the device (fie_mask_prep) on the current stream, in front of the job."""
+        r = hmask.check_args(mask_blur, paste_back, mask_image is not None)
+        if mask_image is None:
+            return None, None
+        if torch.is_tensor(mask_image):
+            if mask_image.dim() != 2 or mask_image.dtype != torch.uint8:
+                raise ValueError("a mask tensor must be u8 [H, W]")
+            if tuple(mask_image.shape) != (h, w):
+                raise ValueError(f"mask size {(mask_image.shape[1], mask_image.shape[0])} differs from the image size {(w, h)}")
+            lm = mask_image.to(self.ctx.device).contiguous()
+        else:
+            lm = torch.from_numpy(hmask.to_l_array(mask_image, (w, h))).to(self.ctx.device)
+        with self.eager_lock:                             # the context's stream binding is shared by the threads of in-flight edits
+            m_px, m_lat = self.ctx.mask_prep(lm, r)
+        return m_lat[None], (m_px[None] if paste_back else None)
 
     def _prepare(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                 controlnet_conditioning_scale, generator):
+                 controlnet_conditioning_scale, generator, mask_image=None, mask_blur=0, paste_back=True):
         """Host side of one call: argument checks, tokenisation, RNG draws (in upstream order: posterior sample, init
         noise, one per non-final step) and the H2D copies.  Returns the device-resident job for run_device()."""
         ctx = self.ctx
@@ -148,6 +170,7 @@ class HipImg2ImgPipeline:
         w, h = size_of(image)
         if h % 8 or w % 8:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {h} and {w}.")
+        mask_lat, mask_px = self._mask_job(mask_image, mask_blur, paste_back, h, w)
         steps = self.scheduler.plan(num_inference_steps, strength)
         if not steps:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of "
@@ -180,23 +203,39 @@ class HipImg2ImgPipeline:
             img_u8=u8(image), ctl_u8=u8(control_image), hw=(h, w), steps=steps, nb=nb,
             guidance=float(guidance_scale), cn_scale=float(controlnet_conditioning_scale),
             time_ids=const[0], t_dev=const[1],
-            noises=[self._randn((1, 4, lh, lw), generator) for _ in range(n_noise)])
+            noises=[self._randn((1, 4, lh, lw), generator) for _ in range(n_noise)],
+            mask_lat=mask_lat, mask_px=mask_px, mask_cfg=None if mask_lat is None else (float(mask_blur), bool(paste_back)))
 
     def prepare_batch(self, prompts, negative_prompts, images, control_images, strength=0.8, num_inference_steps=4,
-                      guidance_scale=1.5, controlnet_conditioning_scale=0.5, generators=None):
+                      guidance_scale=1.5, controlnet_conditioning_scale=0.5, generators=None, mask_image=None, mask_blur=0,
+                      paste_back=True):
         """[additive] n independent edits as ONE device job (BASELINE config "batch=8"): the UNet / ControlNet / CLIP run
         at batch n * nb, the VAE per image.  Rows are image-major ([img0 uncond, img0 cond, img1 uncond, ...]); each
         image keeps its own generator, so image i of a batch draws exactly the noise a single call with that generator
-        draws (upstream: a list of generators, one per prompt)."""
+        draws (upstream: a list of generators, one per prompt).  `mask_image`: None, or one mask per image (None in the
+        list = edit everywhere)."""
         n = len(prompts)
         if not (n == len(images) == len(control_images)) or n == 0:
             raise ValueError("prompts, images and control_images must be non-empty lists of one length")
+        masks = list(mask_image) if mask_image is not None else [None] * n
+        if len(masks) != n:
+            raise ValueError(f"{len(masks)} masks for {n} images: one mask (or None) per image")
+        masked = any(m is not None for m in masks)
+        hmask.check_args(mask_blur, paste_back, masked)
         negative_prompts = negative_prompts or [""] * n
         generators = generators or [None] * n
         jobs = [self._prepare(prompts[i], negative_prompts[i], images[i], control_images[i], strength, num_inference_steps,
-                              guidance_scale, controlnet_conditioning_scale, generators[i]) for i in range(n)]
+                              guidance_scale, controlnet_conditioning_scale, generators[i], masks[i],
+                              mask_blur if masks[i] is not None else 0, paste_back) for i in range(n)]
         if any(j["hw"] != jobs[0]["hw"] for j in jobs):
             raise ValueError("all images of a batch must have one size")
+        if masked:                                        # an image without a mask edits everywhere: an all-ones mask
+            h, w = jobs[0]["hw"]
+            for j in jobs:
+                if j["mask_lat"] is None:
+                    j["mask_lat"] = torch.ones((1, (h // 8) * (w // 8)), device=self.ctx.device, dtype=torch.uint8)
+                    j["mask_px"] = torch.ones((1, h, w), device=self.ctx.device, dtype=torch.float32) if paste_back else None
+                    j["mask_cfg"] = (float(mask_blur), bool(paste_back))
         if n == 1:
             return jobs[0]                                # the single-image job (and its graph)
         nb, t77 = jobs[0]["nb"], jobs[0]["ids_g"].shape[1]
@@ -209,6 +248,9 @@ class HipImg2ImgPipeline:
         job["ctl_u8"] = torch.stack([j["ctl_u8"] for j in jobs])
         job["t_dev"] = [t.repeat(n, 1) for t in jobs[0]["t_dev"]]
         job["noises"] = [z for j in jobs for z in j["noises"]]          # image-major: image i owns [i*k, (i+1)*k)
+        for k in ("mask_lat", "mask_px"):
+            if job[k] is not None:
+                job[k] = torch.cat([j[k] for j in jobs], dim=0)
         return job
 
     def _side_stream(self):
@@ -269,14 +311,20 @@ class HipImg2ImgPipeline:
         # 3. pixels, 5. prepare_latents: VAE posterior sample (draw #1), init noise (draw #2), add_noise -- per image (the
         # 1024^2 VAE tensors of a batch would cross the 2 GiB operand limit of the buffer-load kernels, and gain nothing)
         per = len(job["noises"]) // n                     # noise tensors per image
+        mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")     # a masked edit
         latents = torch.empty((n, hw, 4), device=dev, dtype=torch.float32)
+        z0 = torch.empty((n, hw, 4), device=dev, dtype=torch.float32) if mask_lat is not None else None
         model_in = torch.empty((n * nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
         sf = self.cfgs["vae"]["scaling_factor"]
         for i in range(n):
             x_img = ctx.pixels_in(imgs[i], True)
             moments = cabi.vae_encode(self.vae, x_img) if self.cpp_walks else self.vae.encode_moments(x_img)[0]
-            ctx.latent_prep(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
-                            steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb])
+            if mask_lat is None:
+                ctx.latent_prep(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
+                                steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb])
+            else:
+                ctx.latent_prep_src(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
+                                    steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb], z0[i])
         next_noise = 2
         main.wait_stream(side)
         self._mark("clip+vae_encode")
@@ -299,19 +347,29 @@ class HipImg2ImgPipeline:
             self._mark("unet_dec")
             for i in range(n):
                 z = None if st["last"] else job["noises"][i * per + next_noise]
-                ctx.lcm_step(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
-                             st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
-                             1.0 / sf, decode_in[i:i + 1])
+                if mask_lat is None:
+                    ctx.lcm_step(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
+                                 st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
+                                 1.0 / sf, decode_in[i:i + 1])
+                else:
+                    ctx.lcm_step_masked(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
+                                        st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
+                                        1.0 / sf, decode_in[i:i + 1], mask_lat[i], z0[i], job["noises"][i * per + 1])
             next_noise += 1
             self._mark("lcm_step")
         # 8-9. decode + postprocess
         dec = (lambda z: cabi.vae_decode(self.vae, z)) if self.cpp_walks else self.vae.decode
-        outs = [ctx.pixels_out(dec(decode_in[i:i + 1])) for i in range(n)]
+        if mask_px is None:
+            outs = [ctx.pixels_out(dec(decode_in[i:i + 1])) for i in range(n)]
+        else:                                             # paste-back of the source outside the (feathered) mask
+            outs = [ctx.pixels_out_composite(dec(decode_in[i:i + 1]), imgs[i], mask_px[i]) for i in range(n)]
         out_u8 = outs[0] if n == 1 else torch.stack(outs)
         self._mark("vae_decode")
         self.last_stats = dict(unet_evals=len(steps), cfg_batch=nb, latent_hw=(lh, lw), images=n)
         self._latents = latents
         job["_result"] = dict(stats=dict(self.last_stats), latents=latents)     # what THIS job produced (graph entries keep theirs)
+        if z0 is not None:
+            job["_result"]["z0"] = z0                     # a masked edit's clean source latents (its blend target)
         return out_u8
 
     def _run_eager(self, job):
@@ -396,6 +454,8 @@ class HipImg2ImgPipeline:
         `slot` selects an independent graph instance (own static buffers / scratch) so that several edits can be in
         flight on different streams of one GPU."""
         base = (job["hw"], job["nb"], tuple(st["t"] for st in job["steps"]), job["guidance"], job["cn_scale"], slot, job.get("n", 1))
+        if job.get("mask_lat") is not None:              # masked: (masked, mask_blur, paste_back); an unmasked key is what it was
+            base = base + ((True,) + job["mask_cfg"],)
         # A forked graph owns extra runtime streams; past ~8 such graphs in one process new ones start sharing hardware queues
         # with their own launch stream and replay 50 % slower (measured: 82 -> 125 ms, tools/edit_ab.py).  Beyond the budget a
         # new key is captured on one stream instead (87 ms): slower than a healthy forked graph, never pathological.
@@ -426,7 +486,7 @@ class HipImg2ImgPipeline:
             self._graphs[key] = self._graphs.pop(key)    # most recently used last
         graph, static, out = entry
         if static is not job:
-            for k in self._TENSOR_KEYS:
+            for k in self._tensor_keys(job):
                 static[k].copy_(job[k], non_blocking=True)
             for d, s_ in zip(static["noises"], job["noises"]):
                 d.copy_(s_, non_blocking=True)
@@ -435,9 +495,13 @@ class HipImg2ImgPipeline:
         self.last_stats = dict(static["_result"]["stats"])
         return out
 
+    def _tensor_keys(self, job):
+        """The job tensors a graph reads from its static buffers: the mask tensors of a masked job join them."""
+        return self._TENSOR_KEYS + tuple(k for k in ("mask_lat", "mask_px") if job.get(k) is not None)
+
     def _capture(self, key, job, slot):
         static = dict(job)
-        for k in self._TENSOR_KEYS:
+        for k in self._tensor_keys(job):
             static[k] = job[k].clone()
         static["noises"] = [n.clone() for n in job["noises"]]
         static["t_dev"] = [t.clone() for t in job["t_dev"]]
@@ -521,20 +585,21 @@ class HipImg2ImgPipeline:
 
     def __call__(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                  num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
-                 output_type="pil", slot=0, post_check=None, **unused):
+                 output_type="pil", slot=0, post_check=None, mask_image=None, mask_blur=0, paste_back=True, **unused):
         """`slot` (additive): independent hipGraph instance + stream, so that several calls may be in flight from different
         host threads on one GPU (graph mode only).  `post_check` (additive): a callable run after the result has reached the host
         (the stream is idle then); when it returns True the device-resident inputs have changed meanwhile and the device job is run
         again.  FastEditor.edit() passes the second half of its asynchronous device Canny: the edge map is computed with a fixed
         number of hysteresis rounds in front of the edit, and whether they had reached the fixed point is only looked at here --
-        no host wait in front of the edit, a repeated job in the rare case that they had not."""
+        no host wait in front of the edit, a repeated job in the rare case that they had not.  `mask_image` / `mask_blur` / `paste_back`
+        (additive): a mask-restricted edit (prepare(); a list of masks for a batch call)."""
         if slot and not self.use_graph:
             raise ValueError("slots > 0 need hipGraph replay (the eager path shares per-image state)")
         caller, st = torch.cuda.current_stream(self.ctx.device), self.slot_stream(slot)
         st.wait_stream(caller)                           # device-resident inputs may still be in flight on the caller's stream
         with torch.cuda.stream(st):
             out = self._call(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, generator, output_type, slot, post_check)
+                             controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back))
         caller.wait_stream(st)
         return out
 
@@ -552,11 +617,11 @@ class HipImg2ImgPipeline:
         return host.numpy().copy()
 
     def _call(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-              controlnet_conditioning_scale, generator, output_type, slot, post_check=None):
+              controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_args=(None, 0, True)):
         if isinstance(prompt, (list, tuple)):            # [additive] a batch: lists of prompts / images / generators
             job = self.prepare_batch(list(prompt), negative_prompt if isinstance(negative_prompt, (list, tuple)) else None,
                                      list(image), list(control_image), strength, num_inference_steps, guidance_scale,
-                                     controlnet_conditioning_scale, generator if isinstance(generator, (list, tuple)) else None)
+                                     controlnet_conditioning_scale, generator if isinstance(generator, (list, tuple)) else None, *mask_args)
             out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
             arr = self._to_host(out_u8, slot)
             if post_check is not None and post_check():
@@ -567,7 +632,7 @@ class HipImg2ImgPipeline:
                 return types.SimpleNamespace(images=list(arr))
             return types.SimpleNamespace(images=[Image.fromarray(a) for a in arr])
         job = self.prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps,
-                           guidance_scale, controlnet_conditioning_scale, generator)
+                           guidance_scale, controlnet_conditioning_scale, generator, *mask_args)
         out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
         if output_type == "latent":
             res = job["_result"]

@@ -511,6 +511,44 @@ int fie_canny_rgb_device_finish_u8(fie_ctx* ctx, int H, int W, void* workspace, 
 int fie_resize_rgb_u8(fie_ctx* ctx, const uint8_t* src, int H, int W, uint8_t* dst, int OH, int OW, const int* kx,
                       const int* bx, int ksx, const int* ky, const int* by, int ksy, uint8_t* tmp);
 
+/* ---- K13 on one band: LANCZOS resize of a u8 [H, W] mode-L image (an edit mask), bit-exact with Pillow's
+ *   `mask.convert("L").resize(..., Image.LANCZOS)`; arguments and coefficient tables as fie_resize_rgb_u8, tmp [H, OW]. */
+int fie_resize_l_u8(fie_ctx* ctx, const uint8_t* src, int H, int W, uint8_t* dst, int OH, int OW, const int* kx,
+                    const int* bx, int ksx, const int* ky, const int* by, int ksy, uint8_t* tmp);
+
+/* ---- Mask-restricted edits.  In an edit, in order:
+ *   1. fie_resize_l_u8 (when the mask is not at the edit size), then fie_mask_prep: mask_l u8 [H, W] (white = edit) ->
+ *      mask_px f32 [H, W] (L >= 128 as 0 / 1, feathered by a separable Gaussian when radius > 0) and mask_lat u8 [H/8 * W/8]
+ *      (mask_lat[y][x] = binary mask at [8y][8x]).  taps: f32 [2 * radius + 1], the normalised Gaussian of sigma r sampled at
+ *      -R .. R (radius R = ceil(3r) <= 64; {1.0f} with radius 0); borders clamp to the edge.  One launch.
+ *   2. fie_latent_prep_src in place of fie_latent_prep: also stores the clean source latent z0_out f32 [H*W, 4] (latent pixels).
+ *   3. fie_lcm_step_masked in place of fie_lcm_step, every step: after the step, latent pixels where mask_lat == 0 take
+ *      sqrt_ab_prev * z0 + sqrt_1mab_prev * noise_init (noise_init: the init noise of fie_latent_prep, f32 [4, H*W]), or z0 on
+ *      the last step (noise == NULL); model_in / decode_in are written from the blended latents.
+ *   4. fie_pixels_out_composite_* in place of fie_pixels_out_* (paste-back; without it keep fie_pixels_out_*): source u8
+ *      [H, W, 3] (the resized source image) where mask == 0, the decoded byte where mask == 1, rint(m d + (1 - m) source)
+ *      between, d the unrounded clamp(x / 2 + 0.5, 0, 1) * 255.  mask: fie_mask_prep's mask_px (16-byte aligned). */
+int fie_mask_prep(fie_ctx* ctx, const uint8_t* mask_l, int H, int W, const float* taps, int radius, float* mask_px,
+                  uint8_t* mask_lat);
+int fie_latent_prep_src(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW,
+                        float scaling_factor, float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in,
+                        int copies, float* z0_out);
+int fie_latent_prep_src_f32(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW,
+                            float scaling_factor, float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in,
+                            int copies, float* z0_out);
+int fie_lcm_step_masked(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents,
+                        const float* noise, int64_t HW, float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out,
+                        float sqrt_ab_prev, float sqrt_1mab_prev, void* model_in, int copies, float inv_scaling,
+                        void* decode_in, const uint8_t* mask_lat, const float* z0, const float* noise_init);
+int fie_lcm_step_masked_f32(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents,
+                            const float* noise, int64_t HW, float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out,
+                            float sqrt_ab_prev, float sqrt_1mab_prev, void* model_in, int copies, float inv_scaling,
+                            void* decode_in, const uint8_t* mask_lat, const float* z0, const float* noise_init);
+int fie_pixels_out_composite_f16_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, const uint8_t* source,
+                                    const float* mask, uint8_t* dst);
+int fie_pixels_out_composite_f32_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, const uint8_t* source,
+                                    const float* mask, uint8_t* dst);
+
 #ifdef __cplusplus
 }
 #endif

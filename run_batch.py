@@ -74,6 +74,14 @@ def build_parser():
     return p
 
 
+def add_mask_args(p):
+    """[additive] mask-restricted edits.  Kept apart from build_parser(), whose flag set is the reference's plus the additive ones above."""
+    p.add_argument("--use_mask", action="store_true",
+                   help="[additive] restrict each edit to the item's PIE-Bench `mask` (run-length code over the 512x512 image); the "
+                        "background is pasted back from the source.  An item without a mask fails loudly")
+    return p
+
+
 def select_entries(mapping, args, say=print):
     """Reference :115-140: explicit ids win; else filter by type, then truncate to --num_images."""
     if args.image_ids:
@@ -151,7 +159,8 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     res = dict(processed=0, skipped=0, failed=0, total_time=0.0, rows=[])
     extra = {} if args.strength is None else {"strength": args.strength}
     bs = max(1, getattr(args, "batch_size", 1))
-    pending = []                                   # (index, image_id, rel, output_path, source_img, prompt) awaiting one device job
+    use_mask = getattr(args, "use_mask", False)
+    pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
     def flush():
         if not pending:
@@ -161,12 +170,14 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
         try:
             t0 = time.time()
             if bs == 1:
-                edited = [editor.edit(image=pending[0][4], prompt=pending[0][5], negative_prompt=args.negative_prompt, **kw)]
+                mkw = dict(mask=pending[0][6]) if use_mask else {}
+                edited = [editor.edit(image=pending[0][4], prompt=pending[0][5], negative_prompt=args.negative_prompt, **kw, **mkw)]
             else:
+                mkw = dict(masks=[p[6] for p in pending]) if use_mask else {}
                 edited = editor.edit_batch(images=[p[4] for p in pending], prompts=[p[5] for p in pending],
-                                           negative_prompts=[args.negative_prompt] * len(pending), **kw)
+                                           negative_prompts=[args.negative_prompt] * len(pending), **kw, **mkw)
             dt = (time.time() - t0) / len(pending)
-            for (index, image_id, rel, output_path, source_img, prompt), out in zip(pending, edited):
+            for (index, image_id, rel, output_path, source_img, prompt, _), out in zip(pending, edited):
                 res["total_time"] += dt
                 out.save(output_path)
                 res["processed"] += 1
@@ -198,7 +209,15 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
             if not prompt:
                 res["failed"] += 1
                 continue
-            pending.append((index, image_id, rel, output_path, source_img, prompt))
+            mask = None
+            if use_mask:
+                if not entry.get("mask"):
+                    print(f"\n      Error processing {image_id}: --use_mask but the entry has no `mask`")
+                    res["failed"] += 1
+                    continue
+                from fie_amd import mask as hmask
+                mask = hmask.rle_decode(entry["mask"], (source_img.height, source_img.width))
+            pending.append((index, image_id, rel, output_path, source_img, prompt, mask))
             if len(pending) == bs:
                 flush()
         except FileNotFoundError as e:
@@ -235,7 +254,7 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = add_mask_args(build_parser()).parse_args(argv)
     import fie_amd  # noqa: F401
     from fie_amd import dist as fdist
     rank, local, world = fdist.init()

@@ -42,6 +42,9 @@ def build_parser():
     a("--show_plot", action="store_true", help="Show comparison plot")
     a("--strength", type=float, default=None, help="[additive] img2img strength (default: FastEditor.edit's 0.80)")
     a("--weights_dir", type=str, default=None, help="[additive] local diffusers-layout weights directory")
+    a("--mask", type=str, default=None, help="[additive] mask image (white = edit): only that region changes")
+    a("--mask_blur", type=float, default=0, help="[additive] with --mask: Gaussian feather (sigma, pixels) of the paste-back seam")
+    a("--no_paste_back", action="store_true", help="[additive] with --mask: blend in latent space only, no paste-back of the source")
     return p
 
 
@@ -92,6 +95,12 @@ def main(argv=None):
     print(f"      Prompt: {args.prompt}")
     print(f"      Steps: {args.steps}, Guidance: {args.guidance}, Control Scale: {args.control_scale}")
     extra = {} if args.strength is None else {"strength": args.strength}
+    if args.mask is not None:
+        if not os.path.exists(args.mask):
+            print(f"Error: Mask not found at {args.mask}")
+            return
+        extra.update(mask=Image.open(args.mask), mask_blur=args.mask_blur, paste_back=not args.no_paste_back)
+        print(f"      Mask: {args.mask} (blur {args.mask_blur}, paste-back {'off' if args.no_paste_back else 'on'})")
     t0 = time.time()
     edited_img = editor.edit(image=source_img, prompt=args.prompt, negative_prompt=args.negative_prompt,
                              num_inference_steps=args.steps, guidance_scale=args.guidance,

@@ -15,6 +15,7 @@ from PIL import Image
 
 import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory)
 from fie_amd import hip, stack
+from fie_amd import mask as hmask
 from fie_amd.pipe import HipImg2ImgPipeline
 
 
@@ -137,8 +138,14 @@ class FastEditor:
         return Image.fromarray(self._canny_device(image, low_threshold, high_threshold)[1].cpu().numpy())
 
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
-             controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None):
-        """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274)."""
+             controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
+             paste_back=True):
+        """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
+        [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
+        latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
+        for byte; `mask_blur` r > 0 feathers the paste-back seam with a Gaussian of sigma r."""
+        hmask.check_args(mask_blur, paste_back, mask is not None)
+        mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
         generator = None
         if seed is not None:
             generator = torch.Generator(device=self.device).manual_seed(seed)
@@ -152,18 +159,35 @@ class FastEditor:
         # run and the device job is repeated on the final edge map -- same result as preprocess_image() + the pipeline call, always
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=(1024, 1024), wait=False)
+            mask_dev = self._mask_device(mask_l, (1024, 1024))
         return self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev,
                          control_image=control_dev, strength=strength, num_inference_steps=num_inference_steps,
                          guidance_scale=guidance_scale, controlnet_conditioning_scale=controlnet_conditioning_scale,
-                         generator=generator, post_check=finish).images[0]
+                         generator=generator, post_check=finish, mask_image=mask_dev, mask_blur=mask_blur, paste_back=paste_back).images[0]
+
+    def _mask_device(self, mask_l, size):
+        """uint8 [H, W] mode-L mask (or None) -> u8 [size[1], size[0]] on the device: LANCZOS-resized as the source is (fie_resize_l_u8,
+        bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`)."""
+        if mask_l is None:
+            return None
+        m = torch.from_numpy(mask_l).to(self.pipe.ctx.device)
+        if (m.shape[1], m.shape[0]) != tuple(size):
+            m = self.pipe.ctx.resize_lanczos(m, size[1], size[0])
+        return m
 
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
-                   controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None):
+                   controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
+                   paste_back=True):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
-        edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects."""
+        edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
+        `masks`: None, or one mask per image as edit()'s `mask` (None in the list: that image is edited everywhere)."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
+        if masks is not None and len(masks) != len(images):
+            raise ValueError(f"{len(masks)} masks for {len(images)} images: one mask (or None) per image")
+        hmask.check_args(mask_blur, paste_back, masks is not None and any(m is not None for m in masks))
+        mask_ls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks, images)] if masks is not None else None
         gens = None
         if seed is not None:
             gens = [torch.Generator(device=self.device).manual_seed(seed) for _ in images]
@@ -174,9 +198,11 @@ class FastEditor:
                 s_dev, c_dev = self._canny_device(im, canny_low_threshold, canny_high_threshold, size=(1024, 1024))
                 srcs.append(s_dev)
                 ctls.append(c_dev)
+            mask_devs = [self._mask_device(m, (1024, 1024)) for m in mask_ls] if mask_ls is not None else None
         return self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls,
                          strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                         controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens).images
+                         controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens, mask_image=mask_devs,
+                         mask_blur=mask_blur, paste_back=paste_back).images
 
     def calibrate_fp8(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                       controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=0, margin=2.0):
