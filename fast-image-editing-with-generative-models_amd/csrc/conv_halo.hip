@@ -266,7 +266,12 @@ constexpr int n2_wait(int var, bool res, int kind, int t) {
 }
 static_assert(n2_tail(true, K_LAST_F, 8) == 0 && n2_tail(true, K_FIRST, 8) == 0 && n2_st(0, K_FIRST, 8) == 0, "tap 8 carries nothing behind its weights");
 
-template <bool RES, bool GN, bool RB, int VAR, bool STAMP, bool SIDE = false, bool GNA = false>
+// EDGE (tile code 78): maps whose height or width is not a multiple of 16.  The patch grid is rounded up, so the patches of the bottom row and the
+// right column reach past the image: their halo pixels outside it read zeros through the range check like every padding pixel, the MFMAs run on
+// them unchanged, and the stores of output pixels outside the image go to kOob per lane (the range check drops them: a plain pixel offset would
+// land in the next row or image).  Stores are never counted in the waits (n2_tail), so stores whose lanes are all dropped cannot let a DMA piece
+// through.  No GroupNorm sums (the granule layout assumes whole patches: the launcher refuses them) and 16-byte stores only
+template <bool RES, bool GN, bool RB, int VAR, bool STAMP, bool SIDE = false, bool GNA = false, bool EDGE = false>
 __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
     constexpr int FM = 4, FN = 4, WN = 64;
     constexpr bool ST16 = (VAR & 2) != 0, STM = (VAR & 4) != 0, IM = (VAR & 8) != 0;
@@ -275,6 +280,7 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
     // groups wait for; the 16-byte stores' lane swap moves to the store slot for the same reason (the sums want the unswapped layout)
     constexpr bool DEFER = ST16 && STM && !IM;
     static_assert(!(SIDE && (RES || RB)), "1x1 side inputs belong to a resnet's conv2 + shortcut: no residual, no row bias");
+    static_assert(!EDGE || (ST16 && !GN && !GNA), "edge patches: 16-byte stores, no GroupNorm sums");
     extern __shared__ __attribute__((aligned(16))) half_t smem[];
     char* const lds = reinterpret_cast<char*>(smem);
 
@@ -289,7 +295,7 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
     const int ntiles = p.nbm * p.nbn;
     const int bid = xcd_remap(blockIdx.x, G);
     const int n0 = (bid % p.nbn) * BNH;
-    const int ppr = p.OW >> 4, ppi = (p.OH >> 4) * ppr;
+    const int ppr = EDGE ? (p.OW + 15) >> 4 : p.OW >> 4, ppi = (EDGE ? (p.OH + 15) >> 4 : p.OH >> 4) * ppr;
     const int ncol = n0 + wn * WN + fq * 4;                     // this lane's first output channel
 
     const int live = p.probe == 1 ? 0 : 1;
@@ -377,6 +383,19 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
         return ((unsigned)(m0 + wm * FM * p.OW + fr) * (unsigned)ld + (unsigned)ncol) * 2u;        // N % 128 == 0 (launcher): every wave's channels are inside the matrix
     };
     const unsigned c_jstep = (unsigned)p.OW * (unsigned)p.ldc * 2u, r_jstep = (unsigned)p.OW * (unsigned)p.ldr * 2u;
+    // EDGE: the corner of the tile whose outputs the deferred stores write (block-uniform), and the store offset of fragment-pair row j of this lane
+    // (ST16: pixel (wm * 4 + j + (fq & 1), fr) of the patch) or kOob when that pixel lies outside the image or the wave's 64 channels past N (N % 64 == 0:
+    // the third column tile of a 320-channel conv)
+    int y0_prev = 0, x0_prev = 0;
+    const bool wave_in_n = n0 + wn * WN < p.N;
+    auto edge_off = [&](unsigned off, int j) -> unsigned {
+        if constexpr (EDGE) {
+            const bool in = wave_in_n && x0_prev + fr < p.OW && y0_prev + wm * FM + j + (fq & 1) < p.OH;
+            return in ? off : kOob;
+        } else {
+            return off;
+        }
+    };
 
     f32x4 acc[FN][FM];
 #pragma unroll
@@ -527,7 +546,7 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
                     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v[0]), "+v"(v[2]));
                     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v[1]), "+v"(v[3]));
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(v, rs_c, ro_prev + (unsigned)(2 * JJ) * c_jstep + (unsigned)(I * 32), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(v, rs_c, edge_off(ro_prev + (unsigned)(2 * JJ) * c_jstep + (unsigned)(I * 32), 2 * JJ), 0, 0);
             } else {
                 const int k = 2 * T + s, j = k / FN, i = k % FN;
                 __builtin_amdgcn_raw_buffer_store_b64(outp[i][j], rs_c, ro_prev + (unsigned)j * c_jstep + (unsigned)(i * 32), 0, 0);
@@ -538,7 +557,10 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
         // MFMAs and the barrier, and no counted wait lies between their issue and their use at the tile end (where every older DMA has landed too)
         auto resload1 = [&](int k) {
             const int j = k / FN, i = k % FN;
-            outp[i][j] = __builtin_amdgcn_raw_buffer_load_b64(rs_r, rr_cur + (unsigned)j * r_jstep + (unsigned)(i * 32), 0, 0);
+            unsigned off = rr_cur + (unsigned)j * r_jstep + (unsigned)(i * 32);
+            // EDGE: a pixel outside the image (or channels past N) reads element 0 instead -- an in-range load whose value no store uses
+            if constexpr (EDGE) off = wave_in_n && x0 + fr < p.OW && y0 + wm * FM + j < p.OH ? off : 0u;
+            outp[i][j] = __builtin_amdgcn_raw_buffer_load_b64(rs_r, off, 0, 0);
         };
         // DEFER && GN: piece q of the sums of the previous tile's fragment pair (JJ, I) = (T / 4, T % 4), one piece behind every second MFMA.  The lane holds
         // 4 channels (one quad) of pixel fr in patch rows 2 JJ and 2 JJ + 1: v_dot2_f32_f16 sums the f16-rounded values and their squares in fp32, four
@@ -868,6 +890,7 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
         }
         tile_end(m0, img);
         ro_prev = ST16 ? row_off16(m0, p.ldc) : row_off(m0, p.ldc);
+        if constexpr (EDGE) { y0_prev = y0; x0_prev = x0; }
         if constexpr (GN && DEFER) {
             // slot of this wave's patch-row pair 0: granule = (row pair of the image, 16-pixel column segment) as in the tile-end form; + n0's first group
             const int gn_nch = p.gn_nch ? p.gn_nch : p.gn_rows >> 5;
@@ -926,7 +949,7 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
                     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v[0]), "+v"(v[2]));
                     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v[1]), "+v"(v[3]));
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(v, rs_c, ro_prev + (unsigned)(2 * jj) * c_jstep + (unsigned)(i * 32), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(v, rs_c, edge_off(ro_prev + (unsigned)(2 * jj) * c_jstep + (unsigned)(i * 32), 2 * jj), 0, 0);
             }
     } else {
 #pragma unroll
@@ -946,9 +969,9 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
     }
 }
 
-template <bool RES, bool GN, bool RB, int VAR, bool STAMP>
+template <bool RES, bool GN, bool RB, int VAR, bool STAMP, bool SIDE = false, bool GNA = false, bool EDGE = false>
 hipError_t halo2_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo2_kernel<RES, GN, RB, VAR, STAMP>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsHalo);
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo2_kernel<RES, GN, RB, VAR, STAMP, SIDE, GNA, EDGE>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsHalo);
 }
 
 }  // namespace
@@ -974,6 +997,10 @@ int fie_conv_halo_init(void) {
     if (e == hipSuccess) e = halo2_attr<true, true, false, 6, true>();
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo2_kernel<false, true, false, 6, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsHalo + 8192);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo2_kernel<true, true, false, 6, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsHalo + 8192);
+    if (e == hipSuccess) e = halo2_attr<false, false, false, 6, false, false, false, true>();
+    if (e == hipSuccess) e = halo2_attr<true, false, false, 6, false, false, false, true>();
+    if (e == hipSuccess) e = halo2_attr<false, false, true, 6, false, false, false, true>();
+    if (e == hipSuccess) e = halo2_attr<false, false, false, 6, false, true, false, true>();
     if (e != hipSuccess) {
         fie_set_error("conv_halo: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         return FIE_EHIP;
@@ -993,6 +1020,26 @@ bool fie_conv_halo_ok(const GemmArgs& a) {
            !a.res && !a.rowbias && a.act == FIE_ACT_NONE && a.scale == 1.f && a.lda2 * 2 * (int64_t)a.OW * a.OH < (1ll << 31) && a.lda3 * 2 * (int64_t)a.OW * a.OH < (1ll << 31);
 }
 
+// Edge patches (tile code 78): the same conv on maps whose height or width is NOT a multiple of 16 (at least one side; maps of whole patches keep
+// codes 71-76, so no shape changes kernels), in the persistent form only, so everything that form asks for: Cin >= 128, no activation / scale, row bias
+// and residual never together.  N % 64 == 0 (not 128): a wave whose 64 channels lie past N drops its stores per lane like a pixel outside the image;
+// its weight rows are the packing's zero rows (Npad = N rounded up to 128), so every DMA piece is a real load.  No GroupNorm sums (their granules are 32-pixel halves of whole patches)
+bool fie_conv_halo_edge_ok(const GemmArgs& a) {
+    const bool base = a.stride == 1 && !a.ups && !a.taps2 && !a.oscat && a.pt == 1 && a.pl == 1 && a.H == a.OH && a.W == a.OW && a.OH > 0 && a.OW > 0 &&
+                      (a.OH % 16 != 0 || a.OW % 16 != 0) && a.M % (a.OH * a.OW) == 0 && a.Cin % BK == 0 && a.Cin >= 2 * BK && !a.w_scale && !a.out_f8 &&
+                      a.splitk <= 1 && a.N % 64 == 0 && a.ldc >= a.N && !a.gn_partial && !a.gna_tab && a.act == FIE_ACT_NONE && a.scale == 1.f && !(a.rowbias && a.res);
+    if (!base) return false;
+    if (!a.A2) return !a.A3 && a.K == 9 * a.Cin;
+    return a.C2x % BK == 0 && a.C3x % BK == 0 && a.C2x > 0 && (a.A3 != nullptr) == (a.C3x > 0) && a.K == 9 * a.Cin + a.C2x + a.C3x && !a.res && !a.rowbias &&
+           a.lda2 * 2 * (int64_t)a.OW * a.OH < (1ll << 31) && a.lda3 * 2 * (int64_t)a.OW * a.OH < (1ll << 31);
+}
+
+// 16x16 patches of the output (the row blocks of the halo-resident kernels), partial ones at the edges counted
+int64_t fie_conv_halo_patches(const GemmArgs& a) {
+    if (a.OH <= 0 || a.OW <= 0) return 0;
+    return (int64_t)(a.M / (a.OH * a.OW)) * ((a.OH + 15) / 16) * ((a.OW + 15) / 16);
+}
+
 // GNA (the input's GroupNorm + SiLU applied on the resident halo): the persistent form, ONE image, GroupNorm sums armed for the output (every resnet conv
 // of the VAE has them), no row bias, no side inputs, Cin <= 1024 (an 8 KiB coefficient table behind the dump), as many column tiles as fit the grid
 bool fie_conv_halo_gna_ok(const GemmArgs& a) {
@@ -1006,8 +1053,26 @@ bool fie_conv_halo_gna_ok(const GemmArgs& a) {
 // segments (72; with at most one tile per block it runs as v1: nothing to defer into), 4 = v2 with stamps (74), 5 = v2 with 8-byte stores issued in
 // the load segments (76: the first form, kept for A/B).  Measured and not kept (profiles/r04_halo_conv.md): the stores counted in the waits
 // (a race), every vector-memory instruction issued from inside the MFMA segment (no faster), the second k half's fragments read under the MFMAs
-// (slower)
+// (slower), 6 = v2 with edge patches (78: maps with a side that is not a multiple of 16)
 int fie_launch_conv_halo(fie_ctx* ctx, GemmArgs& a, int variant) {
+    if (variant == 6) {                                        // edge patches (code 78): persistent blocks, always (the one-tile form has no per-pixel stores)
+        FIE_REQUIRE(fie_conv_halo_edge_ok(a), "halo-resident conv with edge patches (tile code 78): stride-1 same-size 3x3 conv with H or W %% 16 != 0, Cin %% 64 == 0, "
+                    "Cin >= 128, N %% 64 == 0, no activation / scale / GroupNorm sums only");
+        a.frag_ld = a.OW;
+        a.nbn = (a.N + BNH - 1) / BNH;
+        a.nbm = (int)fie_conv_halo_patches(a);
+        const int tiles = a.nbm * a.nbn;
+        int g = tiles < ctx->num_cus ? tiles : ctx->num_cus;
+        g -= g % a.nbn;
+        FIE_REQUIRE(g >= a.nbn && a.nbn <= ctx->num_cus, "halo-resident conv: more column tiles than CUs");
+        const dim3 grid((unsigned)g);
+        if (a.A2) fie_launch(ctx, (conv_halo2_kernel<false, false, false, 6, false, true, false, true>), grid, dim3(512), kLdsHalo, a);
+        else if (a.res) fie_launch(ctx, (conv_halo2_kernel<true, false, false, 6, false, false, false, true>), grid, dim3(512), kLdsHalo, a);
+        else if (a.rowbias) fie_launch(ctx, (conv_halo2_kernel<false, false, true, 6, false, false, false, true>), grid, dim3(512), kLdsHalo, a);
+        else fie_launch(ctx, (conv_halo2_kernel<false, false, false, 6, false, false, false, true>), grid, dim3(512), kLdsHalo, a);
+        FIE_LAUNCH_CHECK();
+        return FIE_OK;
+    }
     FIE_REQUIRE(fie_conv_halo_ok(a), "halo-resident conv: stride-1 same-size 3x3 conv with H, W %% 16 == 0 and Cin %% 64 == 0 only");
     a.frag_ld = a.OW;
     a.nbn = (a.N + BNH - 1) / BNH;

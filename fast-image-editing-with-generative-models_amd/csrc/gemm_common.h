@@ -648,6 +648,8 @@ int fie_gemm_init(void);           // same for the kernels of gemm_conv.hip
 // conv_halo.hip: the halo-resident 3x3 conv (tile code 71; 73 = with cycle stamps): a block = a 16x16 output patch x 128 channels
 int fie_launch_conv_halo(fie_ctx* ctx, fie_gemm::GemmArgs& a, int stamped);
 bool fie_conv_halo_ok(const fie_gemm::GemmArgs& a);
+bool fie_conv_halo_edge_ok(const fie_gemm::GemmArgs& a);     // tile code 78: edge patches (a side not a multiple of 16)
+int64_t fie_conv_halo_patches(const fie_gemm::GemmArgs& a);  // 16x16 output patches, partial ones included
 // conv_thin.hip: 3x3 convs with at most 16 output channels (tile code 77): direct global -> VGPR operands, a wave = a 16-pixel strip x all channels
 int fie_launch_conv_thin(fie_ctx* ctx, fie_gemm::GemmArgs& a);
 bool fie_conv_thin_ok(const fie_gemm::GemmArgs& a);

@@ -665,12 +665,15 @@ constexpr bool is_ln_code(int code) { return code == 42 || code == 96 || code ==
 //                  K is summed chunk-major (the im2col kernels: tap-major): equal to the other codes to rounding, not bit for bit
 //   72 / 74 / 76   conv_halo2_kernel: the same K loop in persistent blocks that prefetch their next tile and defer a tile's stores into the next
 //                  tile's first chunk (74: with cycle stamps, 76: the 8-byte-store form, A/B); THE RULE for eligible convs (heuristic_code)
+//   78             conv_halo2_kernel with edge patches: maps whose height or width is not a multiple of 16 (the aspect-ratio buckets); the patch grid
+//                  is rounded up, stores of pixels outside the image are dropped per lane; no GroupNorm sums.  The rule for eligible convs, under 72's
+//                  threshold.  Sums chunk-major like 71-76
 struct TileDim { int code, bm, bn; };
 constexpr TileDim kTiles[] = {{1, 128, 128}, {2, 128, 64}, {3, 64, 64}, {42, 128, 64}, {43, 64, 64},
                               {51, 128, 128}, {61, 256, 256}, {62, 256, 128}, {81, 256, 256}, {82, 256, 256},
                               {63, 256, 320}, {95, 128, 128}, {96, 256, 128}, {97, 256, 128}, {98, 256, 128}, {94, 128, 64},
                               {52, 128, 128}, {47, 128, 96}, {54, 192, 128}, {46, 64, 64}, {44, 128, 64}, {48, 128, 80}, {64, 256, 320},
-                              {71, 256, 128}, {73, 256, 128}, {72, 256, 128}, {74, 256, 128}, {76, 256, 128}, {77, 64, 16}};
+                              {71, 256, 128}, {73, 256, 128}, {72, 256, 128}, {74, 256, 128}, {76, 256, 128}, {77, 64, 16}, {78, 256, 128}};
 
 // Heuristic tile code for a shape (the default; the autotuner below and the debug hooks can replace it).
 template <int MODE>
@@ -690,6 +693,13 @@ int heuristic_code(const fie_ctx* ctx, const GemmArgs& a, bool dma_ok) {
         // (conv_halo.hip; persistent, deferred stores).  Measured against every im2col code on the VAE's and the UNet's 64x64 / 128x128-latent
         // shapes: -15 to -35 % (profiles/r04_halo_conv.md)
         code = 72;
+    } else if (MODE == 1 && fie_conv_halo_edge_ok(a) && 4 * fie_conv_halo_patches(a) * ((a.N + 127) / 128) >= 3 * cus && a.C2x + a.C3x <= 4 * BK &&
+               std::find(std::begin(ctx->tune_exclude), std::end(ctx->tune_exclude), 78) == std::end(ctx->tune_exclude)) {      // fie_debug_tune_exclude("78"): the A/B switch
+        // the same kernel on maps with a side that is not a multiple of 16 (the aspect-ratio buckets: 72x56, 152x104, 38x26, ...): partial patches at
+        // the right and bottom edges.  Measured against every im2col code on the buckets' UNet maps (profiles/resolution_buckets.md): 0.84-0.86x the
+        // best on the 640-channel maps, 0.97-0.98x on the 320-channel ones; 1.07-1.14x on the 1280-channel maps, which have 120 tiles and stay under
+        // this threshold (so the rule keeps their im2col code)
+        code = 78;
     } else if (MODE == 1) {
         if (!a.A2 && ((b256 >= cus && (a.N % 256 == 0 || (a.N % 128 != 0 && a.K >= 5760))) ||        // 256x256 phased: VAE 256/512-ch maps, 128x128-latent convs into 320 ch (not with 1x1 side inputs: ring kernels only)
             (a.N % 256 == 0 && a.K >= 8192 && 2 * b256 >= cus))) code = 81;                  // ... and the long-K upsampling convs of the 32x32 level
@@ -743,6 +753,8 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
     FIE_REQUIRE(!(a.taps2 && (code < 40 || a.w_scale)), "tile code %d: the 2x2 parity convs run on the f16 LDS-DMA kernels only", code);
     FIE_REQUIRE(!(MODE == 1 && a.A2 && (code < 40 || code == 81 || code == 82 || a.w_scale)), "tile code %d: conv + 1x1 side inputs run on the f16 ring kernels and the halo-resident kernel (72) only", code);
     FIE_REQUIRE(!((code >= 71 && code <= 76) && (MODE != 1 || !dma_ok || !fie_conv_halo_ok(a))), "tile code %d (halo-resident conv): stride-1 same-size 3x3 conv with H, W %% 16 == 0, Cin %% 64 == 0, f16 weights only", code);
+    FIE_REQUIRE(!(code == 78 && (MODE != 1 || !dma_ok || !fie_conv_halo_edge_ok(a))), "tile code 78 (halo-resident conv, edge patches): stride-1 same-size 3x3 conv with H or W %% 16 != 0, "
+                "Cin %% 64 == 0, Cin >= 128, N %% 64 == 0, f16 weights, no activation / scale / GroupNorm sums only");
     if (order < 0) {
         // Tile order = which operand an XCD re-streams past its 4 MiB L2.  Consecutive tile ids run on one XCD (xcd_remap), so an
         // XCD owns T/8 consecutive tiles: with n fastest that is `dm` row blocks x up to all column tiles, with m fastest the
@@ -783,7 +795,7 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
     a.probe = ctx->gemm_probe;
     a.epi_prefetch = ctx->epi_prefetch;
     a.stamps = (code == 97 || code == 98 || code == 94 || code == 73 || code == 74) ? ctx->gemm_stamps : nullptr;
-    snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "%s<%dx%d> (%s, tile code %d)", code >= 90 ? "gemm3_kernel+prefetch" : code >= 80 ? "gemm8_kernel" : code == 77 ? "conv_thin_kernel" : code >= 71 && code <= 76 ? (code == 71 || code == 73 ? "conv_halo_kernel" : "conv_halo2_kernel") : code >= 40 ? "gemm3_kernel" : "gemm_kernel",
+    snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "%s<%dx%d> (%s, tile code %d)", code >= 90 ? "gemm3_kernel+prefetch" : code >= 80 ? "gemm8_kernel" : code == 77 ? "conv_thin_kernel" : code >= 71 && code <= 76 ? (code == 71 || code == 73 ? "conv_halo_kernel" : "conv_halo2_kernel") : code == 78 ? "conv_halo2_kernel+edge" : code >= 40 ? "gemm3_kernel" : "gemm_kernel",
              t->bm, t->bn, MODE == 1 ? "conv3x3" : "gemm", code);
     if (split > 1) snprintf(ctx->last_kernel + strlen(ctx->last_kernel) - 1, 24, ", split-K %d)", split);
     if (ctx->oplog) {
@@ -857,6 +869,7 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
         case 76: return fie_launch_conv_halo(ctx, a, 5);
         case 74: return fie_launch_conv_halo(ctx, a, 4);
         case 77: return fie_launch_conv_thin(ctx, a);
+        case 78: return fie_launch_conv_halo(ctx, a, 6);
         case 81: return fie_launch_gemm8(ctx, a, MODE == 1, 0);
         case 82: return fie_launch_gemm8(ctx, a, MODE == 1, 1);   // A/B: second DMA piece of a phase issued from inside the MFMA cluster (measured slower)
     }
@@ -882,7 +895,7 @@ constexpr size_t kFlushBytes = 384u << 20;
 // autotune below times exactly this list; fie_debug_tune_candidates reports it (tests/test_launch_table_gpu.py runs every entry at the product's shapes).
 template <int MODE>
 std::vector<int> tune_candidates(const fie_ctx* ctx, const GemmArgs& a, int guess) {
-    static const int kRing[] = {43, 46, 42, 44, 51, 52, 54, 96, 81, 63, 47, 48, 64, 72};      // 47 (128x96): FIE_TUNE_47=0 leaves it out
+    static const int kRing[] = {43, 46, 42, 44, 51, 52, 54, 96, 81, 63, 47, 48, 64, 72, 78};      // 47 (128x96): FIE_TUNE_47=0 leaves it out
     static const bool use47 = !(getenv("FIE_TUNE_47") && getenv("FIE_TUNE_47")[0] == '0');
     static const int kW8[] = {43, 42, 62, 52, 54};
     static const int kX8[] = {43, 42, 47, 51, 52, 54, 62, 63};
@@ -890,7 +903,7 @@ std::vector<int> tune_candidates(const fie_ctx* ctx, const GemmArgs& a, int gues
     auto blocks = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
     const bool x8 = a.w_scale && a.a_scale != 0.f;
     const int* cand = x8 ? kX8 : a.w_scale ? kW8 : kRing;
-    const int ncand = x8 ? 8 : a.w_scale ? 5 : 14;
+    const int ncand = x8 ? 8 : a.w_scale ? 5 : 15;
     auto excluded = [&](int c) {
         for (int e : ctx->tune_exclude)
             if (e == c) return e != 0;
@@ -908,6 +921,7 @@ std::vector<int> tune_candidates(const fie_ctx* ctx, const GemmArgs& a, int gues
         if (x8 && (c == 62 || c == 51) && 2 * blocks(c == 62 ? 256 : 128, 128) < ctx->num_cus) continue;
         if (c == 81 && MODE == 1 && a.A2) continue;            // side inputs: ring kernels only
         if (c == 72 && (MODE != 1 || !fie_conv_halo_ok(a) || 2 * (int64_t)(a.M / 256) * ((a.N + 127) / 128) < ctx->num_cus)) continue;
+        if (c == 78 && (MODE != 1 || !fie_conv_halo_edge_ok(a) || 2 * fie_conv_halo_patches(a) * ((a.N + 127) / 128) < ctx->num_cus)) continue;
         out.push_back(c);
     }
     // split-K: big tiles whose grid leaves CUs idle (the M = 2048 class: 80 tiles of 256x128 on 256 CUs) with the K-steps of a tile dealt
@@ -1049,6 +1063,14 @@ int launch(fie_ctx* ctx, GemmArgs& a) {
                 decode(best);
             }
         }
+    }
+    // tuner keys carry neither the map's height and width nor the epilogue: one key covers 144x112 and 168x96 (M 16128), and 78 refuses GroupNorm
+    // sums and activations.  A remembered halo-resident code the launch is not eligible for (72 met on a map of whole patches, then the same key
+    // on a bucket map; 78 met without sums, then with them) falls back to the rule instead of failing
+    if (MODE == 1 && !pinned && ((code >= 71 && code <= 76 && !fie_conv_halo_ok(a)) || (code == 78 && !fie_conv_halo_edge_ok(a)))) {
+        code = heuristic_code<MODE>(ctx, a, dma_ok);
+        order = -1;
+        split = 1;
     }
     return run_code<MODE>(ctx, a, code, order, dma_ok, split);
 }

@@ -389,7 +389,11 @@ int fie_lcm_step_f32(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, floa
 
 /* ---- tuning / test hooks (not part of the drop-in surface).  Tile hooks are PER CTX: nothing process-global sits on the
  * launch path.  Tile codes: 1/2/3 register-staged 128x128 / 128x64 / 64x64 (any shape); 41/42/43 LDS-DMA ring 128x128 /
- * 128x64 / 64x64; 51 ring 128x128 x 8 waves; 61/62 ring 256x256 / 256x128 x 8 waves; 81 phased 256x256 (gemm8.hip).
+ * 128x64 / 64x64; 51 ring 128x128 x 8 waves; 61/62 ring 256x256 / 256x128 x 8 waves; 81 phased 256x256 (gemm8.hip); 71-76 the
+ * halo-resident 3x3 conv on maps whose sides are multiples of 16 (conv_halo.hip; 72 = the rule's); 77 the thin conv (<= 16 output channels);
+ * 78 the halo-resident conv with edge patches: stride-1 same-size 3x3 convs whose height or width is NOT a multiple of 16 (the aspect-ratio
+ * buckets), Cin % 64 == 0, Cin >= 128, N % 64 == 0, no activation / scale, no GroupNorm sums; partial 16x16 patches at the right / bottom edges,
+ * per-pixel store masks; sums K chunk-major like 71-76 (equal to the im2col codes to rounding; bit for bit on integer data).
  * + 1000 / + 2000: force n-tiles / m-tiles fastest tile order (plain codes estimate the order that re-streams fewer bytes).  A code the shape is not eligible for returns FIE_EINVAL from the op. */
 int fie_debug_force_tile(fie_ctx* ctx, int tile);                  /* 0 = heuristic */
 int fie_debug_tile_override(fie_ctx* ctx, const char* spec);       /* "mode,M,N,K=code;..." (mode 0 GEMM, 1 conv); NULL clears; returns the count */

@@ -82,6 +82,14 @@ def add_mask_args(p):
     return p
 
 
+def add_resolution_args(p):
+    """[additive] aspect-ratio edits.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--resolution", type=str, default="square",
+                   help="[additive] output size: 'square' (1024x1024, the reference's), 'auto' (the SDXL bucket nearest each source's aspect "
+                        "ratio; a batch is split into one device job per size) or WxH (multiples of 64, 512..2048, at most 1024^2 pixels)")
+    return p
+
+
 def select_entries(mapping, args, say=print):
     """Reference :115-140: explicit ids win; else filter by type, then truncate to --num_images."""
     if args.image_ids:
@@ -160,6 +168,9 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     extra = {} if args.strength is None else {"strength": args.strength}
     bs = max(1, getattr(args, "batch_size", 1))
     use_mask = getattr(args, "use_mask", False)
+    resolution = getattr(args, "resolution", "square")
+    if resolution != "square":
+        extra = dict(extra, resolution=resolution)
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
     def flush():
@@ -254,7 +265,11 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    args = add_mask_args(build_parser()).parse_args(argv)
+    args = add_resolution_args(add_mask_args(build_parser())).parse_args(argv)
+    if args.resolution != "square":
+        import fie_amd  # noqa: F401
+        from fie_amd import buckets
+        args.resolution = buckets.parse(args.resolution)
     import fie_amd  # noqa: F401
     from fie_amd import dist as fdist
     rank, local, world = fdist.init()

@@ -45,6 +45,9 @@ def build_parser():
     a("--mask", type=str, default=None, help="[additive] mask image (white = edit): only that region changes")
     a("--mask_blur", type=float, default=0, help="[additive] with --mask: Gaussian feather (sigma, pixels) of the paste-back seam")
     a("--no_paste_back", action="store_true", help="[additive] with --mask: blend in latent space only, no paste-back of the source")
+    a("--resolution", type=str, default="square",
+      help="[additive] output size: 'square' (1024x1024, the reference's), 'auto' (the SDXL aspect-ratio bucket nearest the source's) or WxH "
+           "(multiples of 64, 512..2048, at most 1024^2 pixels)")
     return p
 
 
@@ -67,6 +70,10 @@ def save_plot(path, source_img, edited_img, model, prompt):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.resolution != "square":
+        import fie_amd  # noqa: F401
+        from fie_amd import buckets
+        args.resolution = buckets.parse(args.resolution)
     if args.quality_mode:
         args.full_precision = args.full_controlnet = args.no_cpu_offload = True
         print("[Quality Mode] Enabled: fp32 + full ControlNet + no CPU offload")
@@ -101,6 +108,8 @@ def main(argv=None):
             return
         extra.update(mask=Image.open(args.mask), mask_blur=args.mask_blur, paste_back=not args.no_paste_back)
         print(f"      Mask: {args.mask} (blur {args.mask_blur}, paste-back {'off' if args.no_paste_back else 'on'})")
+    if args.resolution != "square":
+        extra.update(resolution=args.resolution)
     t0 = time.time()
     edited_img = editor.edit(image=source_img, prompt=args.prompt, negative_prompt=args.negative_prompt,
                              num_inference_steps=args.steps, guidance_scale=args.guidance,

@@ -14,7 +14,7 @@ import torch
 from PIL import Image
 
 import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory)
-from fie_amd import hip, stack
+from fie_amd import buckets, hip, stack
 from fie_amd import mask as hmask
 from fie_amd.pipe import HipImg2ImgPipeline
 
@@ -139,11 +139,15 @@ class FastEditor:
 
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
-             paste_back=True):
+             paste_back=True, *, resolution=None):
         """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
         [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
         latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
-        for byte; `mask_blur` r > 0 feathers the paste-back seam with a Gaussian of sigma r."""
+        for byte; `mask_blur` r > 0 feathers the paste-back seam with a Gaussian of sigma r.
+        [additive] `resolution`: the size the edit runs at and returns -- None / "square" 1024x1024 (the reference's), "auto" the SDXL
+        aspect-ratio bucket nearest the source's, or (width, height) (fie_amd/buckets.py).  Source, edge map and mask are
+        LANCZOS-resized to it; resizing the result back to the source's size is the caller's choice."""
+        size = buckets.target_size(resolution, image.size)
         hmask.check_args(mask_blur, paste_back, mask is not None)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
         generator = None
@@ -158,8 +162,8 @@ class FastEditor:
         # with it).  Common case: no host wait in front of the edit.  Rare case (a weak chain across more than 15 tiles): the remaining rounds
         # run and the device job is repeated on the final edge map -- same result as preprocess_image() + the pipeline call, always
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
-            source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=(1024, 1024), wait=False)
-            mask_dev = self._mask_device(mask_l, (1024, 1024))
+            source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False)
+            mask_dev = self._mask_device(mask_l, size)
         return self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev,
                          control_image=control_dev, strength=strength, num_inference_steps=num_inference_steps,
                          guidance_scale=guidance_scale, controlnet_conditioning_scale=controlnet_conditioning_scale,
@@ -177,15 +181,34 @@ class FastEditor:
 
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
-                   paste_back=True):
+                   paste_back=True, *, resolution=None):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
         edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
-        `masks`: None, or one mask per image as edit()'s `mask` (None in the list: that image is edited everywhere)."""
+        `masks`: None, or one mask per image as edit()'s `mask` (None in the list: that image is edited everywhere).
+        `resolution`: as edit()'s, per image.  Images of different target sizes ("auto" on mixed aspect ratios) run as one device job per
+        size, in the order of each size's first image; the results come back in input order."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
             raise ValueError(f"{len(masks)} masks for {len(images)} images: one mask (or None) per image")
+        sizes = [buckets.target_size(resolution, im.size) for im in images]
+        groups = {}
+        for i, sz in enumerate(sizes):
+            groups.setdefault(sz, []).append(i)
+        if len(groups) > 1:
+            out = [None] * len(images)
+            pick = lambda seq, idx: None if seq is None else seq if isinstance(seq, str) else [seq[i] for i in idx]
+            for sz, idx in groups.items():
+                res = self.edit_batch([images[i] for i in idx], [prompts[i] for i in idx], pick(negative_prompts, idx), strength=strength,
+                                      num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                      controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
+                                      canny_high_threshold=canny_high_threshold, seed=seed, masks=pick(masks, idx), mask_blur=mask_blur,
+                                      paste_back=paste_back, resolution=sz)
+                for i, r in zip(idx, res):
+                    out[i] = r
+            return out
+        size = sizes[0]
         hmask.check_args(mask_blur, paste_back, masks is not None and any(m is not None for m in masks))
         mask_ls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks, images)] if masks is not None else None
         gens = None
@@ -195,10 +218,10 @@ class FastEditor:
         srcs, ctls = [], []
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             for im in images:
-                s_dev, c_dev = self._canny_device(im, canny_low_threshold, canny_high_threshold, size=(1024, 1024))
+                s_dev, c_dev = self._canny_device(im, canny_low_threshold, canny_high_threshold, size=size)
                 srcs.append(s_dev)
                 ctls.append(c_dev)
-            mask_devs = [self._mask_device(m, (1024, 1024)) for m in mask_ls] if mask_ls is not None else None
+            mask_devs = [self._mask_device(m, size) for m in mask_ls] if mask_ls is not None else None
         return self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls,
                          strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                          controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens, mask_image=mask_devs,
