@@ -2,6 +2,8 @@
 """Evaluation harness -- drop-in for /root/reference/evaluate.py (same flags, same `metrics.csv` columns and
 `summary.json` layout, reference :193-271), on the metrics this build restates (`src/metrics.py`: SSIM, PSNR, MSE).
 LPIPS / CLIP score / DINO distance need hub checkpoints: their cells are empty in the CSV and `null` in the JSON.
+Additive: `--use_mask` appends the background-preservation columns `bg_ssim, bg_psnr, bg_mse` (each item's PIE-Bench `mask`; both images
+zeroed inside the edited region first) to the CSV and to `summary.json`.  Pairs are scored in chunks: on a GPU one launch per chunk.
 
 Under `torch.distributed.run` the mapping entries are sharded image-parallel over the ranks (fie_amd.dist) and rank 0
 writes the merged files -- the "gather of metrics" of SURVEY.md 8e.
@@ -23,6 +25,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 METRICS = ("ssim", "lpips", "clip_score", "psnr", "mse", "dino_distance")
 FIELDS = ["image_id", "image_path", "editing_type_id", "editing_prompt", *METRICS]
+BG_METRICS = ("bg_ssim", "bg_psnr", "bg_mse")
+CHUNK = 16                      # pairs per calculate_pairs() call (one device launch and one synchronisation each)
 KNOWN_SUFFIXES = ("sdxl_fp32", "sdxl_fp16", "ssd-1b_fp32", "ssd-1b_fp16")
 
 
@@ -37,6 +41,14 @@ def build_parser():
     p.add_argument("--summary_file", type=str, default=None,
                    help="Output JSON file for summary statistics (auto-detected from outputs_dir if not specified)")
     p.add_argument("--device", type=str, default="cuda", help="Device to use for metrics computation")
+    return p
+
+
+def add_mask_args(p):
+    """[additive] background-preservation metrics.  Kept apart from build_parser(), whose flag set is the reference's."""
+    p.add_argument("--use_mask", action="store_true",
+                   help="[additive] also score the background (the region outside each item's PIE-Bench `mask`, a run-length code over the "
+                        "512x512 image): columns bg_ssim, bg_psnr, bg_mse.  An item without a mask is skipped loudly")
     return p
 
 
@@ -59,19 +71,48 @@ def _stats(values, with_median):
     return out
 
 
-def summarize(rows):
+def summarize(rows, metrics=METRICS):
     """reference :201-268: overall mean/std/median per metric + per-category mean/std and count."""
-    summary = {"total_images": len(rows), "overall": {m: _stats([r[m] for r in rows], True) for m in METRICS}, "by_category": {}}
+    summary = {"total_images": len(rows), "overall": {m: _stats([r[m] for r in rows], True) for m in metrics}, "by_category": {}}
     cats = {}
     for r in rows:
         cats.setdefault(r["editing_type_id"], []).append(r)
     for cat, rs in cats.items():
-        summary["by_category"][cat] = {"count": len(rs), **{m: _stats([r[m] for r in rs], False) for m in METRICS}}
+        summary["by_category"][cat] = {"count": len(rs), **{m: _stats([r[m] for r in rs], False) for m in metrics}}
     return summary
 
 
 def evaluate_entries(entries, args, calc, progress=None):
     rows, skipped = [], 0
+    use_mask = getattr(args, "use_mask", False)
+    names = METRICS + (BG_METRICS if use_mask else ())
+    if use_mask:
+        from fie_amd import mask as hmask
+    pending = []                                   # (index, image_id, rel, entry, source, edited, mask) awaiting one calculate_pairs() call
+
+    def flush():
+        nonlocal skipped
+        if not pending:
+            return
+        try:
+            ms = calc.calculate_pairs([p[4] for p in pending], [p[5] for p in pending], [p[6] for p in pending] if use_mask else None)
+        except Exception:       # per-image isolation (reference :179-182): score the chunk's pairs one by one, only the failing ones are skipped
+            ms = []
+            for p in pending:
+                try:
+                    ms.append(calc.calculate_pairs([p[4]], [p[5]], [p[6]] if use_mask else None)[0])
+                except Exception as e:
+                    print(f"\n      Error processing {p[1]}: {e}")
+                    skipped += 1
+                    ms.append(None)
+        for (index, image_id, rel, entry, a, b, _), m in zip(pending, ms):
+            if m is None:
+                continue
+            m = calc.with_unavailable(m, a, b, entry.get("editing_prompt", ""))
+            rows.append(dict(index=index, image_id=image_id, image_path=rel, editing_type_id=entry.get("editing_type_id", "unknown"),
+                             editing_prompt=entry.get("editing_prompt", ""), **{k: m[k] for k in names}))
+        pending.clear()
+
     for index, image_id, entry in (progress(entries) if progress else entries):
         rel = entry["image_path"]
         src, out = os.path.join(args.source_dir, rel), os.path.join(args.outputs_dir, rel)
@@ -79,21 +120,23 @@ def evaluate_entries(entries, args, calc, progress=None):
             skipped += 1
             continue
         try:
-            size = (512, 512)
-            a, b = Image.open(src).convert("RGB"), Image.open(out).convert("RGB")
-            a = a if a.size == size else a.resize(size, Image.LANCZOS)
-            b = b if b.size == size else b.resize(size, Image.LANCZOS)
-            m = calc.calculate_all_metrics(source_img=a, edited_img=b, prompt=entry.get("editing_prompt", ""))
-            rows.append(dict(index=index, image_id=image_id, image_path=rel, editing_type_id=entry.get("editing_type_id", "unknown"),
-                             editing_prompt=entry.get("editing_prompt", ""), **{k: m[k] for k in METRICS}))
+            mask = None
+            if use_mask:
+                if not entry.get("mask"):
+                    raise ValueError("--use_mask but the entry has no `mask`")
+                mask = hmask.rle_decode(entry["mask"])
+            pending.append((index, image_id, rel, entry, Image.open(src).convert("RGB"), Image.open(out).convert("RGB"), mask))
         except Exception as e:  # per-image isolation (reference :179-182)
             print(f"\n      Error processing {image_id}: {e}")
             skipped += 1
+        if len(pending) == CHUNK:
+            flush()
+    flush()
     return rows, skipped
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = add_mask_args(build_parser()).parse_args(argv)
     import fie_amd  # noqa: F401
     from fie_amd import dist as fdist
     from src.metrics import MetricsCalculator
@@ -128,11 +171,11 @@ def main(argv=None):
         return
     print("\n[4/4] Saving results...")
     with open(args.results_file, "w", newline="") as fh:
-        w = csv.DictWriter(fh, fieldnames=FIELDS, extrasaction="ignore")
+        w = csv.DictWriter(fh, fieldnames=FIELDS + (list(BG_METRICS) if args.use_mask else []), extrasaction="ignore")
         w.writeheader()
         w.writerows([{k: ("" if v is None else v) for k, v in r.items()} for r in rows])
     print(f"      Saved detailed metrics to: {args.results_file}")
-    summary = summarize(rows)
+    summary = summarize(rows, METRICS + (BG_METRICS if args.use_mask else ()))
     with open(args.summary_file, "w") as fh:
         json.dump(summary, fh, indent=2)
     print(f"      Saved summary statistics to: {args.summary_file}")
@@ -141,6 +184,8 @@ def main(argv=None):
     print(f"\n{bar}\nEVALUATION SUMMARY\n{bar}\n\nTotal Images Evaluated: {len(rows)}\n\nOverall Metrics:")
     labels = (("ssim", "SSIM:      ", ".4f"), ("lpips", "LPIPS:     ", ".4f"), ("psnr", "PSNR:      ", ".2f"), ("mse", "MSE:       ", ".6f"),
               ("clip_score", "CLIP Score:", ".2f"), ("dino_distance", "DINO Dist.:", ".4f"))
+    if args.use_mask:
+        labels += (("bg_ssim", "Bg SSIM:   ", ".4f"), ("bg_psnr", "Bg PSNR:   ", ".2f"), ("bg_mse", "Bg MSE:    ", ".6f"))
     for k, label, spec in labels:
         print(f"  {label} {fmt(summary['overall'][k], spec)}")
     print("\nMetrics by Category:")

@@ -112,6 +112,8 @@ SIGNATURES = {
     "fie_lcm_step_masked_f32": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P, _P, _P, _P],
     "fie_pixels_out_composite_f16_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
     "fie_pixels_out_composite_f32_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
+    "fie_metrics_workspace_bytes": [_I, _I, _I],
+    "fie_metrics_pairs_u8": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _L],
     "fie_debug_force_tile": [_P, _I],
     "fie_debug_attn_variant": [_P, _I],
     "fie_debug_gn_onepass": [_P, _I],
@@ -164,7 +166,7 @@ def lib():
             fn.argtypes = args
             fn.restype = _L if name in ("fie_groupnorm_workspace_bytes", "fie_canny_workspace_bytes", "fie_time_embed_workspace_bytes", "fie_gn_stats_bytes", "fie_debug_oplog_read", "fie_debug_tune_candidates_read", "fie_vae_decode_workspace_bytes",
                                        "fie_vae_encode_workspace_bytes", "fie_clip_text_workspace_bytes", "fie_unet_workspace_bytes", "fie_controlnet_workspace_bytes",
-                                       "fie_unet_step_cache_bytes") else _I
+                                       "fie_unet_step_cache_bytes", "fie_metrics_workspace_bytes") else _I
         _lib.fie_last_error.restype = ctypes.c_char_p
         _lib.fie_last_error.argtypes = []
         _lib.fie_debug_last_gemm_kernel.restype = ctypes.c_char_p
@@ -957,6 +959,29 @@ class Context:
         out = self._alloc((h, w, 3), torch.uint8)
         _chk((lib().fie_pixels_out_composite_f32_u8 if self.f32 else lib().fie_pixels_out_composite_f16_u8)(
             self.h, _p(x_nhwc), ld, h, w, _p(source_u8), _p(mask_px), _p(out)))
+        return out
+
+    def metrics_pairs(self, a, b, mask=None):
+        """u8 [n, H, W, 3] (or [H, W, 3]) device tensors a, b -> int64 [n, 4] device tensor of fie_metrics_pairs_u8's result rows
+        {sse, ssim_sum (float64 bits), bg_sse, bg_ssim_sum (float64 bits)}; fie_amd/metrics.py: rows_to_dicts decodes them on the host.
+        `mask`: None, or u8 [n, H, W] (or [H, W]) with non-zero = edited region (the bg_* fields are 0 without one).  Two launches
+        on the current stream, no synchronisation."""
+        self.sync_stream()
+        if a.dim() == 3:
+            a, b, mask = a[None], b[None], None if mask is None else mask[None]
+        n, h, w, c = a.shape
+        if c != 3 or a.shape != b.shape or a.dtype != torch.uint8 or b.dtype != torch.uint8:
+            raise ValueError(f"metrics_pairs: two u8 [n, H, W, 3] tensors of one shape, got {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+        if mask is not None and (tuple(mask.shape) != (n, h, w) or mask.dtype != torch.uint8):
+            raise ValueError(f"metrics_pairs: mask must be u8 {(n, h, w)}, got {tuple(mask.shape)} {mask.dtype}")
+        a, b = a.contiguous(), b.contiguous()
+        mask = None if mask is None else mask.contiguous()
+        nbytes = lib().fie_metrics_workspace_bytes(n, h, w)
+        if nbytes < 0:
+            raise FieError(f"metrics_pairs: {h} x {w} images are below the 11 x 11 minimum of the SSIM window")
+        ws = torch.empty(nbytes // 8, device=self.device, dtype=torch.int64)
+        out = torch.empty((n, 4), device=self.device, dtype=torch.int64)
+        _chk(lib().fie_metrics_pairs_u8(self.h, _p(a), _p(b), _p(mask), n, h, w, _p(out), _p(ws), nbytes))
         return out
 
     def canny_device(self, rgb_u8, low=100, high=200):

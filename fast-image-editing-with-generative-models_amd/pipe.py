@@ -585,21 +585,23 @@ class HipImg2ImgPipeline:
 
     def __call__(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                  num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
-                 output_type="pil", slot=0, post_check=None, mask_image=None, mask_blur=0, paste_back=True, **unused):
+                 output_type="pil", slot=0, post_check=None, mask_image=None, mask_blur=0, paste_back=True, after_device=None, **unused):
         """`slot` (additive): independent hipGraph instance + stream, so that several calls may be in flight from different
         host threads on one GPU (graph mode only).  `post_check` (additive): a callable run after the result has reached the host
         (the stream is idle then); when it returns True the device-resident inputs have changed meanwhile and the device job is run
         again.  FastEditor.edit() passes the second half of its asynchronous device Canny: the edge map is computed with a fixed
         number of hysteresis rounds in front of the edit, and whether they had reached the fixed point is only looked at here --
         no host wait in front of the edit, a repeated job in the rare case that they had not.  `mask_image` / `mask_blur` / `paste_back`
-        (additive): a mask-restricted edit (prepare(); a list of masks for a batch call)."""
+        (additive): a mask-restricted edit (prepare(); a list of masks for a batch call).  `after_device` (additive): a callable given the u8 result
+        while it is still on the device, on the slot's stream behind the device job and outside its graph; it may queue more work there (FastEditor
+        scores the edit) and whatever it returns comes back as `.extra`, complete once the image has reached the host."""
         if slot and not self.use_graph:
             raise ValueError("slots > 0 need hipGraph replay (the eager path shares per-image state)")
         caller, st = torch.cuda.current_stream(self.ctx.device), self.slot_stream(slot)
         st.wait_stream(caller)                           # device-resident inputs may still be in flight on the caller's stream
         with torch.cuda.stream(st):
             out = self._call(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back))
+                             controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back), after_device)
         caller.wait_stream(st)
         return out
 
@@ -617,32 +619,35 @@ class HipImg2ImgPipeline:
         return host.numpy().copy()
 
     def _call(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-              controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_args=(None, 0, True)):
+              controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_args=(None, 0, True), after_device=None):
+        def run(job):
+            """One device job, the caller's after_device hook behind it, then the result on the host: -> (u8 array, hook's return)."""
+            out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
+            extra = after_device(out_u8) if after_device is not None else None
+            return self._to_host(out_u8, slot), extra       # device -> host sync, as `.images[0]` implies upstream
+
         if isinstance(prompt, (list, tuple)):            # [additive] a batch: lists of prompts / images / generators
             job = self.prepare_batch(list(prompt), negative_prompt if isinstance(negative_prompt, (list, tuple)) else None,
                                      list(image), list(control_image), strength, num_inference_steps, guidance_scale,
                                      controlnet_conditioning_scale, generator if isinstance(generator, (list, tuple)) else None, *mask_args)
-            out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
-            arr = self._to_host(out_u8, slot)
+            arr, extra = run(job)
             if post_check is not None and post_check():
-                out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
-                arr = self._to_host(out_u8, slot)
+                arr, extra = run(job)
             arr = arr[None] if arr.ndim == 3 else arr
             if output_type == "np":
-                return types.SimpleNamespace(images=list(arr))
-            return types.SimpleNamespace(images=[Image.fromarray(a) for a in arr])
+                return types.SimpleNamespace(images=list(arr), extra=extra)
+            return types.SimpleNamespace(images=[Image.fromarray(a) for a in arr], extra=extra)
         job = self.prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps,
                            guidance_scale, controlnet_conditioning_scale, generator, *mask_args)
-        out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
         if output_type == "latent":
+            self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
             res = job["_result"]
             lh, lw = res["stats"]["latent_hw"]
             return types.SimpleNamespace(images=[res["latents"].view(lh, lw, 4).clone()])
-        arr = self._to_host(out_u8, slot)              # device -> host sync, as `.images[0]` implies upstream
+        arr, extra = run(job)
         if post_check is not None and post_check():
             self.repeated_jobs += 1
-            out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
-            arr = self._to_host(out_u8, slot)
+            arr, extra = run(job)
         if output_type == "np":
-            return types.SimpleNamespace(images=[arr])
-        return types.SimpleNamespace(images=[Image.fromarray(arr)])
+            return types.SimpleNamespace(images=[arr], extra=extra)
+        return types.SimpleNamespace(images=[Image.fromarray(arr)], extra=extra)

@@ -553,6 +553,23 @@ int fie_pixels_out_composite_f16_u8(fie_ctx* ctx, const void* src, int64_t ld_in
 int fie_pixels_out_composite_f32_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, const uint8_t* source,
                                     const float* mask, uint8_t* dst);
 
+/* ---- Edit metrics on the device: SSE and SSIM of n pairs of u8 images in one pass.
+ *   a, b: u8 [n, H, W, 3] (H, W >= 11: the 11-tap window's reflect padding); mask: NULL, or u8 [n, H, W] with non-zero = edited region.
+ *   result: n rows of four 8-byte fields (8-byte aligned), written by the device:
+ *       [0] uint64 sse          sum over pixels and channels of (a - b)^2 on the u8 values, exact
+ *       [1] double ssim_sum     sum of the SSIM map over the channels and the (H - 10) x (W - 10) positions whose 11x11 window lies inside
+ *                               the image (oracle/metrics.py: the reflect-padded border is cropped from the map again); Gaussian sigma 1.5,
+ *                               images / 255, c1 = 1e-4, c2 = 9e-4; fp32 moments, summed in fp64
+ *       [2] uint64 bg_sse       } the same two for the BACKGROUND pair: both images with every pixel of the edited region set to 0
+ *       [3] double bg_ssim_sum  } in all channels first, sums over the same (H - 10) x (W - 10) positions; both 0 when mask is NULL
+ *   MSE = sse / (255^2 * 3HW), PSNR = 10 log10(1 / MSE), SSIM = ssim_sum / (3 (H - 10) (W - 10)) are the host's to form (in double: no device rounding
+ *   in MSE / PSNR at all).  workspace: fie_metrics_workspace_bytes(n, H, W) bytes (-1 for sizes the op refuses), 8-byte aligned; one
+ *   partial per 32x32 tile.  Two launches, asynchronous on the ctx stream, never synchronises.  Deterministic: no atomics, partials are
+ *   added in tile order, so a pair's row has the same bits in every run and at every position of every batch. */
+int64_t fie_metrics_workspace_bytes(int n, int H, int W);
+int fie_metrics_pairs_u8(fie_ctx* ctx, const uint8_t* a, const uint8_t* b, const uint8_t* mask, int n, int H, int W, void* result,
+                         void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

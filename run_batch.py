@@ -6,7 +6,7 @@ shards the selected entries image-parallel over N GPUs (fie_amd.dist) and rank 0
     python run_batch.py --num_images 50 --editing_types 0 1 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run_batch.py --model ssd-1b
 
-Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json.
+Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics.
 """
 import argparse
 import json
@@ -90,6 +90,18 @@ def add_resolution_args(p):
     return p
 
 
+def add_metrics_args(p):
+    """[additive] inline metrics.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--metrics", action="store_true",
+                   help="[additive] score every edit where it is made (SSIM / PSNR / MSE against the source at 512x512, on the device, plus the "
+                        "background scores bg_* with --use_mask): per-image values in --results_json, mean / std in the summary.  They are of the "
+                        "result BEFORE JPEG encoding, so they differ slightly from evaluate.py's on the saved file")
+    return p
+
+
+METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse")
+
+
 def select_entries(mapping, args, say=print):
     """Reference :115-140: explicit ids win; else filter by type, then truncate to --num_images."""
     if args.image_ids:
@@ -171,6 +183,9 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     resolution = getattr(args, "resolution", "square")
     if resolution != "square":
         extra = dict(extra, resolution=resolution)
+    with_metrics = getattr(args, "metrics", False)
+    if with_metrics:
+        extra = dict(extra, metrics=True)
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
     def flush():
@@ -182,17 +197,19 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
             t0 = time.time()
             if bs == 1:
                 mkw = dict(mask=pending[0][6]) if use_mask else {}
-                edited = [editor.edit(image=pending[0][4], prompt=pending[0][5], negative_prompt=args.negative_prompt, **kw, **mkw)]
+                edited = editor.edit(image=pending[0][4], prompt=pending[0][5], negative_prompt=args.negative_prompt, **kw, **mkw)
+                edited = ([edited[0]], [edited[1]]) if with_metrics else [edited]
             else:
                 mkw = dict(masks=[p[6] for p in pending]) if use_mask else {}
                 edited = editor.edit_batch(images=[p[4] for p in pending], prompts=[p[5] for p in pending],
                                            negative_prompts=[args.negative_prompt] * len(pending), **kw, **mkw)
             dt = (time.time() - t0) / len(pending)
-            for (index, image_id, rel, output_path, source_img, prompt, _), out in zip(pending, edited):
+            edited, scores = edited if with_metrics else (edited, [{}] * len(pending))
+            for (index, image_id, rel, output_path, source_img, prompt, _), out, score in zip(pending, edited, scores):
                 res["total_time"] += dt
                 out.save(output_path)
                 res["processed"] += 1
-                res["rows"].append(dict(index=index, image_id=image_id, image_path=rel, elapsed_s=dt))
+                res["rows"].append(dict(index=index, image_id=image_id, image_path=rel, elapsed_s=dt, **score))
                 if args.save_comparisons:
                     save_comparison(os.path.join(comparisons_dir, rel.replace(".jpg", ".png")), source_img, out, args.model, prompt)
                 if res["processed"] % 10 == 0:
@@ -251,6 +268,15 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
         print(f"\nAverage time per image: {tot['total_time'] / tot['processed']:.2f}s")
         print(f"Total time: {tot['total_time']:.2f}s ({tot['total_time'] / 60:.1f} minutes)")
         print(f"Throughput: {tot['processed'] / wall:.2f} images/sec wall-clock on {world} GPU(s)")
+        if getattr(args, "metrics", False):
+            import numpy as np
+            print("\nMetrics of the edits (512x512, before JPEG encoding):")
+            for k in METRIC_KEYS:
+                vals = [r[k] for r in tot.get("rows", []) if k in r]
+                finite = [v for v in vals if np.isfinite(v)]          # an unchanged image has PSNR inf
+                if finite:
+                    note = f"  ({len(vals) - len(finite)} infinite not counted)" if len(finite) < len(vals) else ""
+                    print(f"  {k + ':':<9} {np.mean(finite):.6f} ± {np.std(finite):.6f}{note}")
     else:
         print("\n⚠ WARNING: No images were successfully processed!")
         print("  Check that:")
@@ -265,7 +291,7 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    args = add_resolution_args(add_mask_args(build_parser())).parse_args(argv)
+    args = add_metrics_args(add_resolution_args(add_mask_args(build_parser()))).parse_args(argv)
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets

@@ -4,13 +4,22 @@ Evaluation only (not part of the denoising hot path): plain t
 torchmetrics are.  Restated here: SSIM (torchmetrics defaults: 11x11 Gaussian, sigma 1.5, k1/k2 0.01/0.03,
 data_range 1), PSNR and MSE, all on 512x512 LANCZOS-resized RGB in [0,1] (reference :227-239, :291-347).
 LPIPS(squeeze), CLIPScore(ViT-B/16) and the DINO ViT-B/8 distance need checkpoints that only exist on the hub
-(reference :28, :179-186); offline they return None rather than a made-up number."""
+(reference :28, :179-186); offline they return None rather than a made-up number.
+
+On a GPU (`device="cuda..."`) the arithmetic is one HIP op (csrc/metrics.hip through `ctx.metrics_pairs`): each image is
+uploaded once, LANCZOS-resized on the device when it is not 512x512, and SSIM / PSNR / MSE of any number of pairs come from one launch and
+one synchronisation.  `device="cpu"` is the torch restatement above.  Additive: `calculate_all_metrics(..., mask=)` adds the background
+preservation scores `bg_ssim / bg_psnr / bg_mse` (both images zeroed inside the edited region, PIE-Bench's convention), and
+`calculate_pairs(sources, editeds, masks=None)` scores a list at once."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 from PIL import Image
 
-TARGET = (512, 512)
+import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory)
+from fie_amd import metrics as hmetrics
+
+TARGET = hmetrics.TARGET
 
 
 class MetricsCalculator:
@@ -20,7 +29,12 @@ class MetricsCalculator:
         d = torch.arange(-5.0, 6.0)
         g = torch.exp(-(d / 1.5) ** 2 / 2)
         g = (g / g.sum())[None]
-        self._win = (g.T @ g).to(device)
+        self._win = g.T @ g                             # the torch restatement's window (device="cpu")
+        self._ctx = None
+        if str(device).startswith("cuda"):              # no fallback: a missing library or GPU raises here
+            from fie_amd import hip
+            index = torch.device(device).index
+            self._ctx = hip.context(torch.cuda.current_device() if index is None else index)
         print("[MetricsCalculator] Initialization complete! (LPIPS / CLIP score / DINO: unavailable offline)")
 
     def _pil_to_tensor(self, img):
@@ -34,8 +48,52 @@ class MetricsCalculator:
             img2 = img2.resize(TARGET, Image.LANCZOS)
         return self._pil_to_tensor(img1), self._pil_to_tensor(img2)
 
+    def _upload(self, img):
+        """PIL -> u8 [512, 512, 3] on the device: one upload, the LANCZOS resize (when needed) in fie_resize_rgb_u8, bit-exact with Pillow."""
+        t = torch.from_numpy(np.ascontiguousarray(np.array(img)[..., :3])).to(self._ctx.device)
+        if (t.shape[1], t.shape[0]) != TARGET:
+            t = self._ctx.resize_lanczos(t, TARGET[1], TARGET[0])
+        return t
+
+    def calculate_pairs(self, sources, editeds, masks=None):
+        """[additive] {ssim, psnr, mse} of every (source, edited) pair of two lists of PIL images; `masks` (None, or one mask or None per
+        pair: a PIL image or a uint8 / bool [H, W] array of any size, white = edited) adds {bg_ssim, bg_psnr, bg_mse} where a mask is given.
+        On a GPU: one upload per image, one launch and one synchronisation for the whole list."""
+        if len(sources) != len(editeds) or (masks is not None and len(masks) != len(sources)):
+            raise ValueError("sources, editeds and masks must be lists of one length")
+        masks = list(masks) if masks is not None else [None] * len(sources)
+        bins = [None if m is None else hmetrics.binary_mask(m) for m in masks]
+        if not sources:
+            return []
+        if self._ctx is None:
+            return [self._pair_cpu(a, b, m) for a, b, m in zip(sources, editeds, bins)]
+        ctx = self._ctx
+        with torch.cuda.device(ctx.device):
+            a = torch.stack([self._upload(im) for im in sources])
+            b = torch.stack([self._upload(im) for im in editeds])
+            mk = None
+            if any(m is not None for m in bins):
+                zero = np.zeros(TARGET[::-1], np.uint8)
+                mk = torch.from_numpy(np.stack([zero if m is None else m for m in bins])).to(ctx.device)
+            rows = ctx.metrics_pairs(a, b, mk).cpu()
+        return hmetrics.rows_to_dicts(rows.numpy(), TARGET[1], TARGET[0], [m is not None for m in bins])
+
+    def _pair_cpu(self, img1, img2, mask01=None):
+        out = {"ssim": self._ssim_cpu(img1, img2), "psnr": self._psnr_cpu(img1, img2), "mse": self._mse_cpu(img1, img2)}
+        if mask01 is not None:
+            keep = torch.from_numpy(1.0 - mask01.astype(np.float32))[None, None].to(self.device)
+            out.update(bg_ssim=self._ssim_cpu(img1, img2, keep), bg_psnr=self._psnr_cpu(img1, img2, keep), bg_mse=self._mse_cpu(img1, img2, keep))
+        return out
+
     def calculate_ssim(self, img1, img2):
+        if self._ctx is not None:
+            return self.calculate_pairs([img1], [img2])[0]["ssim"]
+        return self._ssim_cpu(img1, img2)
+
+    def _ssim_cpu(self, img1, img2, keep=None):
         x, y = self._pair(img1, img2)
+        if keep is not None:
+            x, y = x * keep, y * keep
         c = x.shape[1]
         win = self._win.expand(c, 1, 11, 11)
         xp, yp = F.pad(x, (5,) * 4, mode="reflect"), F.pad(y, (5,) * 4, mode="reflect")
@@ -46,11 +104,23 @@ class MetricsCalculator:
         return m[..., 5:-5, 5:-5].mean().item()
 
     def calculate_mse(self, img1, img2):
+        if self._ctx is not None:
+            return self.calculate_pairs([img1], [img2])[0]["mse"]
+        return self._mse_cpu(img1, img2)
+
+    def _mse_cpu(self, img1, img2, keep=None):
         x, y = self._pair(img1, img2)
+        if keep is not None:
+            x, y = x * keep, y * keep
         return ((x - y) ** 2).mean().item()
 
     def calculate_psnr(self, img1, img2):
-        m = self.calculate_mse(img1, img2)
+        if self._ctx is not None:
+            return self.calculate_pairs([img1], [img2])[0]["psnr"]
+        return self._psnr_cpu(img1, img2)
+
+    def _psnr_cpu(self, img1, img2, keep=None):
+        m = self._mse_cpu(img1, img2, keep)
         return float("inf") if m == 0 else float(10.0 * np.log10(1.0 / m))
 
     def calculate_lpips(self, img1, img2):
@@ -59,11 +129,17 @@ class MetricsCalculator:
     def calculate_clip_score(self, img, text):
         return None
 
-    def calculate_all_metrics(self, source_img, edited_img, prompt):
-        return {"ssim": self.calculate_ssim(source_img, edited_img), "lpips": self.calculate_lpips(source_img, edited_img),
-                "clip_score": self.calculate_clip_score(edited_img, prompt), "psnr": self.calculate_psnr(source_img, edited_img),
-                "mse": self.calculate_mse(source_img, edited_img), "dino_distance": None}
+    def calculate_all_metrics(self, source_img, edited_img, prompt, mask=None):
+        m = self.calculate_pairs([source_img], [edited_img], None if mask is None else [mask])[0]
+        return self.with_unavailable(m, source_img, edited_img, prompt)
+
+    def with_unavailable(self, m, source_img=None, edited_img=None, prompt=""):
+        """A calculate_pairs() dict in calculate_all_metrics()'s key order, with the metrics that need hub checkpoints as None."""
+        out = {"ssim": m["ssim"], "lpips": self.calculate_lpips(source_img, edited_img), "clip_score": self.calculate_clip_score(edited_img, prompt),
+               "psnr": m["psnr"], "mse": m["mse"], "dino_distance": None}
+        out.update({k: m[k] for k in hmetrics.BG_KEYS if k in m})
+        return out
 
     def clear_memory(self):
-        if self.device == "cuda":
+        if str(self.device).startswith("cuda"):
             torch.cuda.empty_cache()

@@ -16,6 +16,7 @@ from PIL import Image
 import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory)
 from fie_amd import buckets, hip, stack
 from fie_amd import mask as hmask
+from fie_amd import metrics as hmetrics
 from fie_amd.pipe import HipImg2ImgPipeline
 
 
@@ -98,6 +99,7 @@ class FastEditor:
         self.pipe = HipImg2ImgPipeline(ctx, cfgs, sds, tokenizers=toks, noise_dtype=noise_dtype or self.dtype, weight_dtype=weight_dtype)
         self.controlnet = self.pipe.controlnet
         self._tls = threading.local()          # .slot: graph slot of the calling worker thread (set_in_flight)
+        self._metric_rows = {}                 # (slot, images) -> pinned int64 [images, 4]: where an edit's metric rows land (metrics=True)
         del sds
         log("Enabling memory optimizations...")
         # 288 GB of HBM: offload / slicing flags are accepted and ignored (reference toggles them at :165-179)
@@ -107,19 +109,24 @@ class FastEditor:
 
     CANNY_ROUNDS = 4            # hysteresis rounds (of four passes) edit() launches without looking at the flags: weak chains across <= 15 tiles of 32x32
 
-    def _canny_device(self, image, low_threshold, high_threshold, size=None, wait=True):
+    def _canny_device(self, image, low_threshold, high_threshold, size=None, wait=True, original=None):
         """PIL -> (u8 HWC source on the device, u8 HWC edge map on the device): gray, Sobel, NMS and hysteresis run in HIP
         kernels (csrc/canny_device.hip), integer exact.  `size` = (width, height): LANCZOS-resize first, as
         `image.resize(size, Image.LANCZOS)` does -- on the device for RGB images, through PIL for any other mode.
         wait=False: returns (source, edge map, finish) with the kernels still in flight (NMS + CANNY_ROUNDS hysteresis rounds); finish()
         -- called once the stream has drained -- returns True when those rounds had NOT reached the fixed point: it has then run the
-        remaining ones and rewritten the edge map, and whatever was computed from the map must be computed again."""
+        remaining ones and rewritten the edge map, and whatever was computed from the map must be computed again.
+        `original`: a list that receives the source as uploaded, before the resize (what an inline metric scores against)."""
         if size is not None and image.size != tuple(size) and image.mode != "RGB":
+            if original is not None:                    # the one case in which the upload below is not the original: score what evaluate.py would
+                original.append(torch.from_numpy(np.array(image.convert("RGB"))).to(self.pipe.ctx.device))
             image = image.resize(size, Image.LANCZOS)
         arr = np.array(image)
         if arr.ndim == 2:
             arr = np.stack([arr] * 3, axis=2)
         src = torch.from_numpy(np.ascontiguousarray(arr[..., :3])).to(self.pipe.ctx.device)
+        if original is not None and not original:
+            original.append(src)
         if size is not None and (src.shape[1], src.shape[0]) != tuple(size):
             src = self.pipe.ctx.resize_lanczos(src, size[1], size[0])
         ctx = self.pipe.ctx
@@ -139,14 +146,17 @@ class FastEditor:
 
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
-             paste_back=True, *, resolution=None):
+             paste_back=True, *, resolution=None, metrics=False):
         """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
         [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
         latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
         for byte; `mask_blur` r > 0 feathers the paste-back seam with a Gaussian of sigma r.
         [additive] `resolution`: the size the edit runs at and returns -- None / "square" 1024x1024 (the reference's), "auto" the SDXL
         aspect-ratio bucket nearest the source's, or (width, height) (fie_amd/buckets.py).  Source, edge map and mask are
-        LANCZOS-resized to it; resizing the result back to the source's size is the caller's choice."""
+        LANCZOS-resized to it; resizing the result back to the source's size is the caller's choice.
+        [additive] `metrics=True`: returns (image, dict) with `ssim`, `psnr`, `mse` of the edit (and `bg_ssim`, `bg_psnr`, `bg_mse` with a mask),
+        scored on the device behind the edit: the pair is the ORIGINAL source and the u8 result, each LANCZOS-resized to 512x512 -- what
+        evaluate.py would score had the result been saved losslessly.  No additional host wait."""
         size = buckets.target_size(resolution, image.size)
         hmask.check_args(mask_blur, paste_back, mask is not None)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
@@ -161,33 +171,73 @@ class FastEditor:
         # the same stream, and whether the rounds had reached the fixed point is read when the result is on the host (the flags travelled
         # with it).  Common case: no host wait in front of the edit.  Rare case (a weak chain across more than 15 tiles): the remaining rounds
         # run and the device job is repeated on the final edge map -- same result as preprocess_image() + the pipeline call, always
+        origs, omasks = ([], []) if metrics else (None, None)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
-            source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False)
-            mask_dev = self._mask_device(mask_l, size)
-        return self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev,
-                         control_image=control_dev, strength=strength, num_inference_steps=num_inference_steps,
-                         guidance_scale=guidance_scale, controlnet_conditioning_scale=controlnet_conditioning_scale,
-                         generator=generator, post_check=finish, mask_image=mask_dev, mask_blur=mask_blur, paste_back=paste_back).images[0]
+            source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False,
+                                                                 original=origs)
+            mask_dev = self._mask_device(mask_l, size, original=omasks)
+        res = self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev,
+                        control_image=control_dev, strength=strength, num_inference_steps=num_inference_steps,
+                        guidance_scale=guidance_scale, controlnet_conditioning_scale=controlnet_conditioning_scale,
+                        generator=generator, post_check=finish, mask_image=mask_dev, mask_blur=mask_blur, paste_back=paste_back,
+                        after_device=self._scorer(slot, origs, omasks) if metrics else None)
+        if not metrics:
+            return res.images[0]
+        return res.images[0], self._scores(res.extra, [mask_l is not None])[0]
 
-    def _mask_device(self, mask_l, size):
+    def _scorer(self, slot, origs, omasks):
+        """The `after_device` hook of an edit with metrics=True: queues, on the edit's stream behind its result, the LANCZOS resizes to
+        512x512 (sources, results, masks), ONE fie_metrics_pairs_u8 launch pair for all images of the job and the copy of the 32-byte result
+        rows into pinned host memory of the slot.  The edit's own final synchronisation (the image's D2H) completes them."""
+        ctx = self.pipe.ctx
+        th, tw = hmetrics.TARGET[1], hmetrics.TARGET[0]
+        to512 = lambda t: t if tuple(t.shape[:2]) == (th, tw) else ctx.resize_lanczos(t.contiguous(), th, tw)
+        stack = lambda ts: ts[0][None] if len(ts) == 1 else torch.stack(ts)
+
+        def score(out_u8):
+            outs = [out_u8] if out_u8.dim() == 3 else list(out_u8)
+            with self.pipe.eager_lock:                    # the context's stream binding is shared by the threads of in-flight edits
+                a = stack([to512(o) for o in origs])
+                b = stack([to512(o) for o in outs])
+                mk = None
+                if any(m is not None for m in omasks):
+                    zero = lambda: torch.zeros((th, tw), device=ctx.device, dtype=torch.uint8)
+                    mk = stack([zero() if m is None else hmetrics.binary_mask_device(ctx, m) for m in omasks])
+                rows = ctx.metrics_pairs(a, b, mk)
+            host = self._metric_rows.get((slot, len(outs)))
+            if host is None:
+                host = self._metric_rows[(slot, len(outs))] = torch.empty((len(outs), 4), dtype=torch.int64).pin_memory()
+            host.copy_(rows, non_blocking=True)
+            return host
+        return score
+
+    def _scores(self, host_rows, has_mask):
+        return hmetrics.rows_to_dicts(host_rows.numpy().copy(), hmetrics.TARGET[1], hmetrics.TARGET[0], has_mask)
+
+    def _mask_device(self, mask_l, size, original=None):
         """uint8 [H, W] mode-L mask (or None) -> u8 [size[1], size[0]] on the device: LANCZOS-resized as the source is (fie_resize_l_u8,
-        bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`)."""
+        bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`).  `original`: a list that receives the mask as uploaded (or None)."""
         if mask_l is None:
+            if original is not None:
+                original.append(None)
             return None
         m = torch.from_numpy(mask_l).to(self.pipe.ctx.device)
+        if original is not None:
+            original.append(m)
         if (m.shape[1], m.shape[0]) != tuple(size):
             m = self.pipe.ctx.resize_lanczos(m, size[1], size[0])
         return m
 
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
-                   paste_back=True, *, resolution=None):
+                   paste_back=True, *, resolution=None, metrics=False):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
         edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
         `masks`: None, or one mask per image as edit()'s `mask` (None in the list: that image is edited everywhere).
         `resolution`: as edit()'s, per image.  Images of different target sizes ("auto" on mixed aspect ratios) run as one device job per
-        size, in the order of each size's first image; the results come back in input order."""
+        size, in the order of each size's first image; the results come back in input order.
+        `metrics=True`: returns (images, [dict per image]) as edit() does; all images of a device job are scored in one launch."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
@@ -197,17 +247,18 @@ class FastEditor:
         for i, sz in enumerate(sizes):
             groups.setdefault(sz, []).append(i)
         if len(groups) > 1:
-            out = [None] * len(images)
+            out, mets = [None] * len(images), [None] * len(images)
             pick = lambda seq, idx: None if seq is None else seq if isinstance(seq, str) else [seq[i] for i in idx]
             for sz, idx in groups.items():
                 res = self.edit_batch([images[i] for i in idx], [prompts[i] for i in idx], pick(negative_prompts, idx), strength=strength,
                                       num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                       controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
                                       canny_high_threshold=canny_high_threshold, seed=seed, masks=pick(masks, idx), mask_blur=mask_blur,
-                                      paste_back=paste_back, resolution=sz)
-                for i, r in zip(idx, res):
-                    out[i] = r
-            return out
+                                      paste_back=paste_back, resolution=sz, metrics=metrics)
+                res, ms = res if metrics else (res, [None] * len(idx))
+                for i, r, m in zip(idx, res, ms):
+                    out[i], mets[i] = r, m
+            return (out, mets) if metrics else out
         size = sizes[0]
         hmask.check_args(mask_blur, paste_back, masks is not None and any(m is not None for m in masks))
         mask_ls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks, images)] if masks is not None else None
@@ -216,16 +267,25 @@ class FastEditor:
             gens = [torch.Generator(device=self.device).manual_seed(seed) for _ in images]
         slot = getattr(self._tls, "slot", 0)
         srcs, ctls = [], []
+        origs, omasks = ([], []) if metrics else (None, None)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             for im in images:
-                s_dev, c_dev = self._canny_device(im, canny_low_threshold, canny_high_threshold, size=size)
+                one = [] if metrics else None
+                s_dev, c_dev = self._canny_device(im, canny_low_threshold, canny_high_threshold, size=size, original=one)
                 srcs.append(s_dev)
                 ctls.append(c_dev)
-            mask_devs = [self._mask_device(m, size) for m in mask_ls] if mask_ls is not None else None
-        return self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls,
-                         strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                         controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens, mask_image=mask_devs,
-                         mask_blur=mask_blur, paste_back=paste_back).images
+                if metrics:
+                    origs.append(one[0])
+            mask_devs = [self._mask_device(m, size, original=omasks) for m in mask_ls] if mask_ls is not None else None
+        if metrics and mask_ls is None:
+            omasks = [None] * len(images)
+        res = self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls,
+                        strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                        controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens, mask_image=mask_devs,
+                        mask_blur=mask_blur, paste_back=paste_back, after_device=self._scorer(slot, origs, omasks) if metrics else None)
+        if not metrics:
+            return res.images
+        return res.images, self._scores(res.extra, [m is not None for m in omasks])
 
     def calibrate_fp8(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                       controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=0, margin=2.0):
