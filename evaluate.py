@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 METRICS = ("ssim", "lpips", "clip_score", "psnr", "mse", "dino_distance")
 FIELDS = ["image_id", "image_path", "editing_type_id", "editing_prompt", *METRICS]
 BG_METRICS = ("bg_ssim", "bg_psnr", "bg_mse")
+EDITED_METRICS = ("clip_score_edited",)          # only with --use_mask AND a CLIP model directory (--clip_score_dir)
 CHUNK = 16                      # pairs per calculate_pairs() call (one device launch and one synchronisation each)
 KNOWN_SUFFIXES = ("sdxl_fp32", "sdxl_fp16", "ssd-1b_fp32", "ssd-1b_fp16")
 
@@ -49,6 +50,15 @@ def add_mask_args(p):
     p.add_argument("--use_mask", action="store_true",
                    help="[additive] also score the background (the region outside each item's PIE-Bench `mask`, a run-length code over the "
                         "512x512 image): columns bg_ssim, bg_psnr, bg_mse.  An item without a mask is skipped loudly")
+    return p
+
+
+def add_clip_args(p):
+    """[additive] CLIP score.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--clip_score_dir", type=str, default=None,
+                   help="[additive] a local transformers CLIPModel directory (openai/clip-vit-base-patch16 is the reference's): fills the clip_score "
+                        "column (and, with --use_mask, adds clip_score_edited beside bg_*).  Default: FIE_CLIP_SCORE_DIR, else "
+                        "<FIE_WEIGHTS_DIR>/clip_score when it exists; without one the column stays empty")
     return p
 
 
@@ -85,7 +95,8 @@ def summarize(rows, metrics=METRICS):
 def evaluate_entries(entries, args, calc, progress=None):
     rows, skipped = [], 0
     use_mask = getattr(args, "use_mask", False)
-    names = METRICS + (BG_METRICS if use_mask else ())
+    with_edited = use_mask and getattr(calc, "_clip", None) is not None
+    names = METRICS + (BG_METRICS if use_mask else ()) + (EDITED_METRICS if with_edited else ())
     if use_mask:
         from fie_amd import mask as hmask
     pending = []                                   # (index, image_id, rel, entry, source, edited, mask) awaiting one calculate_pairs() call
@@ -105,10 +116,21 @@ def evaluate_entries(entries, args, calc, progress=None):
                     print(f"\n      Error processing {p[1]}: {e}")
                     skipped += 1
                     ms.append(None)
-        for (index, image_id, rel, entry, a, b, _), m in zip(pending, ms):
+        clips = [None] * len(pending)
+        if getattr(calc, "_clip", None) is not None:      # the chunk's CLIP scores in one batched pass; a failure leaves the column empty
+            try:
+                clips = calc.calculate_clip_scores([p[5] for p in pending], [p[3].get("editing_prompt", "") for p in pending],
+                                                   [p[6] for p in pending] if use_mask else None)
+            except Exception as e:
+                print(f"\n      Error computing CLIP scores: {e}")
+        for (index, image_id, rel, entry, a, b, _), m, cs in zip(pending, ms, clips):
             if m is None:
                 continue
-            m = calc.with_unavailable(m, a, b, entry.get("editing_prompt", ""))
+            m = calc.with_unavailable(m, None, None, entry.get("editing_prompt", ""))
+            if cs:
+                m.update(cs)
+            if with_edited:
+                m.setdefault("clip_score_edited", None)
             rows.append(dict(index=index, image_id=image_id, image_path=rel, editing_type_id=entry.get("editing_type_id", "unknown"),
                              editing_prompt=entry.get("editing_prompt", ""), **{k: m[k] for k in names}))
         pending.clear()
@@ -136,7 +158,7 @@ def evaluate_entries(entries, args, calc, progress=None):
 
 
 def main(argv=None):
-    args = add_mask_args(build_parser()).parse_args(argv)
+    args = add_clip_args(add_mask_args(build_parser())).parse_args(argv)
     import fie_amd  # noqa: F401
     from fie_amd import dist as fdist
     from src.metrics import MetricsCalculator
@@ -150,7 +172,7 @@ def main(argv=None):
     say(f"\n[2/4] Scanning outputs in {args.outputs_dir}")
     say(f"\n[3/4] Initializing metrics on {args.device}...")
     device = args.device if world == 1 or not args.device.startswith("cuda") else f"cuda:{local}"
-    calc = MetricsCalculator(device=device)
+    calc = MetricsCalculator(device=device, clip_dir=args.clip_score_dir)
     mine = fdist.shard([(i, k, e) for i, (k, e) in enumerate(mapping.items())], rank, world)
     progress = None
     if rank == 0:
@@ -171,11 +193,12 @@ def main(argv=None):
         return
     print("\n[4/4] Saving results...")
     with open(args.results_file, "w", newline="") as fh:
-        w = csv.DictWriter(fh, fieldnames=FIELDS + (list(BG_METRICS) if args.use_mask else []), extrasaction="ignore")
+        edited = list(EDITED_METRICS) if args.use_mask and getattr(calc, "_clip", None) is not None else []
+        w = csv.DictWriter(fh, fieldnames=FIELDS + (list(BG_METRICS) if args.use_mask else []) + edited, extrasaction="ignore")
         w.writeheader()
         w.writerows([{k: ("" if v is None else v) for k, v in r.items()} for r in rows])
     print(f"      Saved detailed metrics to: {args.results_file}")
-    summary = summarize(rows, METRICS + (BG_METRICS if args.use_mask else ()))
+    summary = summarize(rows, METRICS + (BG_METRICS if args.use_mask else ()) + tuple(edited))
     with open(args.summary_file, "w") as fh:
         json.dump(summary, fh, indent=2)
     print(f"      Saved summary statistics to: {args.summary_file}")
@@ -186,6 +209,8 @@ def main(argv=None):
               ("clip_score", "CLIP Score:", ".2f"), ("dino_distance", "DINO Dist.:", ".4f"))
     if args.use_mask:
         labels += (("bg_ssim", "Bg SSIM:   ", ".4f"), ("bg_psnr", "Bg PSNR:   ", ".2f"), ("bg_mse", "Bg MSE:    ", ".6f"))
+    if edited:
+        labels += (("clip_score_edited", "CLIP edited:", ".2f"),)
     for k, label, spec in labels:
         print(f"  {label} {fmt(summary['overall'][k], spec)}")
     print("\nMetrics by Category:")

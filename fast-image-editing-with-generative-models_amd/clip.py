@@ -1,4 +1,4 @@
-"""CLIP text encoders on HIP kernels (upstream transformers modeling_clip.py).
+"""CLIP text encoders (and the image tower of the CLIP score) on HIP kernels (upstream transformers modeling_clip.py).
 
 Pre-LN transformer, causal 77x77 attention (head dim 64 in both CLIP-L and OpenCLIP-bigG), returns what
 encode_prompt() consumes: hidden_states[-2] (penultimate layer, before the final LayerNorm) and -- for the
@@ -73,3 +73,48 @@ class ClipText:
                 ctx._keep.append(idx)             # a launch program reads the indices by raw pointer: keep a converted copy alive
             pooled = self.proj(ctx, ctx.clip_embed(idx.view(-1, 1), last, self.zero_row))
         return penult, pooled
+
+
+class ClipVision:
+    """The image tower of a CLIPModel (`vision_model.*` + `visual_projection` of upstream modeling_clip.py): pre-LN ViT.  The
+    bias-free patch convolution is a GEMM over the patch rows fie_clip_patches_u8_* wrote; class token and position table are added by
+    fie_vit_embed_*; `pre_layrnorm` (upstream's spelling), N layers of non-causal attention, then post_layernorm and the projection on the CLS rows only.
+    No torch kernel in the walk.  Runs in the fp16 and in the exact-fp32 context."""
+
+    def __init__(self, ctx, cfg, sd):
+        self.ctx, self.cfg = ctx, cfg
+        p = "vision_model."
+        self.patch = Linear(ctx, None, None, w=sd[p + "embeddings.patch_embedding.weight"])      # [C, 3, ps, ps] -> [C, 3 ps ps]
+        self.cls = _dev(ctx, sd[p + "embeddings.class_embedding"].reshape(-1))
+        self.pos = _dev(ctx, sd[p + "embeddings.position_embedding.weight"])
+        if self.pos.shape != (cfg["tokens"], cfg["hidden"]):
+            raise ValueError(f"clip_vision: position table {tuple(self.pos.shape)} for {cfg['tokens']} tokens x {cfg['hidden']}")
+        self.pre = Norm(ctx, sd, p + "pre_layrnorm")
+        self.layers = []
+        for i in range(cfg["layers"]):
+            q = f"{p}encoder.layers.{i}."
+            w = torch.cat([sd[q + f"self_attn.{n}_proj.weight"] for n in "qkv"], 0)
+            b = torch.cat([sd[q + f"self_attn.{n}_proj.bias"] for n in "qkv"], 0)
+            self.layers.append(dict(
+                ln1=Norm(ctx, sd, q + "layer_norm1"), qkv=Linear(ctx, None, None, w=w, b=b),
+                out=Linear(ctx, sd, q + "self_attn.out_proj"), ln2=Norm(ctx, sd, q + "layer_norm2"),
+                fc1=Linear(ctx, sd, q + "mlp.fc1"), fc2=Linear(ctx, sd, q + "mlp.fc2")))
+        self.post = Norm(ctx, sd, p + "post_layernorm")
+        self.proj = Linear(ctx, None, None, w=sd["visual_projection.weight"])
+        self.act = hip.ACT_QUICK_GELU if cfg["act"] == "quick_gelu" else hip.ACT_GELU
+
+    def __call__(self, patches, n):
+        """patches: [n * P, 3 ps ps] (ctx.clip_patches).  Returns the image embeddings [n, projection_dim]."""
+        ctx, cfg = self.ctx, self.cfg
+        c, heads, t = cfg["hidden"], cfg["heads"], cfg["tokens"]
+        x = ctx.vit_embed(self.patch(ctx, patches), self.cls, self.pos, n)
+        x = ctx.layernorm(x, self.pre.g, self.pre.b, cfg["eps"])
+        for L in self.layers:
+            y = ctx.layernorm(x, L["ln1"].g, L["ln1"].b, cfg["eps"])
+            qkv = L["qkv"](ctx, y)
+            a = ctx.attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], heads, c // heads, t, t, n, causal=False)
+            x = L["out"](ctx, a, residual=x)
+            y = ctx.layernorm(x, L["ln2"].g, L["ln2"].b, cfg["eps"])
+            x = L["fc2"](ctx, L["fc1"](ctx, y, act=self.act), residual=x)
+        cls_rows = x.view(n, t, c)[:, 0]                  # a strided view (row stride t c): the LayerNorm reads the CLS rows in place
+        return self.proj(ctx, ctx.layernorm(cls_rows, self.post.g, self.post.b, cfg["eps"]))

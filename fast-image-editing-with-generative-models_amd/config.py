@@ -132,6 +132,40 @@ def clip_cfg(c, name="clip(config.json)", pad_token_id=None):
                 bos_token_id=c.get("bos_token_id", 0))
 
 
+def clip_vision_cfg(c, name="clip_vision(config.json)"):
+    """`c` = a CLIPConfig dict (`text_config` / `vision_config` / `projection_dim`, as `CLIPModel.save_pretrained` writes it) -> the graph config of
+    the image tower (`CLIPVisionModelWithProjection`; clip.py: ClipVision).  Missing keys take CLIPVisionConfig's defaults."""
+    v = c.get("vision_config")
+    if not isinstance(v, dict):
+        raise ValueError("clip_vision: the config has no vision_config (a CLIPModel directory is needed, not a text encoder's)")
+    hidden, heads = v.get("hidden_size", 768), v.get("num_attention_heads", 12)
+    if hidden % heads or hidden // heads != 64:
+        raise ValueError(f"clip_vision: head dim {hidden / heads:g} (hidden {hidden} / {heads} heads) -- the HIP attention kernels are built for 64")
+    image, patch = v.get("image_size", 224), v.get("patch_size", 32)
+    if image % patch:
+        raise ValueError(f"clip_vision: image size {image} is not divisible by the patch size {patch}")
+    if patch % 8:
+        raise ValueError(f"clip_vision: patch size {patch} -- the patch kernel writes 8 pixels of a patch row at a time (multiples of 8)")
+    act = v.get("hidden_act", "quick_gelu")
+    if act not in ("quick_gelu", "gelu"):
+        raise ValueError(f"clip_vision: hidden_act {act!r} is not supported (quick_gelu or gelu)")
+    return dict(kind="clip_vision", name=name, hidden=hidden, layers=v.get("num_hidden_layers", 12), heads=heads,
+                intermediate=v.get("intermediate_size", 3072), act=act, eps=v.get("layer_norm_eps", 1e-5), image_size=image, patch_size=patch,
+                tokens=(image // patch) ** 2 + 1, projection_dim=c.get("projection_dim", v.get("projection_dim", 512)))
+
+
+def clip_score_text_cfg(c, name="clip_score_text(config.json)"):
+    """The text half of the same CLIPConfig dict, through clip_cfg: always WITH the projection (CLIPModel.text_projection).  Missing keys take
+    CLIPTextConfig's defaults."""
+    t = c.get("text_config")
+    if not isinstance(t, dict):
+        raise ValueError("clip_score: the config has no text_config (a CLIPModel directory is needed)")
+    full = dict(vocab_size=49408, hidden_size=512, intermediate_size=2048, num_hidden_layers=12, num_attention_heads=8)
+    full.update(t)
+    full.update(architectures=["CLIPTextModelWithProjection"], projection_dim=c.get("projection_dim", t.get("projection_dim", 512)))
+    return clip_cfg(full, name=name)
+
+
 BUILDERS = {"unet": unet_cfg, "controlnet": controlnet_cfg, "vae": vae_cfg, "clip_l": clip_cfg, "clip_g": clip_cfg}
 
 

@@ -114,6 +114,13 @@ SIGNATURES = {
     "fie_pixels_out_composite_f32_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
     "fie_metrics_workspace_bytes": [_I, _I, _I],
     "fie_metrics_pairs_u8": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _L],
+    "fie_clip_mask_rgb_u8": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "fie_clip_patches_u8_f16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "fie_clip_patches_u8_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "fie_vit_embed_f16": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "fie_vit_embed_f32": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "fie_clip_score_f16": [_P, _P, _L, _P, _L, _I, _I, _P],
+    "fie_clip_score_f32": [_P, _P, _L, _P, _L, _I, _I, _P],
     "fie_debug_force_tile": [_P, _I],
     "fie_debug_attn_variant": [_P, _I],
     "fie_debug_gn_onepass": [_P, _I],
@@ -313,7 +320,7 @@ class Context:
         self.ln_fold_which = os.environ.get("FIE_LN_FOLD_WHICH", "qkv,q2")      # which of the two folds run (A/B)
         self.ln_fold_ff1 = os.environ.get("FIE_LN_FOLD_FF1", "0") != "0"
         self.conv_plus_shortcut = os.environ.get("FIE_CONV_PLUS", "1") != "0"   # resnet conv2 + 1x1 shortcut as one GEMM (fie_conv3x3_plus_nhwc_f16)      # 2x-upsampling convs as four 2x2 convs (fie_conv_up2x_nhwc_f16)
-        self._resize_tables = {}       # (in, out) -> (taps, bounds, ksize) of the LANCZOS resample, on the device
+        self._resize_tables = {}       # (in, out) -> (taps, bounds, ksize) of the LANCZOS resample, on the device; ("bicubic", in, out) likewise; ("nearest", in, out) -> indices
         self.ws_tag = 0
         self._keep = None              # list collecting the tensors allocated while a program is being recorded (Context.record)
         self.w8 = False                # while True, pack_linear / pack_conv3x3 quantise eligible weights to fp8 e4m3 (see W8)
@@ -919,16 +926,26 @@ class Context:
         h, w, _ = rgb_u8.shape
         return self._resize(rgb_u8, h, w, out_h, out_w, (3,), lib().fie_resize_rgb_u8)
 
-    def _resize(self, src, h, w, out_h, out_w, chan, entry):
+    def resize_bicubic(self, rgb_u8, out_h, out_w, out=None):
+        """u8 [H, W, 3] device tensor -> u8 [out_h, out_w, 3], bit-exact with PIL's `resize(..., Image.BICUBIC)` (what CLIPImageProcessor resizes
+        with): the kernels of resize_lanczos on BICUBIC tables.  `out`: a contiguous u8 [out_h, out_w, 3] tensor to write (a slice of a batch)."""
+        self.sync_stream()
+        assert rgb_u8.dtype == torch.uint8 and rgb_u8.is_contiguous() and rgb_u8.dim() == 3
+        h, w, _ = rgb_u8.shape
+        return self._resize(rgb_u8, h, w, out_h, out_w, (3,), lib().fie_resize_rgb_u8, filter="bicubic", out=out)
+
+    def _resize(self, src, h, w, out_h, out_w, chan, entry, filter="lanczos", out=None):
         from . import resize
         tabs = []
         for n_in, n_out in ((w, out_w), (h, out_h)):
-            key = (n_in, n_out)
+            key = (n_in, n_out) if filter == "lanczos" else (filter, n_in, n_out)
             if n_in != n_out and key not in self._resize_tables:
-                kk, bounds, ks = resize.coefficients(n_in, n_out)
+                kk, bounds, ks = resize.coefficients(n_in, n_out, filter)
                 self._resize_tables[key] = (torch.from_numpy(kk).to(self.device), torch.from_numpy(bounds).to(self.device), ks)
             tabs.append(self._resize_tables.get(key) if n_in != n_out else (None, None, 0))
-        out = torch.empty((out_h, out_w) + chan, device=src.device, dtype=torch.uint8)
+        if out is None:
+            out = torch.empty((out_h, out_w) + chan, device=src.device, dtype=torch.uint8)
+        assert out.shape == (out_h, out_w) + chan and out.dtype == torch.uint8 and out.is_contiguous()
         tmp = torch.empty((h, out_w) + chan, device=src.device, dtype=torch.uint8) if (h != out_h and w != out_w) else None
         (kx, bx, ksx), (ky, by, ksy) = tabs
         _chk(entry(self.h, _p(src), h, w, _p(out), out_h, out_w, _p(kx), _p(bx), ksx, _p(ky), _p(by), ksy, _p(tmp)))
@@ -982,6 +999,63 @@ class Context:
         ws = torch.empty(nbytes // 8, device=self.device, dtype=torch.int64)
         out = torch.empty((n, 4), device=self.device, dtype=torch.int64)
         _chk(lib().fie_metrics_pairs_u8(self.h, _p(a), _p(b), _p(mask), n, h, w, _p(out), _p(ws), nbytes))
+        return out
+
+    # ------------------------------------------------------------------ CLIP score (csrc/clip_score.hip)
+    def clip_mask(self, rgb_u8, mask_l, out=None):
+        """u8 [n, H, W, 3] (or [H, W, 3]) images with every pixel outside the edited region set to 0.  mask_l: u8 [n, MH, MW] (or [MH, MW]), L >= 128 =
+        edited, of any size: sampled as Pillow's NEAREST resize to H x W would (fie_clip_mask_rgb_u8)."""
+        from . import resize
+        self.sync_stream()
+        single = rgb_u8.dim() == 3
+        a, m = (rgb_u8[None], mask_l[None]) if single else (rgb_u8, mask_l)
+        n, h, w, c = a.shape
+        if c != 3 or a.dtype != torch.uint8 or m.dtype != torch.uint8 or m.dim() != 3 or m.shape[0] != n or not a.is_contiguous() or not m.is_contiguous():
+            raise ValueError(f"clip_mask: contiguous u8 [n, H, W, 3] images and u8 [n, MH, MW] masks, got {tuple(a.shape)} {a.dtype} and {tuple(m.shape)} {m.dtype}")
+        mh, mw = m.shape[1:]
+        tabs = []
+        for n_in, n_out in ((mh, h), (mw, w)):
+            key = ("nearest", n_in, n_out)
+            if n_in != n_out and key not in self._resize_tables:
+                self._resize_tables[key] = torch.from_numpy(resize.nearest_indices(n_in, n_out)).to(self.device)
+            tabs.append(self._resize_tables.get(key) if n_in != n_out else None)
+        if out is None:
+            out = torch.empty_like(a)
+        _chk(lib().fie_clip_mask_rgb_u8(self.h, _p(a), _p(m), n, h, w, mh, mw, _p(tabs[0]), _p(tabs[1]), _p(out)))
+        return out[0] if single else out
+
+    def clip_patches(self, rgb_u8, top, left, size, patch, mean, std):
+        """u8 [n, H, W, 3] (the images after the processor's resize) -> [n * (size / patch)^2, 3 patch^2] in the context's dtype: centre crop at
+        (top, left), /255, (x - mean) / std, patchify, cast -- one launch (fie_clip_patches_u8_*)."""
+        self.sync_stream()
+        n, h, w, c = rgb_u8.shape
+        if c != 3 or rgb_u8.dtype != torch.uint8 or not rgb_u8.is_contiguous():
+            raise ValueError(f"clip_patches: a contiguous u8 [n, H, W, 3] tensor, got {tuple(rgb_u8.shape)} {rgb_u8.dtype}")
+        out = self._alloc((n * (size // max(patch, 1)) ** 2, 3 * patch * patch))
+        fn = lib().fie_clip_patches_u8_f32 if self.f32 else lib().fie_clip_patches_u8_f16
+        _chk(fn(self.h, _p(rgb_u8), n, h, w, int(top), int(left), int(size), int(patch), (_F * 3)(*mean), (_F * 3)(*std), _p(out)))
+        return out
+
+    def vit_embed(self, patches, cls, pos, n):
+        """patches [n * P, C] (the patch GEMM's output), cls [C], pos [1 + P, C] -> the tower's input tokens [n * (1 + P), C] (fie_vit_embed_*)."""
+        self.sync_stream()
+        rows, c = patches.shape
+        p = rows // n
+        assert rows == n * p and pos.shape == (p + 1, c) and cls.numel() == c and patches.is_contiguous() and pos.is_contiguous() and cls.is_contiguous()
+        out = self._alloc((n * (p + 1), c))
+        _chk((lib().fie_vit_embed_f32 if self.f32 else lib().fie_vit_embed_f16)(self.h, _p(patches), _p(cls), _p(pos), n, p, c, _p(out)))
+        return out
+
+    def clip_score(self, img_emb, txt_emb, out=None):
+        """[n, P] image and text embeddings (the context's dtype, last dim contiguous) -> f32 [n, 2] = (100 cos, max(100 cos, 0)) per pair, on the
+        device (fie_clip_score_*): one launch, no synchronisation."""
+        self.sync_stream()
+        n, p = img_emb.shape
+        if txt_emb.shape != img_emb.shape or img_emb.dtype != self.dtype or txt_emb.dtype != self.dtype or img_emb.stride(1) != 1 or txt_emb.stride(1) != 1:
+            raise ValueError(f"clip_score: two [n, P] {self.dtype} tensors of one shape, got {tuple(img_emb.shape)} {img_emb.dtype} and {tuple(txt_emb.shape)} {txt_emb.dtype}")
+        if out is None:
+            out = self._alloc((n, 2), torch.float32)
+        _chk((lib().fie_clip_score_f32 if self.f32 else lib().fie_clip_score_f16)(self.h, _p(img_emb), img_emb.stride(0), _p(txt_emb), txt_emb.stride(0), n, p, _p(out)))
         return out
 
     def canny_device(self, rgb_u8, low=100, high=200):

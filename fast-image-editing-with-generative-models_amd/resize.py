@@ -1,9 +1,11 @@
-"""Coefficient tables of Pillow's 8-bit LANCZOS resample, restated (host side of csrc/resize.hip).
+"""Coefficient tables of Pillow's 8-bit LANCZOS / BICUBIC resample, restated (host side of csrc/resize.hip).
 
 Follows Pillow `src/libImaging/Resample.c`: `precompute_coeffs` (support 3 x max(scale, 1), bounds by truncating
 `center -/+ support + 0.5`, weights normalised to sum 1) and `normalize_coeffs_8bpc` (22-bit fixed point, round half away from
 zero).  The reference reaches it through `image.resize((1024, 1024), Image.LANCZOS)` (`src/pipeline.py:251`).  Pure Python / libm
-doubles, as Pillow's C: the tables -- and therefore the device result -- are bit-exact with Pillow (tests/test_cabi_cpu.py)."""
+doubles, as Pillow's C: the tables -- and therefore the device result -- are bit-exact with Pillow (tests/test_cabi_cpu.py).
+`filter="bicubic"` is Pillow's `bicubic_filter` (a = -0.5, support 2): what `CLIPImageProcessor` resizes with; the
+kernels are the same, taps and bounds come from the tables.  `nearest_indices` restates the index table of Pillow's NEAREST resize."""
 import math
 
 import numpy as np
@@ -23,11 +25,28 @@ def _lanczos(x):
     return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
 
 
-def coefficients(in_size, out_size):
+def _bicubic(x):
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+FILTERS = {"lanczos": (_lanczos, LANCZOS_SUPPORT), "bicubic": (_bicubic, 2.0)}
+
+
+def coefficients(in_size, out_size, filter="lanczos"):
     """-> (kk int32 [out_size, ksize], bounds int32 [out_size, 2] = (first input index, tap count), ksize)."""
+    if filter not in FILTERS:
+        raise ValueError(f"resample filter {filter!r}: one of {sorted(FILTERS)}")
+    kernel, base_support = FILTERS[filter]
     scale = float(np.float32(in_size) - np.float32(0)) / out_size          # Pillow's box is float32
     filterscale = max(scale, 1.0)
-    support = LANCZOS_SUPPORT * filterscale
+    support = base_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     kk = np.zeros((out_size, ksize), dtype=np.int32)
     bounds = np.zeros((out_size, 2), dtype=np.int32)
@@ -36,7 +55,7 @@ def coefficients(in_size, out_size):
         center = 0.0 + (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)                         # int(): truncation, as the C cast
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = [_lanczos((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        w = [kernel((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for v in w:
             ww += v
@@ -47,13 +66,25 @@ def coefficients(in_size, out_size):
     return kk, bounds, ksize
 
 
-def resample_numpy(rgb, out_h, out_w):
+def nearest_indices(in_size, out_size):
+    """int32 [out_size]: the input index Pillow's `resize(..., Image.NEAREST)` reads for every output position (`ImagingScaleAffine`: the
+    coordinate starts at scale / 2 and is ADVANCED by additions of scale, in doubles, then truncated)."""
+    a = float(in_size) / out_size
+    xo = a * 0.5
+    out = np.empty(out_size, dtype=np.int32)
+    for x in range(out_size):
+        out[x] = min(int(xo), in_size - 1)
+        xo += a
+    return out
+
+
+def resample_numpy(rgb, out_h, out_w, filter="lanczos"):
     """The two passes in numpy with the tables above (CPU checker of the tables; the product path is the HIP kernel)."""
     a = np.asarray(rgb, dtype=np.uint8)
     h, w, _ = a.shape
 
     def one_pass(img, axis_len, out_len):
-        kk, bounds, _ = coefficients(axis_len, out_len)
+        kk, bounds, _ = coefficients(axis_len, out_len, filter)
         out = np.empty((img.shape[0], out_len, 3), dtype=np.uint8)
         for o in range(out_len):
             x0, n = bounds[o]

@@ -570,6 +570,30 @@ int64_t fie_metrics_workspace_bytes(int n, int H, int W);
 int fie_metrics_pairs_u8(fie_ctx* ctx, const uint8_t* a, const uint8_t* b, const uint8_t* mask, int n, int H, int W, void* result,
                          void* workspace, int64_t workspace_bytes);
 
+/* ---- CLIP score on the device: the pieces around the ViT image tower, which itself runs on fie_gemm_* / fie_layernorm_* /
+ * fie_attention_f16.  All asynchronous on the ctx stream, none synchronises, none uses atomics.
+ *   fie_clip_mask_rgb_u8     the "edited" variant of n u8 [H, W, 3] images: pixels outside the edited region set to 0.  mask: u8 [n, MH, MW], L >= 128 =
+ *                            edited; when (MH, MW) != (H, W) it is sampled through ytab int32 [H] / xtab int32 [W], the source indices of Pillow's
+ *                            NEAREST resize (fie_amd/resize.py: nearest_indices; a table may be NULL when that axis keeps its size).  dst may be src.
+ *   fie_clip_patches_u8_*    src: u8 [n, H, W, 3], the images after the processor's resize.  Crops size x size at (top, left), x / 255, (x - mean[c]) /
+ *                            std[c] (mean, std: 3 HOST floats each) and writes the patch rows [n * (size / patch)^2, 3 patch^2], k = (c patch + py) patch
+ *                            + px: the K order of the patch-embedding weight [C, 3, patch, patch] viewed as a matrix.  patch % 8 == 0; out 16-byte aligned.
+ *                            f32: every value is the fp32 expression above; f16: its round-to-nearest-even.
+ *   fie_vit_embed_*          out [n, 1 + P, C]: row 0 = cls + pos[0], row 1 + i = patches[n, i] + pos[1 + i] (patches [n * P, C]: the patch GEMM's
+ *                            output; cls [C]; pos [1 + P, C]).  C % 8 == 0, operands 16-byte aligned.
+ *   fie_clip_score_*         img, txt: [n, P] embeddings (row strides ld_img / ld_txt in elements); out f32 [n, 2] = (100 cos, max(100 cos, 0)).  One wave per
+ *                            pair, fp32 sums in a fixed order: a pair's bits depend neither on n nor on its position.  A zero norm gives 0. */
+int fie_clip_mask_rgb_u8(fie_ctx* ctx, const uint8_t* src, const uint8_t* mask, int n, int H, int W, int MH, int MW, const int* ytab, const int* xtab,
+                         uint8_t* dst);
+int fie_clip_patches_u8_f16(fie_ctx* ctx, const uint8_t* src, int n, int H, int W, int top, int left, int size, int patch, const float* mean,
+                            const float* std, void* out);
+int fie_clip_patches_u8_f32(fie_ctx* ctx, const uint8_t* src, int n, int H, int W, int top, int left, int size, int patch, const float* mean,
+                            const float* std, void* out);
+int fie_vit_embed_f16(fie_ctx* ctx, const void* patches, const void* cls, const void* pos, int n, int P, int C, void* out);
+int fie_vit_embed_f32(fie_ctx* ctx, const void* patches, const void* cls, const void* pos, int n, int P, int C, void* out);
+int fie_clip_score_f16(fie_ctx* ctx, const void* img, int64_t ld_img, const void* txt, int64_t ld_txt, int n, int P, float* out);
+int fie_clip_score_f32(fie_ctx* ctx, const void* img, int64_t ld_img, const void* txt, int64_t ld_txt, int n, int P, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ shards the selected entries image-parallel over N GPUs (fie_amd.dist) and rank 0
     python run_batch.py --num_images 50 --editing_types 0 1 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run_batch.py --model ssd-1b
 
-Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics.
+Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir.
 """
 import argparse
 import json
@@ -99,7 +99,16 @@ def add_metrics_args(p):
     return p
 
 
-METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse")
+def add_clip_args(p):
+    """[additive] CLIP score of every edit.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--clip_score_dir", type=str, default=None,
+                   help="[additive] with --metrics: a local transformers CLIPModel directory (config.json, model.safetensors, vocab.json, merges.txt; "
+                        "openai/clip-vit-base-patch16 is the reference's); adds clip_score (and clip_score_edited with --use_mask) to every row.  "
+                        "Default: FIE_CLIP_SCORE_DIR, else <weights_dir>/clip_score when it exists")
+    return p
+
+
+METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse", "clip_score", "clip_score_edited")
 
 
 def select_entries(mapping, args, say=print):
@@ -291,7 +300,7 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    args = add_metrics_args(add_resolution_args(add_mask_args(build_parser()))).parse_args(argv)
+    args = add_clip_args(add_metrics_args(add_resolution_args(add_mask_args(build_parser())))).parse_args(argv)
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets
@@ -320,6 +329,12 @@ def main(argv=None):
     mine = fdist.shard([(i, k, e) for i, (k, e) in enumerate(selected)], rank, world)
 
     say(f"\n[3/3] Initializing FastEditor ({model_suffix})...")
+    clip_dir = None
+    if args.metrics:
+        from fie_amd import clip_score as hclip
+        clip_dir = hclip.resolve_dir(args.clip_score_dir)
+        if clip_dir is None and args.weights_dir and os.path.isdir(os.path.join(args.weights_dir, "clip_score")):
+            clip_dir = os.path.join(args.weights_dir, "clip_score")
     from src.pipeline import FastEditor
     import contextlib
     import io
@@ -327,7 +342,8 @@ def main(argv=None):
         import torch
         editor = FastEditor(model_name=args.model, device="cuda" if world == 1 else f"cuda:{local % max(torch.cuda.device_count(), 1)}",
                             enable_cpu_offload=not args.no_cpu_offload, use_full_precision=args.full_precision,
-                            use_full_controlnet=args.full_controlnet, weights_dir=args.weights_dir)
+                            use_full_controlnet=args.full_controlnet, weights_dir=args.weights_dir,
+                            clip_score_dir=clip_dir)
     if hasattr(editor, "pipe"):
         editor.pipe.set_progress_bar_config(disable=True)
     mem = editor.get_memory_usage()

@@ -48,6 +48,9 @@ def build_parser():
     a("--resolution", type=str, default="square",
       help="[additive] output size: 'square' (1024x1024, the reference's), 'auto' (the SDXL aspect-ratio bucket nearest the source's) or WxH "
            "(multiples of 64, 512..2048, at most 1024^2 pixels)")
+    a("--clip_score_dir", type=str, default=None,
+      help="[additive] with --compute_metrics: a local transformers CLIPModel directory (openai/clip-vit-base-patch16 is the reference's): fills the "
+           "CLIP score.  Default: FIE_CLIP_SCORE_DIR, else <FIE_WEIGHTS_DIR>/clip_score when it exists")
     return p
 
 
@@ -128,7 +131,7 @@ def main(argv=None):
     if args.compute_metrics:
         print("\n[4/4] Computing metrics...")
         from src.metrics import MetricsCalculator
-        calc = MetricsCalculator(device="cuda")
+        calc = MetricsCalculator(device="cuda", clip_dir=args.clip_score_dir)
         metrics = calc.calculate_all_metrics(source_img=source_img, edited_img=edited_img, prompt=args.prompt)
         labels = [("ssim", "SSIM (structure preservation):  ", ".4f", ""), ("lpips", "LPIPS (perceptual distance):    ", ".4f", ""),
                   ("psnr", "PSNR (signal quality):          ", ".2f", " dB"), ("mse", "MSE (pixel difference):         ", ".6f", ""),

@@ -3,27 +3,32 @@
 Evaluation only (not part of the denoising hot path): plain torch ops, as the reference's
 torchmetrics are.  Restated here: SSIM (torchmetrics defaults: 11x11 Gaussian, sigma 1.5, k1/k2 0.01/0.03,
 data_range 1), PSNR and MSE, all on 512x512 LANCZOS-resized RGB in [0,1] (reference :227-239, :291-347).
-LPIPS(squeeze), CLIPScore(ViT-B/16) and the DINO ViT-B/8 distance need checkpoints that only exist on the hub
-(reference :28, :179-186); offline they return None rather than a made-up number.
+LPIPS(squeeze) and the DINO ViT-B/8 distance need checkpoints that only exist on the hub (reference :28, :179-186); offline they
+return None rather than a made-up number.  CLIPScore(ViT-B/16) (reference :184-186, :271-289) runs on the device when a local
+`CLIPModel` directory is given (`clip_dir=`, else FIE_CLIP_SCORE_DIR, else <FIE_WEIGHTS_DIR>/clip_score): fie_amd/clip_score.py,
+DESIGN.md section 11; without one, and on the CPU, it returns None as well.
 
 On a GPU (`device="cuda..."`) the arithmetic is one HIP op (csrc/metrics.hip through `ctx.metrics_pairs`): each image is
 uploaded once, LANCZOS-resized on the device when it is not 512x512, and SSIM / PSNR / MSE of any number of pairs come from one launch and
 one synchronisation.  `device="cpu"` is the torch restatement above.  Additive: `calculate_all_metrics(..., mask=)` adds the background
 preservation scores `bg_ssim / bg_psnr / bg_mse` (both images zeroed inside the edited region, PIE-Bench's convention), and
-`calculate_pairs(sources, editeds, masks=None)` scores a list at once."""
+`calculate_pairs(sources, editeds, masks=None)` scores a list at once; with a CLIP directory `mask=` also adds `clip_score_edited` (the score of
+the image zeroed OUTSIDE the edited region) and `calculate_clip_scores(images, texts, masks=None)` scores a list."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 from PIL import Image
 
 import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory)
+from fie_amd import clip_score as hclip
+from fie_amd import mask as hmask
 from fie_amd import metrics as hmetrics
 
 TARGET = hmetrics.TARGET
 
 
 class MetricsCalculator:
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", clip_dir=None):
         self.device = device
         print(f"[MetricsCalculator] Initializing on {device}...")
         d = torch.arange(-5.0, 6.0)
@@ -35,7 +40,12 @@ class MetricsCalculator:
             from fie_amd import hip
             index = torch.device(device).index
             self._ctx = hip.context(torch.cuda.current_device() if index is None else index)
-        print("[MetricsCalculator] Initialization complete! (LPIPS / CLIP score / DINO: unavailable offline)")
+        self._clip = None                               # fie_amd.clip_score.ClipScorer: only on a GPU and only from a local CLIPModel directory
+        clip_dir = hclip.resolve_dir(clip_dir) if self._ctx is not None else None
+        if clip_dir:
+            print(f"[MetricsCalculator] Loading the CLIP score model from {clip_dir}")
+            self._clip = hclip.load(clip_dir, self._ctx)
+        print("[MetricsCalculator] Initialization complete! (LPIPS / DINO: unavailable offline" + ("" if self._clip else "; CLIP score: no model directory") + ")")
 
     def _pil_to_tensor(self, img):
         a = np.array(img).astype(np.float32) / 255.0
@@ -127,17 +137,64 @@ class MetricsCalculator:
         return None
 
     def calculate_clip_score(self, img, text):
-        return None
+        """max(100 cos(image embedding, text embedding), 0) of the reference's CLIPScore, or None without a model directory / on the CPU."""
+        if self._clip is None or img is None:
+            return None
+        return self.calculate_clip_scores([img], [text])[0]["clip_score"]
+
+    def calculate_clip_scores(self, images, texts, masks=None, unclamped=False):
+        """[additive] {"clip_score": float} per (image, text) pair of two lists; `masks` (None, or per pair None / a mask as calculate_pairs takes
+        it, NEAREST-resized to the image's size, L >= 128 = edited) adds "clip_score_edited": the score of the image with every pixel outside the
+        edited region set to 0.  One upload per image, one batched pass of the image tower per image size, all prompts in one pass of the text
+        tower, one synchronisation.  `unclamped`: 100 cos itself (may be negative) instead of the clamped score.  Without a model directory
+        every entry is None."""
+        if len(images) != len(texts) or (masks is not None and len(masks) != len(images)):
+            raise ValueError("images, texts and masks must be lists of one length")
+        if self._clip is None:
+            return [None] * len(images)
+        if not images:
+            return []
+        clip, ctx = self._clip, self._ctx
+        masks = list(masks) if masks is not None else [None] * len(images)
+        with torch.cuda.device(ctx.device):
+            devs = [torch.from_numpy(np.ascontiguousarray(np.array(im.convert("RGB") if im.mode != "RGB" else im))).to(ctx.device) for im in images]
+            mdevs = [None if m is None else torch.from_numpy(hmask.to_l_array(m)).to(ctx.device) for m in masks]
+            # items = (image, masked?) sorted into size groups: a group's rows are contiguous in the text pass and in the result
+            groups = {}
+            for i, d in enumerate(devs):
+                g = groups.setdefault(tuple(d.shape[:2]), [])
+                g.append((i, False))
+                if mdevs[i] is not None:
+                    g.append((i, True))
+            order = [it for g in groups.values() for it in g]
+            txt = clip.text_embeddings([texts[i] for i, _ in order])
+            rows = torch.empty((len(order), 2), device=ctx.device, dtype=torch.float32)
+            r0 = 0
+            for g in groups.values():
+                emb = clip.image_embeddings([devs[i] for i, _ in g], [mdevs[i] if masked else None for i, masked in g])
+                clip.score_rows(emb, txt[r0:r0 + len(g)], out=rows[r0:r0 + len(g)])
+                r0 += len(g)
+            host = rows.cpu().numpy()
+        out = [{} for _ in images]
+        for (i, masked), row in zip(order, host):
+            out[i]["clip_score_edited" if masked else "clip_score"] = float(row[0 if unclamped else 1])
+        return out
 
     def calculate_all_metrics(self, source_img, edited_img, prompt, mask=None):
         m = self.calculate_pairs([source_img], [edited_img], None if mask is None else [mask])[0]
-        return self.with_unavailable(m, source_img, edited_img, prompt)
+        return self.with_unavailable(m, source_img, edited_img, prompt, mask=mask)
 
-    def with_unavailable(self, m, source_img=None, edited_img=None, prompt=""):
-        """A calculate_pairs() dict in calculate_all_metrics()'s key order, with the metrics that need hub checkpoints as None."""
-        out = {"ssim": m["ssim"], "lpips": self.calculate_lpips(source_img, edited_img), "clip_score": self.calculate_clip_score(edited_img, prompt),
+    def with_unavailable(self, m, source_img=None, edited_img=None, prompt="", mask=None):
+        """A calculate_pairs() dict in calculate_all_metrics()'s key order, with the metrics that need hub checkpoints as None.  `clip_score`
+        is filled when the calculator has a CLIP model (and `clip_score_edited`, behind the bg_* keys, when a mask comes with it)."""
+        clip = {"clip_score": None}
+        if self._clip is not None and edited_img is not None:
+            clip = self.calculate_clip_scores([edited_img], [prompt], None if mask is None else [mask])[0]
+        out = {"ssim": m["ssim"], "lpips": self.calculate_lpips(source_img, edited_img), "clip_score": clip["clip_score"],
                "psnr": m["psnr"], "mse": m["mse"], "dino_distance": None}
         out.update({k: m[k] for k in hmetrics.BG_KEYS if k in m})
+        if "clip_score_edited" in clip:
+            out["clip_score_edited"] = clip["clip_score_edited"]
         return out
 
     def clear_memory(self):

@@ -4,7 +4,8 @@ Same constructor, `MODEL_CONFIGS`, `edit()` / `preprocess_image()` / `clear_memo
 signatures, defaults, attributes and error behaviour; `self.pipe` is an `fie_amd.pipe.HipImg2ImgPipeline`
 (hand-written HIP kernels behind a C ABI) instead of the diffusers pipeline.  There is no CPU fallback: a missing
 HIP library or GPU raises.  Additive: `set_in_flight(n)` / `worker_slot(i)` (several edits in flight from worker threads), and keyword-only knobs: `weights_dir`, `seed_weights`, `noise_dtype`, `weight_dtype` ("f8e4m3": fp8 UNet / ControlNet weights, BASELINE config 5), `broadcast_weights`
-(under torch.distributed with world_size > 1, rank 0's synthetic weights are broadcast over RCCL instead of regenerated).
+(under torch.distributed with world_size > 1, rank 0's synthetic weights are broadcast over RCCL instead of regenerated), `clip_score_dir` (a local
+transformers CLIPModel directory: `edit(..., metrics=True)` then also returns the CLIP score of the edit).
 """
 import os
 import threading
@@ -42,7 +43,7 @@ class FastEditor:
 
     def __init__(self, model_name="sdxl", device="cuda", dtype=torch.float16, enable_cpu_offload=True,
                  use_full_precision=False, use_full_controlnet=False, *, weights_dir=None, seed_weights=1234,
-                 noise_dtype=None, broadcast_weights=True, weight_dtype="f16"):
+                 noise_dtype=None, broadcast_weights=True, weight_dtype="f16", clip_score_dir=None):
         if model_name not in self.MODEL_CONFIGS and model_name not in self._EXTRA_STACKS:
             raise ValueError(f"Unknown model: {model_name}. Choose from {list(self.MODEL_CONFIGS.keys())}")
         self.model_name = model_name
@@ -100,6 +101,12 @@ class FastEditor:
         self.controlnet = self.pipe.controlnet
         self._tls = threading.local()          # .slot: graph slot of the calling worker thread (set_in_flight)
         self._metric_rows = {}                 # (slot, images) -> pinned int64 [images, 4]: where an edit's metric rows land (metrics=True)
+        self.clip_scorer = None                # fie_amd.clip_score.ClipScorer: only from a directory, never a made-up number
+        self._clip_rows = {}                   # (slot, rows) -> pinned f32 [rows, 2]: where an edit's CLIP score rows land
+        if clip_score_dir:
+            from fie_amd import clip_score as hclip
+            log(f"Loading the CLIP score model from {clip_score_dir}")
+            self.clip_scorer = hclip.load(clip_score_dir, ctx)
         del sds
         log("Enabling memory optimizations...")
         # 288 GB of HBM: offload / slicing flags are accepted and ignored (reference toggles them at :165-179)
@@ -156,7 +163,9 @@ class FastEditor:
         LANCZOS-resized to it; resizing the result back to the source's size is the caller's choice.
         [additive] `metrics=True`: returns (image, dict) with `ssim`, `psnr`, `mse` of the edit (and `bg_ssim`, `bg_psnr`, `bg_mse` with a mask),
         scored on the device behind the edit: the pair is the ORIGINAL source and the u8 result, each LANCZOS-resized to 512x512 -- what
-        evaluate.py would score had the result been saved losslessly.  No additional host wait."""
+        evaluate.py would score had the result been saved losslessly.  No additional host wait.  With
+        `FastEditor(clip_score_dir=...)` the dict also holds `clip_score` (the result against `prompt`) and, with a mask,
+        `clip_score_edited` (the result zeroed outside the edited region)."""
         size = buckets.target_size(resolution, image.size)
         hmask.check_args(mask_blur, paste_back, mask is not None)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
@@ -180,15 +189,17 @@ class FastEditor:
                         control_image=control_dev, strength=strength, num_inference_steps=num_inference_steps,
                         guidance_scale=guidance_scale, controlnet_conditioning_scale=controlnet_conditioning_scale,
                         generator=generator, post_check=finish, mask_image=mask_dev, mask_blur=mask_blur, paste_back=paste_back,
-                        after_device=self._scorer(slot, origs, omasks) if metrics else None)
+                        after_device=self._scorer(slot, origs, omasks, [prompt]) if metrics else None)
         if not metrics:
             return res.images[0]
         return res.images[0], self._scores(res.extra, [mask_l is not None])[0]
 
-    def _scorer(self, slot, origs, omasks):
+    def _scorer(self, slot, origs, omasks, prompts=None):
         """The `after_device` hook of an edit with metrics=True: queues, on the edit's stream behind its result, the LANCZOS resizes to
         512x512 (sources, results, masks), ONE fie_metrics_pairs_u8 launch pair for all images of the job and the copy of the 32-byte result
-        rows into pinned host memory of the slot.  The edit's own final synchronisation (the image's D2H) completes them."""
+        rows into pinned host memory of the slot.  The edit's own final synchronisation (the image's D2H) completes them.  With a CLIP model
+        (`clip_scorer`) the hook also queues the CLIP score of every result against its prompt (cached text embedding, one batched pass of the
+        image tower, the masked variants in the same pass) and returns (metric rows, CLIP rows, which (image, masked) each CLIP row is)."""
         ctx = self.pipe.ctx
         th, tw = hmetrics.TARGET[1], hmetrics.TARGET[0]
         to512 = lambda t: t if tuple(t.shape[:2]) == (th, tw) else ctx.resize_lanczos(t.contiguous(), th, tw)
@@ -208,11 +219,27 @@ class FastEditor:
             if host is None:
                 host = self._metric_rows[(slot, len(outs))] = torch.empty((len(outs), 4), dtype=torch.int64).pin_memory()
             host.copy_(rows, non_blocking=True)
-            return host
+            if self.clip_scorer is None:
+                return host
+            clip = self.clip_scorer
+            items = [(i, False) for i in range(len(outs))] + [(i, True) for i, m in enumerate(omasks) if m is not None]
+            with self.pipe.eager_lock:
+                txts = [clip.text_embedding(prompts[i]) for i, _ in items]
+                emb = clip.image_embeddings([outs[i] for i, _ in items], [omasks[i] if masked else None for i, masked in items])
+                crow = clip.score_rows(emb, txts[0] if len(txts) == 1 else torch.cat(txts))
+            chost = self._clip_rows.get((slot, len(items)))
+            if chost is None:
+                chost = self._clip_rows[(slot, len(items))] = torch.empty((len(items), 2), dtype=torch.float32).pin_memory()
+            chost.copy_(crow, non_blocking=True)
+            return host, chost, items
         return score
 
-    def _scores(self, host_rows, has_mask):
-        return hmetrics.rows_to_dicts(host_rows.numpy().copy(), hmetrics.TARGET[1], hmetrics.TARGET[0], has_mask)
+    def _scores(self, extra, has_mask):
+        host_rows, clip_rows, items = extra if isinstance(extra, tuple) else (extra, None, ())
+        out = hmetrics.rows_to_dicts(host_rows.numpy().copy(), hmetrics.TARGET[1], hmetrics.TARGET[0], has_mask)
+        for (i, masked), row in zip(items, clip_rows.numpy().copy() if clip_rows is not None else ()):
+            out[i]["clip_score_edited" if masked else "clip_score"] = float(row[1])
+        return out
 
     def _mask_device(self, mask_l, size, original=None):
         """uint8 [H, W] mode-L mask (or None) -> u8 [size[1], size[0]] on the device: LANCZOS-resized as the source is (fie_resize_l_u8,
@@ -282,7 +309,8 @@ class FastEditor:
         res = self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls,
                         strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                         controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens, mask_image=mask_devs,
-                        mask_blur=mask_blur, paste_back=paste_back, after_device=self._scorer(slot, origs, omasks) if metrics else None)
+                        mask_blur=mask_blur, paste_back=paste_back,
+                        after_device=self._scorer(slot, origs, omasks, list(prompts)) if metrics else None)
         if not metrics:
             return res.images
         return res.images, self._scores(res.extra, [m is not None for m in omasks])
