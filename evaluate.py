@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Evaluation harness -- drop-in for /root/reference/evaluate.py (same flags, same `metrics.csv` columns and
 `summary.json` layout, reference :193-271), on the metrics this build restates (`src/metrics.py`: SSIM, PSNR, MSE).
-LPIPS / CLIP score / DINO distance need hub checkpoints: their cells are empty in the CSV and `null` in the JSON.
+LPIPS / CLIP score / DINO distance need checkpoints: without a local model directory (`--clip_score_dir`, `--dino_dir`) their cells are empty in
+the CSV and `null` in the JSON; LPIPS always.
 Additive: `--use_mask` appends the background-preservation columns `bg_ssim, bg_psnr, bg_mse` (each item's PIE-Bench `mask`; both images
 zeroed inside the edited region first) to the CSV and to `summary.json`.  Pairs are scored in chunks: on a GPU one launch per chunk.
 
@@ -59,6 +60,14 @@ def add_clip_args(p):
                    help="[additive] a local transformers CLIPModel directory (openai/clip-vit-base-patch16 is the reference's): fills the clip_score "
                         "column (and, with --use_mask, adds clip_score_edited beside bg_*).  Default: FIE_CLIP_SCORE_DIR, else "
                         "<FIE_WEIGHTS_DIR>/clip_score when it exists; without one the column stays empty")
+    return p
+
+
+def add_dino_args(p):
+    """[additive] DINO structure distance.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--dino_dir", type=str, default=None,
+                   help="[additive] a local transformers ViTModel directory (facebook/dino-vitb8 is the reference's): fills the dino_distance "
+                        "column for square pairs.  Default: FIE_DINO_DIR, else <FIE_WEIGHTS_DIR>/dino when it exists; without one the column stays empty")
     return p
 
 
@@ -123,10 +132,19 @@ def evaluate_entries(entries, args, calc, progress=None):
                                                    [p[6] for p in pending] if use_mask else None)
             except Exception as e:
                 print(f"\n      Error computing CLIP scores: {e}")
-        for (index, image_id, rel, entry, a, b, _), m, cs in zip(pending, ms, clips):
+        dinos = [None] * len(pending)
+        if getattr(calc, "_dino", None) is not None:      # the chunk's structure distances, one batched pass per size; square pairs only
+            sq = [i for i, p in enumerate(pending) if p[4].size[0] == p[4].size[1] and p[5].size[0] == p[5].size[1]]
+            try:
+                for i, d in zip(sq, calc.calculate_dino_distances([pending[i][4] for i in sq], [pending[i][5] for i in sq])):
+                    dinos[i] = d
+            except Exception as e:
+                print(f"\n      Error computing DINO distances: {e}")
+        for (index, image_id, rel, entry, a, b, _), m, cs, dd in zip(pending, ms, clips, dinos):
             if m is None:
                 continue
             m = calc.with_unavailable(m, None, None, entry.get("editing_prompt", ""))
+            m["dino_distance"] = dd
             if cs:
                 m.update(cs)
             if with_edited:
@@ -158,7 +176,7 @@ def evaluate_entries(entries, args, calc, progress=None):
 
 
 def main(argv=None):
-    args = add_clip_args(add_mask_args(build_parser())).parse_args(argv)
+    args = add_dino_args(add_clip_args(add_mask_args(build_parser()))).parse_args(argv)
     import fie_amd  # noqa: F401
     from fie_amd import dist as fdist
     from src.metrics import MetricsCalculator
@@ -172,7 +190,7 @@ def main(argv=None):
     say(f"\n[2/4] Scanning outputs in {args.outputs_dir}")
     say(f"\n[3/4] Initializing metrics on {args.device}...")
     device = args.device if world == 1 or not args.device.startswith("cuda") else f"cuda:{local}"
-    calc = MetricsCalculator(device=device, clip_dir=args.clip_score_dir)
+    calc = MetricsCalculator(device=device, clip_dir=args.clip_score_dir, dino_dir=args.dino_dir)
     mine = fdist.shard([(i, k, e) for i, (k, e) in enumerate(mapping.items())], rank, world)
     progress = None
     if rank == 0:

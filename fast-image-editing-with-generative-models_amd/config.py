@@ -166,6 +166,32 @@ def clip_score_text_cfg(c, name="clip_score_text(config.json)"):
     return clip_cfg(full, name=name)
 
 
+def dino_vit_cfg(c, layer=11, name="dino_vit(config.json)"):
+    """`c` = a transformers ViTConfig dict (a `ViTModel` directory such as facebook/dino-vitb8) -> the graph config of the tower the DINO structure
+    distance walks up to the key projection of block `layer` (dino.py: DinoVit).  Missing keys take ViTConfig's defaults.
+    What the device path does not restate is refused by name."""
+    hidden, heads = c.get("hidden_size", 768), c.get("num_attention_heads", 12)
+    if hidden % heads or hidden // heads != 64:
+        raise ValueError(f"dino_vit: head dim {hidden / heads:g} (hidden_size {hidden} / num_attention_heads {heads}) -- the HIP attention kernels are built for 64")
+    image, patch = c.get("image_size", 224), c.get("patch_size", 16)
+    if patch % 8:
+        raise ValueError(f"dino_vit: patch_size {patch} -- the patch kernel writes 8 pixels of a patch row at a time (multiples of 8)")
+    if image % patch:
+        raise ValueError(f"dino_vit: image_size {image} is not divisible by the patch_size {patch}")
+    act = c.get("hidden_act", "gelu")
+    if act != "gelu":
+        raise ValueError(f"dino_vit: hidden_act {act!r} is not supported (only the exact gelu of ViTModel)")
+    if c.get("num_channels", 3) != 3:
+        raise ValueError(f"dino_vit: num_channels {c.get('num_channels')} -- RGB images only")
+    if c.get("qkv_bias", True) is not True:
+        raise ValueError("dino_vit: qkv_bias=False is not supported (the key projection carries its bias)")
+    layers = c.get("num_hidden_layers", 12)
+    if not isinstance(layer, int) or not 0 <= layer < layers:
+        raise ValueError(f"dino_vit: layer {layer!r} is out of range for num_hidden_layers {layers}")
+    return dict(kind="dino_vit", name=name, hidden=hidden, layers=layers, heads=heads, intermediate=c.get("intermediate_size", 3072), act=act,
+                eps=c.get("layer_norm_eps", 1e-12), image_size=image, patch_size=patch, tokens=(image // patch) ** 2 + 1, layer=layer)
+
+
 BUILDERS = {"unet": unet_cfg, "controlnet": controlnet_cfg, "vae": vae_cfg, "clip_l": clip_cfg, "clip_g": clip_cfg}
 
 

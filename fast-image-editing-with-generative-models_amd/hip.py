@@ -121,6 +121,11 @@ SIGNATURES = {
     "fie_vit_embed_f32": [_P, _P, _P, _P, _I, _I, _I, _P],
     "fie_clip_score_f16": [_P, _P, _L, _P, _L, _I, _I, _P],
     "fie_clip_score_f32": [_P, _P, _L, _P, _L, _I, _I, _P],
+    "fie_dino_patches_u8_f16": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P],
+    "fie_dino_patches_u8_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P],
+    "fie_selfsim_workspace_bytes": [_I, _I],
+    "fie_selfsim_mse_f16": [_P, _P, _P, _L, _I, _I, _I, _P, _P],
+    "fie_selfsim_mse_f32": [_P, _P, _P, _L, _I, _I, _I, _P, _P],
     "fie_debug_force_tile": [_P, _I],
     "fie_debug_attn_variant": [_P, _I],
     "fie_debug_gn_onepass": [_P, _I],
@@ -173,7 +178,7 @@ def lib():
             fn.argtypes = args
             fn.restype = _L if name in ("fie_groupnorm_workspace_bytes", "fie_canny_workspace_bytes", "fie_time_embed_workspace_bytes", "fie_gn_stats_bytes", "fie_debug_oplog_read", "fie_debug_tune_candidates_read", "fie_vae_decode_workspace_bytes",
                                        "fie_vae_encode_workspace_bytes", "fie_clip_text_workspace_bytes", "fie_unet_workspace_bytes", "fie_controlnet_workspace_bytes",
-                                       "fie_unet_step_cache_bytes", "fie_metrics_workspace_bytes") else _I
+                                       "fie_unet_step_cache_bytes", "fie_metrics_workspace_bytes", "fie_selfsim_workspace_bytes") else _I
         _lib.fie_last_error.restype = ctypes.c_char_p
         _lib.fie_last_error.argtypes = []
         _lib.fie_debug_last_gemm_kernel.restype = ctypes.c_char_p
@@ -1056,6 +1061,56 @@ class Context:
         if out is None:
             out = self._alloc((n, 2), torch.float32)
         _chk((lib().fie_clip_score_f32 if self.f32 else lib().fie_clip_score_f16)(self.h, _p(img_emb), img_emb.stride(0), _p(txt_emb), txt_emb.stride(0), n, p, _p(out)))
+        return out
+
+    # ------------------------------------------------------------------ DINO structure distance (csrc/dino.hip)
+    def _aa_tables(self, n_in, n_out):
+        """Device tables of the antialias triangle filter (resize.py: aa_coefficients), cached per (in, out) size like the LANCZOS / BICUBIC ones."""
+        from . import resize
+        key = ("aa", n_in, n_out)
+        if key not in self._resize_tables:
+            ww, bounds, ks = resize.aa_coefficients(n_in, n_out)
+            if (bounds[:, 0] < 0).any() or (bounds[:, 0] + bounds[:, 1] > n_in).any() or (bounds[:, 1] > ks).any():
+                raise ValueError(f"aa_coefficients({n_in}, {n_out}): taps leave the input")
+            self._resize_tables[key] = (torch.from_numpy(ww).to(self.device), torch.from_numpy(bounds).to(self.device), ks)
+        return self._resize_tables[key]
+
+    def dino_patches(self, rgb_u8, out_h, out_w, patch, mean, std, out=None):
+        """u8 [n, H, W, 3] -> [n * (out_h / patch) * (out_w / patch), 3 patch^2] in the context's dtype: x / 255, torch's antialiased bilinear resize to
+        out_h x out_w in fp32, (x - mean) / std, patchify, cast (fie_dino_patches_u8_*: two launches).  `out`: the rows of a larger patch matrix to write."""
+        self.sync_stream()
+        n, h, w, c = rgb_u8.shape
+        if c != 3 or rgb_u8.dtype != torch.uint8 or not rgb_u8.is_contiguous():
+            raise ValueError(f"dino_patches: a contiguous u8 [n, H, W, 3] tensor, got {tuple(rgb_u8.shape)} {rgb_u8.dtype}")
+        rows, k = n * (out_h // max(patch, 1)) * (out_w // max(patch, 1)), 3 * patch * patch
+        if out is None:
+            out = self._alloc((rows, k))
+        elif tuple(out.shape) != (rows, k) or out.dtype != self.dtype or not out.is_contiguous():
+            raise ValueError(f"dino_patches: out must be a contiguous {self.dtype} {(rows, k)} tensor, got {tuple(out.shape)} {out.dtype}")
+        wx, bx, ksx = self._aa_tables(w, out_w)
+        wy, by, ksy = self._aa_tables(h, out_h)
+        tmp = self._alloc((n, h, out_w, 3), torch.float32)
+        fn = lib().fie_dino_patches_u8_f32 if self.f32 else lib().fie_dino_patches_u8_f16
+        _chk(fn(self.h, _p(rgb_u8), n, h, w, int(out_h), int(out_w), _p(wx), _p(bx), ksx, _p(wy), _p(by), ksy, int(patch), (_F * 3)(*mean), (_F * 3)(*std),
+                _p(tmp), _p(out)))
+        return out
+
+    def selfsim_mse(self, keys_a, keys_b, n, out=None):
+        """keys_a, keys_b: [n * T, C] key matrices of n pairs (the context's dtype, last dim contiguous, one row stride: a column range of a fused qkv
+        output) -> f64 [n] on the device: the mean over T x T of the squared difference of their cosine self-similarity matrices
+        (fie_selfsim_mse_*: three launches, no synchronisation)."""
+        self.sync_stream()
+        rows, c = keys_a.shape
+        t = rows // max(n, 1)
+        if (n <= 0 or rows != n * t or keys_b.shape != keys_a.shape or keys_a.dtype != self.dtype or keys_b.dtype != self.dtype or keys_a.stride(1) != 1
+                or keys_b.stride(1) != 1 or keys_a.stride(0) != keys_b.stride(0)):
+            raise ValueError(f"selfsim_mse: two [n * T, C] {self.dtype} tensors of one shape and row stride, got {tuple(keys_a.shape)} {keys_a.dtype} and "
+                             f"{tuple(keys_b.shape)} {keys_b.dtype} for n={n}")
+        nbytes = lib().fie_selfsim_workspace_bytes(n, t)
+        ws = self._alloc(((nbytes + 7) // 8,), torch.int64)
+        if out is None:
+            out = self._alloc((n,), torch.float64)
+        _chk((lib().fie_selfsim_mse_f32 if self.f32 else lib().fie_selfsim_mse_f16)(self.h, _p(keys_a), _p(keys_b), keys_a.stride(0), n, t, c, _p(ws), _p(out)))
         return out
 
     def canny_device(self, rgb_u8, low=100, high=200):

@@ -5,7 +5,8 @@ Follows Pillow `src/libImaging/Resample.c`: `precompute_coeffs` (support 3 x max
 zero).  The reference reaches it through `image.resize((1024, 1024), Image.LANCZOS)` (`src/pipeline.py:251`).  Pure Python / libm
 doubles, as Pillow's C: the tables -- and therefore the device result -- are bit-exact with Pillow (tests/test_cabi_cpu.py).
 `filter="bicubic"` is Pillow's `bicubic_filter` (a = -0.5, support 2): what `CLIPImageProcessor` resizes with; the
-kernels are the same, taps and bounds come from the tables.  `nearest_indices` restates the index table of Pillow's NEAREST resize."""
+kernels are the same, taps and bounds come from the tables.  `nearest_indices` restates the index table of Pillow's NEAREST resize.
+`aa_coefficients` restates the fp32 tables of torch's antialiased bilinear interpolation (host side of csrc/dino.hip)."""
 import math
 
 import numpy as np
@@ -96,4 +97,55 @@ def resample_numpy(rgb, out_h, out_w, filter="lanczos"):
         a = one_pass(a, w, out_w)
     if h != out_h:
         a = one_pass(a.transpose(1, 0, 2), h, out_h).transpose(1, 0, 2)
+    return np.ascontiguousarray(a)
+
+
+def aa_coefficients(in_size, out_size):
+    """Tables of torch's `interpolate(mode="bilinear", antialias=True, align_corners=False)` on a float tensor, one axis (ATen
+    UpSampleKernel.cpp: `_compute_indices_min_size_weights_aa` with the triangle filter, what torchvision's `Resize(antialias=True)` runs):
+    scale = in / out in fp32, support = max(scale, 1), centre = scale (i + 0.5), first index = int(centre - support + 0.5) clipped at 0, count up to
+    int(centre + support + 0.5) clipped at the input size, weight = max(1 - |(x - centre + 0.5) / max(scale, 1)|, 0), normalised per output pixel.
+    The weights are fp32 and fp32 divisions, as ATen's (its mixed float / double expressions are restated as written there).
+    -> (weights float32 [out_size, ksize], bounds int32 [out_size, 2] = (first input index, tap count), ksize).  Up-scaling (support 1, at most
+    three taps) and the identity size (taps {1, 0}: exact) come from the same formula."""
+    f32 = np.float32
+    scale = f32(in_size) / f32(out_size)
+    support = scale if scale >= 1.0 else f32(1.0)
+    invscale = f32(1.0) / scale if scale >= 1.0 else f32(1.0)
+    ksize = int(math.ceil(float(support))) * 2 + 1
+    ww = np.zeros((out_size, ksize), dtype=np.float32)
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    for i in range(out_size):
+        center = f32(float(scale) * (i + 0.5))
+        xmin = max(int(float(center) - float(support) + 0.5), 0)
+        xsize = min(max(min(int(float(center) + float(support) + 0.5), in_size) - xmin, 0), ksize)
+        total = f32(0.0)
+        for j in range(xsize):
+            x = abs(f32((float(f32(j + xmin) - center) + 0.5) * float(invscale)))
+            w = f32(1.0) - x if x < 1.0 else f32(0.0)
+            ww[i, j] = w
+            total = f32(total + w)
+        if total != 0.0:
+            ww[i, :xsize] = ww[i, :xsize] / total
+        bounds[i] = (xmin, xsize)
+    return ww, bounds, ksize
+
+
+def aa_resample_numpy(x, out_h, out_w):
+    """float32 [h, w, c] -> float32 [out_h, out_w, c] with the tables above: the horizontal pass first, each output the fp32 sum of its taps in
+    order (CPU checker of the tables; the product path is csrc/dino.hip)."""
+    a = np.asarray(x, dtype=np.float32)
+
+    def one_pass(img, out_len):                    # along axis 1
+        ww, bounds, _ = aa_coefficients(img.shape[1], out_len)
+        out = np.zeros((img.shape[0], out_len, img.shape[2]), dtype=np.float32)
+        for o in range(out_len):
+            x0, n = bounds[o]
+            for j in range(n):
+                t = img[:, x0 + j, :] * ww[o, j]
+                out[:, o, :] = t if j == 0 else out[:, o, :] + t
+        return out
+
+    a = one_pass(a, out_w)
+    a = one_pass(a.transpose(1, 0, 2), out_h).transpose(1, 0, 2)
     return np.ascontiguousarray(a)

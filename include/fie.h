@@ -594,6 +594,30 @@ int fie_vit_embed_f32(fie_ctx* ctx, const void* patches, const void* cls, const 
 int fie_clip_score_f16(fie_ctx* ctx, const void* img, int64_t ld_img, const void* txt, int64_t ld_txt, int n, int P, float* out);
 int fie_clip_score_f32(fie_ctx* ctx, const void* img, int64_t ld_img, const void* txt, int64_t ld_txt, int n, int P, float* out);
 
+/* ---- DINO structure distance on the device: the pieces around the ViT tower, which itself runs on fie_gemm_* / fie_layernorm_* /
+ * fie_attention_f16 and fie_vit_embed_*.  All asynchronous on the ctx stream, none synchronises, none uses atomics.
+ *   fie_dino_patches_u8_*    src: u8 [n, H, W, 3].  x / 255, then torch's `interpolate(mode="bilinear", antialias=True, align_corners=False)` to OH x OW
+ *                            in fp32 -- the horizontal pass first, into tmp (f32 [n, H, OW, 3], the caller's scratch), then the vertical one --, (x -
+ *                            mean[c]) / std[c] (3 HOST floats each) and the patch rows [n * (OH / patch) * (OW / patch), 3 patch^2] in the K order of
+ *                            fie_clip_patches_u8_*.  wx f32 [OW, ksx] / bx int32 [OW, 2] = (first input index, tap count) and wy / by / ksy likewise:
+ *                            DEVICE tables of the antialias triangle filter (fie_amd/resize.py: aa_coefficients); input indices are clamped to the image.
+ *                            patch % 8 == 0 and divides OH and OW; out 16-byte aligned.  f16: the round-to-nearest-even of the f32 value.  Two launches.
+ *   fie_selfsim_mse_*        keys_a, keys_b: [n, T, C] key matrices of n pairs, row stride ld elements (ld >= C: a column range of a fused qkv output),
+ *                            rows 16-byte aligned; C % 32 == 0 (f16) / C % 16 == 0 (f32).  out: double [n] = mean over the T x T entries of
+ *                            (S_b - S_a)^2, S = K K^T / max(|k_i| |k_j|, 1e-8) (the PRODUCT of the norms is clamped: a zero row gives S = 0).  Both Gram
+ *                            tiles of a 64 x 64 tile come from MFMA with fp32 accumulators and never reach memory; only tiles on and above the
+ *                            diagonal are computed, the latter counted twice.  Row norms: fp32, one wave per row.  workspace:
+ *                            fie_selfsim_workspace_bytes(n, T) bytes (-1 for shapes the op refuses), 8-byte aligned: one fp64 partial per tile, then the
+ *                            norms.  Three launches.  Deterministic: partials are added in tile order in fp64, so a pair's bits depend neither on n nor on
+ *                            its position, and an identical pair gives exactly 0. */
+int fie_dino_patches_u8_f16(fie_ctx* ctx, const uint8_t* src, int n, int H, int W, int OH, int OW, const float* wx, const int* bx, int ksx,
+                            const float* wy, const int* by, int ksy, int patch, const float* mean, const float* std, float* tmp, void* out);
+int fie_dino_patches_u8_f32(fie_ctx* ctx, const uint8_t* src, int n, int H, int W, int OH, int OW, const float* wx, const int* bx, int ksx,
+                            const float* wy, const int* by, int ksy, int patch, const float* mean, const float* std, float* tmp, void* out);
+int64_t fie_selfsim_workspace_bytes(int n, int T);
+int fie_selfsim_mse_f16(fie_ctx* ctx, const void* keys_a, const void* keys_b, int64_t ld, int n, int T, int C, void* workspace, double* out);
+int fie_selfsim_mse_f32(fie_ctx* ctx, const void* keys_a, const void* keys_b, int64_t ld, int n, int T, int C, void* workspace, double* out);
+
 #ifdef __cplusplus
 }
 #endif

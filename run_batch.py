@@ -6,7 +6,7 @@ shards the selected entries image-parallel over N GPUs (fie_amd.dist) and rank 0
     python run_batch.py --num_images 50 --editing_types 0 1 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run_batch.py --model ssd-1b
 
-Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir.
+Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir, --dino_dir.
 """
 import argparse
 import json
@@ -108,7 +108,16 @@ def add_clip_args(p):
     return p
 
 
-METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse", "clip_score", "clip_score_edited")
+def add_dino_args(p):
+    """[additive] DINO structure distance of every edit.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--dino_dir", type=str, default=None,
+                   help="[additive] with --metrics: a local transformers ViTModel directory (config.json, model.safetensors; facebook/dino-vitb8 is the "
+                        "reference's); adds dino_distance to every row (None for a source that is not square).  Default: FIE_DINO_DIR, else "
+                        "<weights_dir>/dino when it exists")
+    return p
+
+
+METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse", "clip_score", "clip_score_edited", "dino_distance")
 
 
 def select_entries(mapping, args, say=print):
@@ -281,7 +290,7 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
             import numpy as np
             print("\nMetrics of the edits (512x512, before JPEG encoding):")
             for k in METRIC_KEYS:
-                vals = [r[k] for r in tot.get("rows", []) if k in r]
+                vals = [r[k] for r in tot.get("rows", []) if r.get(k) is not None]
                 finite = [v for v in vals if np.isfinite(v)]          # an unchanged image has PSNR inf
                 if finite:
                     note = f"  ({len(vals) - len(finite)} infinite not counted)" if len(finite) < len(vals) else ""
@@ -300,7 +309,7 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    args = add_clip_args(add_metrics_args(add_resolution_args(add_mask_args(build_parser())))).parse_args(argv)
+    args = add_dino_args(add_clip_args(add_metrics_args(add_resolution_args(add_mask_args(build_parser()))))).parse_args(argv)
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets
@@ -329,8 +338,12 @@ def main(argv=None):
     mine = fdist.shard([(i, k, e) for i, (k, e) in enumerate(selected)], rank, world)
 
     say(f"\n[3/3] Initializing FastEditor ({model_suffix})...")
-    clip_dir = None
+    clip_dir = dino_dir = None
     if args.metrics:
+        from fie_amd import dino as hdino
+        dino_dir = hdino.resolve_dir(args.dino_dir)
+        if dino_dir is None and args.weights_dir and os.path.isdir(os.path.join(args.weights_dir, "dino")):
+            dino_dir = os.path.join(args.weights_dir, "dino")
         from fie_amd import clip_score as hclip
         clip_dir = hclip.resolve_dir(args.clip_score_dir)
         if clip_dir is None and args.weights_dir and os.path.isdir(os.path.join(args.weights_dir, "clip_score")):
@@ -343,7 +356,7 @@ def main(argv=None):
         editor = FastEditor(model_name=args.model, device="cuda" if world == 1 else f"cuda:{local % max(torch.cuda.device_count(), 1)}",
                             enable_cpu_offload=not args.no_cpu_offload, use_full_precision=args.full_precision,
                             use_full_controlnet=args.full_controlnet, weights_dir=args.weights_dir,
-                            clip_score_dir=clip_dir)
+                            clip_score_dir=clip_dir, dino_dir=dino_dir)
     if hasattr(editor, "pipe"):
         editor.pipe.set_progress_bar_config(disable=True)
     mem = editor.get_memory_usage()

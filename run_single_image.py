@@ -51,6 +51,9 @@ def build_parser():
     a("--clip_score_dir", type=str, default=None,
       help="[additive] with --compute_metrics: a local transformers CLIPModel directory (openai/clip-vit-base-patch16 is the reference's): fills the "
            "CLIP score.  Default: FIE_CLIP_SCORE_DIR, else <FIE_WEIGHTS_DIR>/clip_score when it exists")
+    a("--dino_dir", type=str, default=None,
+      help="[additive] with --compute_metrics: a local transformers ViTModel directory (facebook/dino-vitb8 is the reference's): fills the DINO "
+           "structure distance of a square pair.  Default: FIE_DINO_DIR, else <FIE_WEIGHTS_DIR>/dino when it exists")
     return p
 
 
@@ -131,11 +134,11 @@ def main(argv=None):
     if args.compute_metrics:
         print("\n[4/4] Computing metrics...")
         from src.metrics import MetricsCalculator
-        calc = MetricsCalculator(device="cuda", clip_dir=args.clip_score_dir)
+        calc = MetricsCalculator(device="cuda", clip_dir=args.clip_score_dir, dino_dir=args.dino_dir)
         metrics = calc.calculate_all_metrics(source_img=source_img, edited_img=edited_img, prompt=args.prompt)
         labels = [("ssim", "SSIM (structure preservation):  ", ".4f", ""), ("lpips", "LPIPS (perceptual distance):    ", ".4f", ""),
                   ("psnr", "PSNR (signal quality):          ", ".2f", " dB"), ("mse", "MSE (pixel difference):         ", ".6f", ""),
-                  ("clip_score", "CLIP Score (text alignment):    ", ".2f", "")]
+                  ("clip_score", "CLIP Score (text alignment):    ", ".2f", ""), ("dino_distance", "DINO distance (structure):      ", ".6f", "")]
         fmt = lambda k, f: "unavailable offline" if metrics.get(k) is None else format(metrics[k], f)
         print("\n      Metrics:")
         for k, label, f, unit in labels:

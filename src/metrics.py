@@ -3,8 +3,9 @@
 Evaluation only (not part of the denoising hot path): plain torch ops, as the reference's
 torchmetrics are.  Restated here: SSIM (torchmetrics defaults: 11x11 Gaussian, sigma 1.5, k1/k2 0.01/0.03,
 data_range 1), PSNR and MSE, all on 512x512 LANCZOS-resized RGB in [0,1] (reference :227-239, :291-347).
-LPIPS(squeeze) and the DINO ViT-B/8 distance need checkpoints that only exist on the hub (reference :28, :179-186); offline they
-return None rather than a made-up number.  CLIPScore(ViT-B/16) (reference :184-186, :271-289) runs on the device when a local
+LPIPS(squeeze) needs a checkpoint that only exists on the hub (reference :179-183); offline it returns None rather than a made-up number.
+The DINO ViT-B/8 structure distance (reference :24-147) runs on the device when a local transformers `ViTModel` directory is given
+(`dino_dir=`, else FIE_DINO_DIR, else <FIE_WEIGHTS_DIR>/dino): fie_amd/dino.py; without one, and on the CPU, it returns None.  CLIPScore(ViT-B/16) (reference :184-186, :271-289) runs on the device when a local
 `CLIPModel` directory is given (`clip_dir=`, else FIE_CLIP_SCORE_DIR, else <FIE_WEIGHTS_DIR>/clip_score): fie_amd/clip_score.py,
 DESIGN.md section 11; without one, and on the CPU, it returns None as well.
 
@@ -21,6 +22,7 @@ from PIL import Image
 
 import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory)
 from fie_amd import clip_score as hclip
+from fie_amd import dino as hdino
 from fie_amd import mask as hmask
 from fie_amd import metrics as hmetrics
 
@@ -28,7 +30,7 @@ TARGET = hmetrics.TARGET
 
 
 class MetricsCalculator:
-    def __init__(self, device="cuda", clip_dir=None):
+    def __init__(self, device="cuda", clip_dir=None, dino_dir=None, dino_layer=hdino.DEFAULT_LAYER):
         self.device = device
         print(f"[MetricsCalculator] Initializing on {device}...")
         d = torch.arange(-5.0, 6.0)
@@ -45,7 +47,13 @@ class MetricsCalculator:
         if clip_dir:
             print(f"[MetricsCalculator] Loading the CLIP score model from {clip_dir}")
             self._clip = hclip.load(clip_dir, self._ctx)
-        print("[MetricsCalculator] Initialization complete! (LPIPS / DINO: unavailable offline" + ("" if self._clip else "; CLIP score: no model directory") + ")")
+        self._dino = None                               # fie_amd.dino.DinoScorer: only on a GPU and only from a local ViTModel directory
+        dino_dir = hdino.resolve_dir(dino_dir) if self._ctx is not None else None
+        if dino_dir:
+            print(f"[MetricsCalculator] Loading the DINO structure distance model from {dino_dir}")
+            self._dino = hdino.load(dino_dir, self._ctx, layer=dino_layer)
+        print("[MetricsCalculator] Initialization complete! (LPIPS: unavailable offline" + ("" if self._clip else "; CLIP score: no model directory")
+              + ("" if self._dino else "; DINO distance: no model directory") + ")")
 
     def _pil_to_tensor(self, img):
         a = np.array(img).astype(np.float32) / 255.0
@@ -180,18 +188,65 @@ class MetricsCalculator:
             out[i]["clip_score_edited" if masked else "clip_score"] = float(row[0 if unclamped else 1])
         return out
 
+    def calculate_dino_distance(self, source_img, edited_img):
+        """The reference's DinoDistanceMetric.calculate_distance (MSE between the self-similarity matrices of the layer-11 keys), or None without a
+        model directory / on the CPU.  Both images must be square (ValueError naming the sizes otherwise)."""
+        if self._dino is None or source_img is None or edited_img is None:
+            return None
+        return self.calculate_dino_distances([source_img], [edited_img])[0]
+
+    def calculate_dino_distances(self, sources, editeds):
+        """[additive] The structure distance of every (source, edited) pair of two lists of PIL images: one upload per image, one batched pass of the
+        tower per (source size, edited size), one synchronisation.  Without a model directory every entry is None."""
+        if len(sources) != len(editeds):
+            raise ValueError("sources and editeds must be lists of one length")
+        if self._dino is None:
+            return [None] * len(sources)
+        if not sources:
+            return []
+        dino, ctx = self._dino, self._ctx
+        rgb = lambda im: np.ascontiguousarray(np.array(im.convert("RGB") if im.mode != "RGB" else im))
+        for im in list(sources) + list(editeds):
+            dino.check_size(im.size[1], im.size[0])
+        with torch.cuda.device(ctx.device):
+            a = [torch.from_numpy(rgb(im)).to(ctx.device) for im in sources]
+            b = [torch.from_numpy(rgb(im)).to(ctx.device) for im in editeds]
+            groups = {}
+            for i in range(len(a)):
+                groups.setdefault((tuple(a[i].shape[:2]), tuple(b[i].shape[:2])), []).append(i)
+            rows = torch.empty(len(a), device=ctx.device, dtype=torch.float64)
+            r0, order = 0, []
+            for idx in groups.values():
+                dino.distances([a[i] for i in idx], [b[i] for i in idx], out=rows[r0:r0 + len(idx)])
+                r0 += len(idx)
+                order += idx
+            host = rows.cpu().numpy()
+        out = [None] * len(a)
+        for i, v in zip(order, host):
+            out[i] = float(v)
+        return out
+
+    def _dino_or_none(self, source_img, edited_img):
+        """calculate_dino_distance, with None for a pair the tower cannot take (not square) -- as a column of a table wants it."""
+        if self._dino is None or source_img is None or edited_img is None:
+            return None
+        if not (hdino.supported_size(source_img.size[1], source_img.size[0]) and hdino.supported_size(edited_img.size[1], edited_img.size[0])):
+            return None
+        return self.calculate_dino_distance(source_img, edited_img)
+
     def calculate_all_metrics(self, source_img, edited_img, prompt, mask=None):
         m = self.calculate_pairs([source_img], [edited_img], None if mask is None else [mask])[0]
         return self.with_unavailable(m, source_img, edited_img, prompt, mask=mask)
 
     def with_unavailable(self, m, source_img=None, edited_img=None, prompt="", mask=None):
         """A calculate_pairs() dict in calculate_all_metrics()'s key order, with the metrics that need hub checkpoints as None.  `clip_score`
-        is filled when the calculator has a CLIP model (and `clip_score_edited`, behind the bg_* keys, when a mask comes with it)."""
+        is filled when the calculator has a CLIP model (and `clip_score_edited`, behind the bg_* keys, when a mask comes with it),
+        `dino_distance` when it has a DINO model and both images are square."""
         clip = {"clip_score": None}
         if self._clip is not None and edited_img is not None:
             clip = self.calculate_clip_scores([edited_img], [prompt], None if mask is None else [mask])[0]
         out = {"ssim": m["ssim"], "lpips": self.calculate_lpips(source_img, edited_img), "clip_score": clip["clip_score"],
-               "psnr": m["psnr"], "mse": m["mse"], "dino_distance": None}
+               "psnr": m["psnr"], "mse": m["mse"], "dino_distance": self._dino_or_none(source_img, edited_img)}
         out.update({k: m[k] for k in hmetrics.BG_KEYS if k in m})
         if "clip_score_edited" in clip:
             out["clip_score_edited"] = clip["clip_score_edited"]

@@ -5,7 +5,8 @@ signatures, defaults, attributes and error behaviour; `self.pipe` is an `fie_amd
 (hand-written HIP kernels behind a C ABI) instead of the diffusers pipeline.  There is no CPU fallback: a missing
 HIP library or GPU raises.  Additive: `set_in_flight(n)` / `worker_slot(i)` (several edits in flight from worker threads), and keyword-only knobs: `weights_dir`, `seed_weights`, `noise_dtype`, `weight_dtype` ("f8e4m3": fp8 UNet / ControlNet weights, BASELINE config 5), `broadcast_weights`
 (under torch.distributed with world_size > 1, rank 0's synthetic weights are broadcast over RCCL instead of regenerated), `clip_score_dir` (a local
-transformers CLIPModel directory: `edit(..., metrics=True)` then also returns the CLIP score of the edit).
+transformers CLIPModel directory: `edit(..., metrics=True)` then also returns the CLIP score of the edit), `dino_dir` (a local
+transformers ViTModel directory: `edit(..., metrics=True)` then also returns the DINO structure distance of the edit).
 """
 import os
 import threading
@@ -43,7 +44,7 @@ class FastEditor:
 
     def __init__(self, model_name="sdxl", device="cuda", dtype=torch.float16, enable_cpu_offload=True,
                  use_full_precision=False, use_full_controlnet=False, *, weights_dir=None, seed_weights=1234,
-                 noise_dtype=None, broadcast_weights=True, weight_dtype="f16", clip_score_dir=None):
+                 noise_dtype=None, broadcast_weights=True, weight_dtype="f16", clip_score_dir=None, dino_dir=None, dino_layer=11):
         if model_name not in self.MODEL_CONFIGS and model_name not in self._EXTRA_STACKS:
             raise ValueError(f"Unknown model: {model_name}. Choose from {list(self.MODEL_CONFIGS.keys())}")
         self.model_name = model_name
@@ -107,6 +108,12 @@ class FastEditor:
             from fie_amd import clip_score as hclip
             log(f"Loading the CLIP score model from {clip_score_dir}")
             self.clip_scorer = hclip.load(clip_score_dir, ctx)
+        self.dino_scorer = None                # fie_amd.dino.DinoScorer: only from a directory, never a made-up number
+        self._dino_rows = {}                   # (slot, rows) -> pinned f64 [rows]: where an edit's structure distances land
+        if dino_dir:
+            from fie_amd import dino as hdino
+            log(f"Loading the DINO structure distance model from {dino_dir}")
+            self.dino_scorer = hdino.load(dino_dir, ctx, layer=dino_layer)
         del sds
         log("Enabling memory optimizations...")
         # 288 GB of HBM: offload / slicing flags are accepted and ignored (reference toggles them at :165-179)
@@ -165,7 +172,8 @@ class FastEditor:
         scored on the device behind the edit: the pair is the ORIGINAL source and the u8 result, each LANCZOS-resized to 512x512 -- what
         evaluate.py would score had the result been saved losslessly.  No additional host wait.  With
         `FastEditor(clip_score_dir=...)` the dict also holds `clip_score` (the result against `prompt`) and, with a mask,
-        `clip_score_edited` (the result zeroed outside the edited region)."""
+        `clip_score_edited` (the result zeroed outside the edited region).  With `FastEditor(dino_dir=...)` the dict also holds `dino_distance`: the
+        structure distance between the ORIGINAL source and the result; None when the source or the result is not square."""
         size = buckets.target_size(resolution, image.size)
         hmask.check_args(mask_blur, paste_back, mask is not None)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
@@ -199,7 +207,9 @@ class FastEditor:
         512x512 (sources, results, masks), ONE fie_metrics_pairs_u8 launch pair for all images of the job and the copy of the 32-byte result
         rows into pinned host memory of the slot.  The edit's own final synchronisation (the image's D2H) completes them.  With a CLIP model
         (`clip_scorer`) the hook also queues the CLIP score of every result against its prompt (cached text embedding, one batched pass of the
-        image tower, the masked variants in the same pass) and returns (metric rows, CLIP rows, which (image, masked) each CLIP row is)."""
+        image tower, the masked variants in the same pass) and returns (metric rows, CLIP rows, which (image, masked) each CLIP row is).  With a DINO
+        model (`dino_scorer`) it queues, behind those, the structure distance of every (original source, result) pair of square images -- one batched
+        pass of the tower per (source size, result size) -- and the tuple grows by (distance rows, which image each row is)."""
         ctx = self.pipe.ctx
         th, tw = hmetrics.TARGET[1], hmetrics.TARGET[0]
         to512 = lambda t: t if tuple(t.shape[:2]) == (th, tw) else ctx.resize_lanczos(t.contiguous(), th, tw)
@@ -219,8 +229,10 @@ class FastEditor:
             if host is None:
                 host = self._metric_rows[(slot, len(outs))] = torch.empty((len(outs), 4), dtype=torch.int64).pin_memory()
             host.copy_(rows, non_blocking=True)
-            if self.clip_scorer is None:
+            if self.clip_scorer is None and self.dino_scorer is None:
                 return host
+            if self.clip_scorer is None:
+                return (host, None, ()) + self._dino_queue(slot, origs, outs)
             clip = self.clip_scorer
             items = [(i, False) for i in range(len(outs))] + [(i, True) for i, m in enumerate(omasks) if m is not None]
             with self.pipe.eager_lock:
@@ -231,14 +243,45 @@ class FastEditor:
             if chost is None:
                 chost = self._clip_rows[(slot, len(items))] = torch.empty((len(items), 2), dtype=torch.float32).pin_memory()
             chost.copy_(crow, non_blocking=True)
+            if self.dino_scorer is not None:
+                return (host, chost, items) + self._dino_queue(slot, origs, outs)
             return host, chost, items
         return score
 
+    def _dino_queue(self, slot, origs, outs):
+        """Queues the structure distances of the square (original, result) pairs on the current stream and the copy of their 8 bytes each into pinned
+        host memory of the slot.  -> (f64 rows on the host or None, the image index of every row)."""
+        from fie_amd import dino as hdino
+        groups = {}
+        for i, (a, b) in enumerate(zip(origs, outs)):
+            if hdino.supported_size(*a.shape[:2]) and hdino.supported_size(*b.shape[:2]):
+                groups.setdefault((tuple(a.shape[:2]), tuple(b.shape[:2])), []).append(i)
+        order = [i for g in groups.values() for i in g]
+        if not order:
+            return None, ()
+        ctx = self.pipe.ctx
+        rows = torch.empty(len(order), device=ctx.device, dtype=torch.float64)
+        r0 = 0
+        with self.pipe.eager_lock:
+            for g in groups.values():
+                self.dino_scorer.distances([origs[i] for i in g], [outs[i] for i in g], out=rows[r0:r0 + len(g)])
+                r0 += len(g)
+        dhost = self._dino_rows.get((slot, len(order)))
+        if dhost is None:
+            dhost = self._dino_rows[(slot, len(order))] = torch.empty(len(order), dtype=torch.float64).pin_memory()
+        dhost.copy_(rows, non_blocking=True)
+        return dhost, tuple(order)
+
     def _scores(self, extra, has_mask):
-        host_rows, clip_rows, items = extra if isinstance(extra, tuple) else (extra, None, ())
+        host_rows, clip_rows, items, dino_rows, dino_items = (tuple(extra) + (None, ()))[:5] if isinstance(extra, tuple) else (extra, None, (), None, ())
         out = hmetrics.rows_to_dicts(host_rows.numpy().copy(), hmetrics.TARGET[1], hmetrics.TARGET[0], has_mask)
         for (i, masked), row in zip(items, clip_rows.numpy().copy() if clip_rows is not None else ()):
             out[i]["clip_score_edited" if masked else "clip_score"] = float(row[1])
+        if self.dino_scorer is not None:
+            for m in out:
+                m["dino_distance"] = None
+            for i, v in zip(dino_items, dino_rows.numpy().copy() if dino_rows is not None else ()):
+                out[i]["dino_distance"] = float(v)
         return out
 
     def _mask_device(self, mask_l, size, original=None):
