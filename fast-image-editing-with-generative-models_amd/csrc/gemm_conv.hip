@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "gemm_common.h"
+#include "gemm_tiles.h"
 
 using namespace fie_gemm;
 
@@ -595,85 +596,177 @@ __global__ __launch_bounds__(NW * 64) void gemm3_kernel(GemmArgs p) {
     }
 }
 
-template <int BM, int BN, int ST, int NW>
-constexpr int ring_lds() { return ST * (BM + BN) * BK * (int)sizeof(half_t); }
+// ---- the launch table: ONE row per tile code (also the values fie_debug_force_tile / fie_debug_tile_override take; + 1000 / + 2000 force the tile
+// order, n-tiles / m-tiles fastest, plain codes estimate it).  Everything the host knows about a code is in its row; a new tile is one row here
+// (and, for an fp8 kernel, one entry in gemm_tiles.h).
+enum Family { kGeneric, kRing, kPhased, kHalo, kHaloEdge, kThin };      // kGeneric and kThin serve shapes the LDS-DMA kernels cannot address (no dma_ok needed)
+// flags: may split K (ring kernels with <= 16 accumulator fragments per lane, no stamps); writes cycle stamps (fie_debug_gemm_stamps: slower, for
+// tools/kstep_stamps.py only; on a ring row also the kernel's STAMP); no conv-view build; has an LN-folded build (LEAN == 2); ring rows: the kernel's PF / ALT
+enum : unsigned { kSplitK = 1, kStamps = 2, kGemmOnly = 4, kLnFold = 8, kPF = 16, kAlt = 32 };
+using LaunchFn = int (*)(fie_ctx*, GemmArgs&, dim3 grid);
+struct Tile {
+    int code, bm, bn;
+    Family family;
+    const char* name;               // the kernel family as fie_debug_last_gemm_kernel prints it
+    unsigned flags;
+    int w8, x8;                     // the code that runs in its place with fp8 weights (gemm_w8.hip) / fp8 activations x weights (gemm_x8.hip); 0 = none
+    LaunchFn gemm, conv, ln;        // launch in the GEMM view / the conv view / with LayerNorm folded in; null where not built
+    hipError_t (*attr)();           // sets the dynamic-LDS attribute of every kernel the row launches; null for the families with an init of their own
+};
 
-// tiles with <= 16 accumulator fragments per lane have a LEAN instantiation for the GEMM view (gemm_common.h: epilogue_lean)
-template <int BM, int BN, int MODE, int NW, bool STAMP>
-constexpr bool has_lean() { return MODE == 0 && !STAMP && BM * BN / (NW * 64) <= 64; }
-
-template <int BM, int BN, int ST, int MODE, int NW, bool PF = false, bool STAMP = false, bool ALT = false>
-hipError_t ring_attr() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm3_kernel<BM, BN, ST, MODE, NW, PF, STAMP, ALT, 0>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, ring_lds<BM, BN, ST, NW>());
-    if constexpr (has_lean<BM, BN, MODE, NW, STAMP>()) {
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm3_kernel<BM, BN, ST, MODE, NW, PF, STAMP, ALT, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, ring_lds<BM, BN, ST, NW>());
-    }
-    return e;
-}
-
-template <int BM, int BN, int ST, int MODE, int NW, bool PF = false, bool STAMP = false, bool ALT = false>
-void launch_ring(fie_ctx* ctx, const GemmArgs& a, dim3 grid) {
-    constexpr int lds = ring_lds<BM, BN, ST, NW>();
-    if constexpr (has_lean<BM, BN, MODE, NW, STAMP>()) {
-        // a plain Linear (optional bias, optional residual, f16 out): the kernel with the lean epilogue
-        if (a.epi_prefetch && a.splitk <= 1 && !a.rowbias && a.act == FIE_ACT_NONE && a.scale == 1.f && !a.gn_partial && !a.out_f8 && !a.w_scale && !a.oscat &&
-            a.probe == 0) {
-            fie_launch(ctx, (gemm3_kernel<BM, BN, ST, MODE, NW, PF, STAMP, ALT, 1>), grid, dim3(NW * 64), lds, a);
-            return;
+// A ring tile: the template arguments of gemm3_kernel are named HERE and nowhere else, so the launches, the lean / non-lean pair, the LN build and
+// the attribute setter of a row cannot disagree
+template <int BM, int BN, int ST, int NW, unsigned F = 0>
+struct RingTile {
+    static constexpr bool PF = F & kPF, STAMP = F & kStamps, ALT = F & kAlt;
+    static constexpr int lds = ST * (BM + BN) * BK * (int)sizeof(half_t);
+    // tiles with <= 16 accumulator fragments per lane have a LEAN instantiation for the GEMM view (gemm_common.h: epilogue_lean)
+    template <int MODE>
+    static constexpr bool has_lean = MODE == 0 && !STAMP && BM * BN / (NW * 64) <= 64;
+    static_assert(!((F & kLnFold) && STAMP) && !((F & kSplitK) && (STAMP || BM * BN / (NW * 64) > 64)), "no LN fold or split-K with stamps; split-K on <= 16 fragments per lane");
+    template <int MODE, int LEAN>
+    static constexpr auto kernel() { return &gemm3_kernel<BM, BN, ST, MODE, NW, PF, STAMP, ALT, LEAN>; }
+    // LN: LayerNorm folded into the GEMM (GemmArgs::ln_tab, LEAN == 2), built for the tiles the transformer blocks' LN consumers run on
+    template <int MODE, bool LN = false>
+    static int launch(fie_ctx* ctx, GemmArgs& a, dim3 grid) {
+        auto k = kernel<MODE, LN ? 2 : 0>();
+        if constexpr (!LN && has_lean<MODE>) {
+            // a plain Linear (optional bias, optional residual, f16 out): the kernel with the lean epilogue
+            if (a.epi_prefetch && a.splitk <= 1 && !a.rowbias && a.act == FIE_ACT_NONE && a.scale == 1.f && !a.gn_partial && !a.out_f8 && !a.w_scale && !a.oscat &&
+                a.probe == 0)
+                k = kernel<MODE, 1>();
         }
+        fie_launch(ctx, k, grid, dim3(NW * 64), lds, a);
+        FIE_LAUNCH_CHECK();
+        return FIE_OK;
     }
-    fie_launch(ctx, (gemm3_kernel<BM, BN, ST, MODE, NW, PF, STAMP, ALT, 0>), grid, dim3(NW * 64), lds, a);
-}
+    static hipError_t attr() {
+        hipError_t e = hipSuccess;
+        auto set = [&](auto* k) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds); };
+        set(kernel<0, 0>());
+        if constexpr (has_lean<0>) set(kernel<0, 1>());
+        if constexpr (!(F & kGemmOnly)) set(kernel<2, 0>());
+        if constexpr (F & kLnFold) set(kernel<0, 2>());
+        return e;
+    }
+    static constexpr Tile row(int code, const char* name, int w8, int x8) {
+        Tile t = {code, BM, BN, kRing, name, F, w8, x8, &launch<0>, nullptr, nullptr, &attr};
+        if constexpr (!(F & kGemmOnly)) t.conv = &launch<2>;
+        if constexpr (F & kLnFold) t.ln = &launch<0, true>;
+        return t;
+    }
+};
 
-// LayerNorm folded into the GEMM (GemmArgs::ln_tab, LEAN == 2): built for the four tiles the transformer blocks' LN consumers run on
-template <int BM, int BN, int ST, int NW, bool PF = false, bool ALT = false>
-void launch_ring_ln(fie_ctx* ctx, const GemmArgs& a, dim3 grid) {
-    fie_launch(ctx, (gemm3_kernel<BM, BN, ST, 0, NW, PF, false, ALT, 2>), grid, dim3(NW * 64), (ring_lds<BM, BN, ST, NW>()), a);
+template <int BM, int BN, int MODE>
+int launch_generic(fie_ctx* ctx, GemmArgs& a, dim3 grid) {
+    fie_launch(ctx, (gemm_kernel<BM, BN, MODE>), grid, dim3(256), 0, a);
+    FIE_LAUNCH_CHECK();
+    return FIE_OK;
 }
-template <int BM, int BN, int ST, int NW, bool PF = false, bool ALT = false>
-hipError_t ring_attr_ln() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm3_kernel<BM, BN, ST, 0, NW, PF, false, ALT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               ring_lds<BM, BN, ST, NW>());
-}
-// (128x80, tile 48, was built too and is NOT offered: its instantiation returned wrong values in 16-row x 1-column spots on a loaded chip, in every form
-// tried, while 42 / 96 / 64 never did: profiles/r04_ln_fold_tile48_anomaly.md; tests/test_ops_gpu.py screens the three that ship)
-constexpr bool is_ln_code(int code) { return code == 42 || code == 96 || code == 64; }
+template <int BM, int BN>
+constexpr Tile generic_row(int code, int w8, int x8) { return {code, BM, BN, kGeneric, "gemm_kernel", 0, w8, x8, &launch_generic<BM, BN, 0>, &launch_generic<BM, BN, 1>}; }
+// the families with launchers (and attribute setters) of their own: gemm8.hip, conv_halo.hip (by variant number), conv_thin.hip
+template <int CONV, int VARIANT>
+int launch_phased(fie_ctx* ctx, GemmArgs& a, dim3) { return fie_launch_gemm8(ctx, a, CONV, VARIANT); }
+template <int VARIANT>
+int launch_halo(fie_ctx* ctx, GemmArgs& a, dim3) { return fie_launch_conv_halo(ctx, a, VARIANT); }
+int launch_thin(fie_ctx* ctx, GemmArgs& a, dim3) { return fie_launch_conv_thin(ctx, a); }
 
-// ---- tile codes (also the values fie_debug_force_tile / fie_debug_tile_override take)
-//   1 / 2 / 3      gemm_kernel   128x128 / 128x64 / 64x64 (any shape)
-//   42 / 43        gemm3_kernel  128x64 / 64x64, 3 stages, 4 waves (two / three blocks per CU)
-//   44 / 46        the same tiles with 2 stages (three / five blocks per CU)
-//   52 / 54        gemm3_kernel  128x128 / 192x128, 2 stages, 8 waves: two blocks per CU
-//   47             gemm3_kernel  128x96, 3 stages, 4 waves: 224 tiles for M 2048 x N 1280 (one per CU, each streaming a 96-row weight tile:
-//                  the 32x32-latent convs lose nothing on cold weights with it, 7-9 % with 128x128)
-//   48             gemm3_kernel  128x80, 3 stages, 4 waves stacked along the rows (wave tile 32x80); M 2048 x N 1280 = 256 tiles, one per CU
-//   51             gemm3_kernel  128x128, 3 stages, 8 waves
-//   61 / 62        gemm3_kernel  256x256 x 2 stages / 256x128 x 3 stages, 8 waves
-//   63             gemm3_kernel  256x320 x 2 stages, 8 waves (wave tile 128x80): exactly ONE tile per CU for the FF1 projection M 2048 x N 10240
-//                  (256 tiles) and two rounds for M 8192 x N 5120; 142 FLOP per staged byte pair against 85 for 256x128
-//   64             63 with the two wave groups taking turns at a K-step's LDS-DMA refill (ALT above): FF1 56.5 us against 59.5-63.4 (the same idea on
-//                  256x128 x 3 stages was 3 % SLOWER than 62 and is not built: the barrier still paces both groups by the slower one)
-//   + 1000 / + 2000  force the tile order (n-tiles / m-tiles fastest); plain codes estimate it
-//   95 / 96        gemm3_kernel 51 / 62 with fragment reads one half K-step ahead of the MFMAs (the 4-wave and 2-stage tiles gain nothing from it)
-//   97 / 98 / 94   62 / 96 / 42 with in-kernel cycle stamps (fie_debug_gemm_stamps; slower, for tools/kstep_stamps.py only)
-//   81 / 82        gemm8_kernel  256x256 phased (82: second DMA piece of each phase inside the MFMA cluster, A/B: slower)
-//   71 / 73        conv_halo_kernel (conv_halo.hip): a 16x16 output patch x 128 channels per block, the patch's 18x18 halo resident in LDS per
-//                  64-channel chunk, weights through a ring; stride-1 same-size convs with H, W % 16 == 0 only (73: with cycle stamps).
-//                  K is summed chunk-major (the im2col kernels: tap-major): equal to the other codes to rounding, not bit for bit
-//   72 / 74 / 76   conv_halo2_kernel: the same K loop in persistent blocks that prefetch their next tile and defer a tile's stores into the next
-//                  tile's first chunk (74: with cycle stamps, 76: the 8-byte-store form, A/B); THE RULE for eligible convs (heuristic_code)
-//   78             conv_halo2_kernel with edge patches: maps whose height or width is not a multiple of 16 (the aspect-ratio buckets); the patch grid
-//                  is rounded up, stores of pixels outside the image are dropped per lane; no GroupNorm sums.  The rule for eligible convs, under 72's
-//                  threshold.  Sums chunk-major like 71-76
-struct TileDim { int code, bm, bn; };
-constexpr TileDim kTiles[] = {{1, 128, 128}, {2, 128, 64}, {3, 64, 64}, {42, 128, 64}, {43, 64, 64},
-                              {51, 128, 128}, {61, 256, 256}, {62, 256, 128}, {81, 256, 256}, {82, 256, 256},
-                              {63, 256, 320}, {95, 128, 128}, {96, 256, 128}, {97, 256, 128}, {98, 256, 128}, {94, 128, 64},
-                              {52, 128, 128}, {47, 128, 96}, {54, 192, 128}, {46, 64, 64}, {44, 128, 64}, {48, 128, 80}, {64, 256, 320},
-                              {71, 256, 128}, {73, 256, 128}, {72, 256, 128}, {74, 256, 128}, {76, 256, 128}, {77, 64, 16}, {78, 256, 128}};
+// Columns: code, bm, bn, family, name, flags, w8, x8, gemm, conv (ln, attr: ring rows only).  With fp8 WEIGHTS every code runs on one of the five W8 tiles
+// (its own shape where that is built, 256x128 otherwise; the halo rows never get there: their eligibility test refuses fp8 weights first); with fp8
+// ACTIVATIONS a code without a stand-in is refused.
+constexpr Tile kTiles[] = {
+    generic_row<128, 128>(1, 62, 43),      // gemm_kernel: any shape
+    generic_row<128, 64>(2, 42, 42),
+    generic_row<64, 64>(3, 43, 43),
+    RingTile<128, 64, 3, 4, kSplitK | kLnFold>::row(42, "gemm3_kernel", 42, 42),      // 128x64 / 64x64, 3 stages, 4 waves (two / three blocks per CU)
+    RingTile<64, 64, 3, 4, kSplitK>::row(43, "gemm3_kernel", 43, 43),
+    RingTile<128, 64, 2, 4, kSplitK>::row(44, "gemm3_kernel", 42, 42),                // the same tiles with 2 stages (three / five blocks per CU)
+    RingTile<64, 64, 2, 4, kSplitK>::row(46, "gemm3_kernel", 43, 43),
+    // 128x96, 3 stages, 4 waves: 224 tiles for M 2048 x N 1280 (one per CU, each streaming a 96-row weight tile: the 32x32-latent convs lose nothing
+    // on cold weights with it, 7-9 % with 128x128)
+    RingTile<128, 96, 3, 4, kSplitK>::row(47, "gemm3_kernel", 62, 47),
+    // 128x80, 3 stages, 4 waves stacked along the rows (wave tile 32x80); M 2048 x N 1280 = 256 tiles, one per CU.  Weight rows past the packed matrix
+    // (80 does not divide Npad) read as zero through the descriptor.  (Its LN-folded build returned wrong values in 16-row x 1-column spots on a loaded
+    // chip, in every form tried, while 42 / 96 / 64 never did, and is NOT built: profiles/r04_ln_fold_tile48_anomaly.md; tests/test_ops_gpu.py screens the three that ship)
+    RingTile<128, 80, 3, 4, kSplitK>::row(48, "gemm3_kernel", 62, 0),
+    RingTile<128, 128, 3, 8, kSplitK>::row(51, "gemm3_kernel", 62, 51),               // 128x128, 3 stages, 8 waves
+    RingTile<128, 128, 2, 8, kSplitK>::row(52, "gemm3_kernel", 52, 52),               // 128x128 / 192x128, 2 stages, 8 waves: two blocks per CU
+    RingTile<192, 128, 2, 8, kSplitK>::row(54, "gemm3_kernel", 54, 54),
+    RingTile<256, 256, 2, 8>::row(61, "gemm3_kernel", 62, 62),                        // 256x256 x 2 stages / 256x128 x 3 stages, 8 waves
+    RingTile<256, 128, 3, 8, kSplitK>::row(62, "gemm3_kernel", 62, 62),
+    // 256x320 x 2 stages, 8 waves (wave tile 128x80): exactly ONE tile per CU for the FF1 projection M 2048 x N 10240 (256 tiles) and two rounds for
+    // M 8192 x N 5120; 142 FLOP per staged byte pair against 85 for 256x128
+    RingTile<256, 320, 2, 8, kGemmOnly>::row(63, "gemm3_kernel", 62, 63),
+    // 63 with the two wave groups taking turns at a K-step's LDS-DMA refill (ALT above): FF1 56.5 us against 59.5-63.4 (the same idea on 256x128 x 3
+    // stages was 3 % SLOWER than 62 and is not built: the barrier still paces both groups by the slower one).  No alternating-refill form of the fp8 kernels
+    RingTile<256, 320, 2, 8, kGemmOnly | kAlt | kLnFold>::row(64, "gemm3_kernel", 62, 63),
+    // 51 / 62 with fragment reads one half K-step ahead of the MFMAs (the 4-wave and 2-stage tiles gain nothing from it)
+    RingTile<128, 128, 3, 8, kPF | kSplitK>::row(95, "gemm3_kernel+prefetch", 62, 51),
+    RingTile<256, 128, 3, 8, kPF | kSplitK | kLnFold>::row(96, "gemm3_kernel+prefetch", 62, 62),
+    // 62 / 96 / 42 with in-kernel cycle stamps.  97 and 94 do NOT prefetch: their printed name is a misnomer of the old `code >= 90` rule that tests,
+    // tools and bench.py parse; fixing it is a change of its own
+    RingTile<256, 128, 3, 8, kStamps>::row(97, "gemm3_kernel+prefetch", 62, 0),
+    RingTile<256, 128, 3, 8, kPF | kStamps>::row(98, "gemm3_kernel+prefetch", 62, 0),
+    RingTile<128, 64, 3, 4, kStamps>::row(94, "gemm3_kernel+prefetch", 62, 0),
+    {81, 256, 256, kPhased, "gemm8_kernel", 0, 62, 62, &launch_phased<0, 0>, &launch_phased<1, 0>},      // gemm8.hip: 256x256 phased
+    {82, 256, 256, kPhased, "gemm8_kernel", 0, 62, 0, &launch_phased<0, 1>, &launch_phased<1, 1>},       // A/B: second DMA piece of each phase inside the MFMA cluster (measured slower)
+    // conv_halo.hip: a 16x16 output patch x 128 channels per block, the patch's 18x18 halo resident in LDS per 64-channel chunk, weights through a ring;
+    // stride-1 same-size convs with H, W % 16 == 0 only (73: with cycle stamps).  K is summed chunk-major (the im2col kernels: tap-major): equal to the
+    // other codes to rounding, not bit for bit
+    {71, 256, 128, kHalo, "conv_halo_kernel", 0, 62, 0, nullptr, &launch_halo<0>},
+    {73, 256, 128, kHalo, "conv_halo_kernel", kStamps, 62, 0, nullptr, &launch_halo<1>},
+    // the same K loop in persistent blocks that prefetch their next tile and defer a tile's stores into the next tile's first chunk (74: with cycle
+    // stamps, 76: the 8-byte-store form, A/B); 72 is THE RULE for eligible convs (heuristic_code)
+    {72, 256, 128, kHalo, "conv_halo2_kernel", 0, 62, 0, nullptr, &launch_halo<2>},
+    {74, 256, 128, kHalo, "conv_halo2_kernel", kStamps, 62, 0, nullptr, &launch_halo<4>},
+    {76, 256, 128, kHalo, "conv_halo2_kernel", 0, 62, 0, nullptr, &launch_halo<5>},
+    // ... with edge patches: maps whose height or width is not a multiple of 16 (the aspect-ratio buckets); the patch grid is rounded up, stores of pixels
+    // outside the image are dropped per lane; no GroupNorm sums.  The rule for eligible convs, under 72's threshold.  Sums chunk-major like 71-76
+    {78, 256, 128, kHaloEdge, "conv_halo2_kernel+edge", 0, 62, 0, nullptr, &launch_halo<6>},
+    {77, 64, 16, kThin, "conv_thin_kernel", 0, 62, 0, &launch_thin, &launch_thin},      // conv_thin.hip: at most 16 output channels, by rule; its launcher refuses GEMM arguments itself
+};
+constexpr const Tile* find_tile(int code) {
+    for (const Tile& t : kTiles)
+        if (t.code == code) return &t;
+    return nullptr;
+}
+constexpr bool is_family(int code, Family f) { return find_tile(code) && find_tile(code)->family == f; }
+
+// What the tuner times besides the rule's code, in timing order (the order decides ties): plain tile codes (tune_candidates filters them), then split-K
+// encodings code + 10000 * s (s = 2..4) of the split lists, offered while the tile's grid stays under per_cu blocks per CU
+constexpr int kCandF16[] = {43, 46, 42, 44, 51, 52, 54, 96, 81, 63, 47, 48, 64, 72, 78};      // 47 (128x96): FIE_TUNE_47=0 leaves it out
+constexpr int kCandW8[] = {43, 42, 62, 52, 54};
+constexpr int kCandX8[] = {43, 42, 47, 51, 52, 54, 62, 63};
+struct SplitCand { int code, per_cu; };
+constexpr SplitCand kSplitF16[] = {{96, 1}, {95, 1}, {47, 1}, {54, 2}, {52, 2}};
+constexpr SplitCand kSplitX8[] = {{62, 1}, {51, 1}, {47, 1}, {54, 2}, {52, 2}};
+
+// ---- the checks the hand-kept lists never had: 0, or the number of the first rule the tables break
+template <size_t N>
+constexpr bool f8_built(const fie_f8_tile (&built)[N], int code) {      // a kernel of that precision with the row's tile shape
+    const Tile* t = find_tile(code);
+    for (const fie_f8_tile& b : built)
+        if (t && b.code == code && b.bm == t->bm && b.bn == t->bn) return true;
+    return false;
+}
+constexpr int table_error() {
+    for (const Tile& t : kTiles) {
+        int n = 0;
+        for (const Tile& u : kTiles) n += u.code == t.code;
+        if (n != 1) return 1;                                                                       // codes are unique
+        if (!f8_built(kFieW8Tiles, t.w8) || (t.x8 && !f8_built(kFieX8Tiles, t.x8))) return 2;       // a remap target is a row with a kernel of that precision
+        if ((t.flags & kSplitK) && t.family != kRing) return 3;                                     // only the ring kernels reduce split K
+        if ((!t.conv && !(t.flags & kGemmOnly)) || (!t.gemm && t.family != kHalo && t.family != kHaloEdge)) return 4;      // a missing view is declared (run_code refuses the halo rows' GEMM view by family)
+    }
+    for (int c : kCandF16) if (!find_tile(c)) return 5;                                                // every candidate is a row, with a kernel of its precision
+    for (int c : kCandW8) if (!f8_built(kFieW8Tiles, c)) return 6;
+    for (int c : kCandX8) if (!f8_built(kFieX8Tiles, c)) return 7;
+    for (const SplitCand& c : kSplitF16) if (!find_tile(c.code) || !(find_tile(c.code)->flags & kSplitK)) return 8;
+    for (const SplitCand& c : kSplitX8) if (!f8_built(kFieX8Tiles, c.code) || !(find_tile(c.code)->flags & kSplitK)) return 9;
+    return 0;
+}
+static_assert(table_error() == 0, "kTiles / candidate lists inconsistent: see table_error for the rule with that number");
 
 // Heuristic tile code for a shape (the default; the autotuner below and the debug hooks can replace it).
 template <int MODE>
@@ -731,11 +824,11 @@ int heuristic_code(const fie_ctx* ctx, const GemmArgs& a, bool dma_ok) {
 // One launch of `code` (order: 0 n-tiles fastest, 1 m-tiles fastest, -1 estimate).
 constexpr int64_t kSkTickets = 4096;        // arrival counters at the head of the split-K workspace
 
-// Largest usable split for a tile code: ring kernels with <= 16 accumulator fragments per lane (not 256x256), at least 4 K-steps per
-// slice, counters and slabs inside the bound workspace.  Returns 1 when split-K cannot run.
-inline int splitk_fit(const fie_ctx* ctx, const GemmArgs& a, int code, int bm, int bn, int want) {
-    const bool ring = (code >= 42 && code <= 54) || code == 62 || code == 95 || code == 96;
-    if (want <= 1 || !ring || !ctx->sk_ws || !ctx->splitk_mode || (a.w_scale && a.a_scale == 0.f)) return 1;
+// Largest usable split for a tile: a row that may split K (kSplitK), at least 4 K-steps per slice, counters and slabs inside the bound
+// workspace.  Returns 1 when split-K cannot run.
+inline int splitk_fit(const fie_ctx* ctx, const GemmArgs& a, const Tile& t, int want) {
+    const int bm = t.bm, bn = t.bn;
+    if (want <= 1 || !(t.flags & kSplitK) || !ctx->sk_ws || !ctx->splitk_mode || (a.w_scale && a.a_scale == 0.f)) return 1;
     const int64_t tiles = (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn) * (a.oscat == 2 ? 4 : 1);
     const int nk = (a.K + BK - 1) / BK / (a.a_scale != 0.f ? 2 : 1);      // fp8 activations: 128 k-values per K-step
     int s = want;
@@ -745,15 +838,14 @@ inline int splitk_fit(const fie_ctx* ctx, const GemmArgs& a, int code, int bm, i
 
 template <int MODE>
 int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int split = 1) {
-    const TileDim* t = nullptr;
-    for (const TileDim& d : kTiles)
-        if (d.code == code) t = &d;
+    const Tile* t = find_tile(code);
     FIE_REQUIRE(t != nullptr, "unknown tile code %d", code);
-    FIE_REQUIRE(code < 40 || code == 77 || dma_ok, "tile code %d: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0 or K1 %% 64 != 0)", code);
-    FIE_REQUIRE(!(a.taps2 && (code < 40 || a.w_scale)), "tile code %d: the 2x2 parity convs run on the f16 LDS-DMA kernels only", code);
-    FIE_REQUIRE(!(MODE == 1 && a.A2 && (code < 40 || code == 81 || code == 82 || a.w_scale)), "tile code %d: conv + 1x1 side inputs run on the f16 ring kernels and the halo-resident kernel (72) only", code);
-    FIE_REQUIRE(!((code >= 71 && code <= 76) && (MODE != 1 || !dma_ok || !fie_conv_halo_ok(a))), "tile code %d (halo-resident conv): stride-1 same-size 3x3 conv with H, W %% 16 == 0, Cin %% 64 == 0, f16 weights only", code);
-    FIE_REQUIRE(!(code == 78 && (MODE != 1 || !dma_ok || !fie_conv_halo_edge_ok(a))), "tile code 78 (halo-resident conv, edge patches): stride-1 same-size 3x3 conv with H or W %% 16 != 0, "
+    const Family fam = t->family;
+    FIE_REQUIRE(fam == kGeneric || fam == kThin || dma_ok, "tile code %d: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0 or K1 %% 64 != 0)", code);
+    FIE_REQUIRE(!(a.taps2 && (fam == kGeneric || a.w_scale)), "tile code %d: the 2x2 parity convs run on the f16 LDS-DMA kernels only", code);
+    FIE_REQUIRE(!(MODE == 1 && a.A2 && (fam == kGeneric || fam == kPhased || a.w_scale)), "tile code %d: conv + 1x1 side inputs run on the f16 ring kernels and the halo-resident kernel (72) only", code);
+    FIE_REQUIRE(!(fam == kHalo && (MODE != 1 || !dma_ok || !fie_conv_halo_ok(a))), "tile code %d (halo-resident conv): stride-1 same-size 3x3 conv with H, W %% 16 == 0, Cin %% 64 == 0, f16 weights only", code);
+    FIE_REQUIRE(!(fam == kHaloEdge && (MODE != 1 || !dma_ok || !fie_conv_halo_edge_ok(a))), "tile code 78 (halo-resident conv, edge patches): stride-1 same-size 3x3 conv with H or W %% 16 != 0, "
                 "Cin %% 64 == 0, Cin >= 128, N %% 64 == 0, f16 weights, no activation / scale / GroupNorm sums only");
     if (order < 0) {
         // Tile order = which operand an XCD re-streams past its 4 MiB L2.  Consecutive tile ids run on one XCD (xcd_remap), so an
@@ -773,30 +865,27 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
     const bool x8 = a.w_scale && a.a_scale != 0.f;           // e4m3 activations x e4m3 weights (gemm_x8.hip): its own tile set
     if (x8) {
         FIE_REQUIRE(dma_ok && !a.A2 && !a.taps2, "fp8 activations: plain GEMM / 3x3 conv views on the LDS-DMA kernels only");
-        if (code == 64) code = 63;                          // no alternating-refill form of the fp8 kernels
-        if (MODE == 1 && code == 63) code = 62;
-        code = code == 96 || code == 81 || code == 61 ? 62 : code == 95 ? 51 : code == 44 || code == 2 ? 42 : code == 46 || code == 3 || code == 1 ? 43 : code;
-        FIE_REQUIRE(code == 42 || code == 43 || code == 47 || code == 51 || code == 52 || code == 54 || code == 62 || code == 63, "tile code %d has no fp8-activation kernel", code);
-        for (const TileDim& d : kTiles)
-            if (d.code == code) t = &d;
-    } else if (a.w_scale) {          // fp8 weights: the three W8 ring tiles (gemm_w8.hip)
+        FIE_REQUIRE(t->x8 != 0, "tile code %d has no fp8-activation kernel", code);
+        t = find_tile(t->x8);
+        if (MODE == 1 && (t->flags & kGemmOnly)) t = find_tile(62);      // the 320-wide tile has no conv view: 256x128 stands in
+    } else if (a.w_scale) {          // fp8 weights: the W8 ring tiles (gemm_w8.hip)
         FIE_REQUIRE(dma_ok, "fp8 weights: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0 or K1 %% 64 != 0)");
-        code = (code == 43 || code == 46 || code == 3) ? 43 : (code == 42 || code == 44 || code == 2) ? 42 : (code == 52 || code == 54) ? code : 62;
-        for (const TileDim& d : kTiles)
-            if (d.code == code) t = &d;
+        t = find_tile(t->w8);
     }
+    code = t->code;
     a.nbm = (a.M + t->bm - 1) / t->bm;
     a.nbn = (a.N + t->bn - 1) / t->bn;
-    split = splitk_fit(ctx, a, code, t->bm, t->bn, split);
+    split = splitk_fit(ctx, a, *t, split);
     a.splitk = split;
     a.sk_tickets = static_cast<unsigned*>(ctx->sk_ws);
     a.sk_slabs = reinterpret_cast<float*>(static_cast<char*>(ctx->sk_ws) + kSkTickets * 4);
     a.order = order;
     a.probe = ctx->gemm_probe;
     a.epi_prefetch = ctx->epi_prefetch;
-    a.stamps = (code == 97 || code == 98 || code == 94 || code == 73 || code == 74) ? ctx->gemm_stamps : nullptr;
-    snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "%s<%dx%d> (%s, tile code %d)", code >= 90 ? "gemm3_kernel+prefetch" : code >= 80 ? "gemm8_kernel" : code == 77 ? "conv_thin_kernel" : code >= 71 && code <= 76 ? (code == 71 || code == 73 ? "conv_halo_kernel" : "conv_halo2_kernel") : code == 78 ? "conv_halo2_kernel+edge" : code >= 40 ? "gemm3_kernel" : "gemm_kernel",
-             t->bm, t->bn, MODE == 1 ? "conv3x3" : "gemm", code);
+    a.stamps = (t->flags & kStamps) ? ctx->gemm_stamps : nullptr;
+    if (x8) snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm3x8_kernel<%dx%d> (gemm, fp8 activations x fp8 weights, tile code %d)", t->bm, t->bn, code);
+    else if (a.w_scale) snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm3w8_kernel<%dx%d> (%s, fp8 weights, tile code %d)", t->bm, t->bn, MODE == 1 ? "conv3x3" : "gemm", code);
+    else snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "%s<%dx%d> (%s, tile code %d)", t->name, t->bm, t->bn, MODE == 1 ? "conv3x3" : "gemm", code);
     if (split > 1) snprintf(ctx->last_kernel + strlen(ctx->last_kernel) - 1, 24, ", split-K %d)", split);
     if (ctx->oplog) {
         // after the flop token: what it takes to rebuild the call (tools/launch_problems.py): batch, padding, side inputs and the A1|A2 seam, the parity
@@ -813,68 +902,17 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
             FIE_DESC(ctx, "gemm M=%d N=%d K=%d act=%d%s%s%s code=%d flop=%.0f%s", a.M, a.N, a.K, a.act, a.res ? " +res" : "", a.ln_tab ? " +ln" : "", a.w_scale ? (a.a_scale != 0.f ? " a8w8" : " w8") : "",
                      code + 10000 * (split > 1 ? split : 0), 2.0 * a.M * a.N * a.K, rebuild);
     }
-    if (x8) {
-        snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm3x8_kernel<%dx%d> (gemm, fp8 activations x fp8 weights, tile code %d%s", t->bm, t->bn, code, split > 1 ? "" : ")");
-        if (split > 1) snprintf(ctx->last_kernel + strlen(ctx->last_kernel), 24, ", split-K %d)", split);
-        return fie_launch_gemm_x8(ctx, a, code, MODE == 1);
-    }
-    if (a.w_scale) {
-        snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm3w8_kernel<%dx%d> (%s, fp8 weights, tile code %d)", t->bm, t->bn, MODE == 1 ? "conv3x3" : "gemm", code);
-        return fie_launch_gemm_w8(ctx, a, MODE == 1, code);
-    }
-    const dim3 grid((unsigned)(a.nbm * a.nbn * (a.oscat == 2 ? 4 : 1) * split)), block(256);
-    constexpr int M3 = MODE == 1 ? 2 : 0;
+    if (x8) return fie_launch_gemm_x8(ctx, a, code, MODE == 1);
+    if (a.w_scale) return fie_launch_gemm_w8(ctx, a, MODE == 1, code);
+    const dim3 grid((unsigned)(a.nbm * a.nbn * (a.oscat == 2 ? 4 : 1) * split));
     if (a.ln_tab) {
-        FIE_REQUIRE(MODE == 0 && is_ln_code(code) && split == 1, "LayerNorm-folded GEMM: tile code %d not built for it", code);
+        FIE_REQUIRE(MODE == 0 && t->ln && split == 1, "LayerNorm-folded GEMM: tile code %d not built for it", code);
         FIE_REQUIRE((code == 64) == (a.act == FIE_ACT_GEGLU), "LayerNorm-folded GEMM: GEGLU runs on tile 64 and nothing else does (code %d, act %d)", code, a.act);
-        switch (code) {
-            case 42: launch_ring_ln<128, 64, 3, 4>(ctx, a, grid); break;
-            case 96: launch_ring_ln<256, 128, 3, 8, true>(ctx, a, grid); break;
-            case 64: launch_ring_ln<256, 320, 2, 8, false, true>(ctx, a, grid); break;
-        }
-        FIE_LAUNCH_CHECK();
-        return FIE_OK;
+        return t->ln(ctx, a, grid);
     }
-    switch (code) {
-        case 1: fie_launch(ctx, (gemm_kernel<128, 128, MODE>), grid, block, 0, a); break;
-        case 2: fie_launch(ctx, (gemm_kernel<128, 64, MODE>), grid, block, 0, a); break;
-        case 3: fie_launch(ctx, (gemm_kernel<64, 64, MODE>), grid, block, 0, a); break;
-        case 42: launch_ring<128, 64, 3, M3, 4>(ctx, a, grid); break;
-        case 43: launch_ring<64, 64, 3, M3, 4>(ctx, a, grid); break;
-        case 51: launch_ring<128, 128, 3, M3, 8>(ctx, a, grid); break;
-        case 61: launch_ring<256, 256, 2, M3, 8>(ctx, a, grid); break;
-        case 62: launch_ring<256, 128, 3, M3, 8>(ctx, a, grid); break;
-        case 63:
-            FIE_REQUIRE(MODE == 0, "tile code 63 (256x320) is built for the GEMM view only");
-            launch_ring<256, 320, 2, 0, 8>(ctx, a, grid);
-            break;
-        case 64:
-            FIE_REQUIRE(MODE == 0, "tile code 64 (256x320, alternating refill) is built for the GEMM view only");
-            launch_ring<256, 320, 2, 0, 8, false, false, true>(ctx, a, grid);
-            break;
-        case 52: launch_ring<128, 128, 2, M3, 8>(ctx, a, grid); break;
-        case 47: launch_ring<128, 96, 3, M3, 4>(ctx, a, grid); break;
-        case 48: launch_ring<128, 80, 3, M3, 4>(ctx, a, grid); break;       // weight rows past the packed matrix (80 does not divide Npad) read as zero through the descriptor
-        case 54: launch_ring<192, 128, 2, M3, 8>(ctx, a, grid); break;
-        case 46: launch_ring<64, 64, 2, M3, 4>(ctx, a, grid); break;
-        case 44: launch_ring<128, 64, 2, M3, 4>(ctx, a, grid); break;
-        case 95: launch_ring<128, 128, 3, M3, 8, true>(ctx, a, grid); break;
-        case 96: launch_ring<256, 128, 3, M3, 8, true>(ctx, a, grid); break;
-        case 97: launch_ring<256, 128, 3, M3, 8, false, true>(ctx, a, grid); break;
-        case 98: launch_ring<256, 128, 3, M3, 8, true, true>(ctx, a, grid); break;
-        case 94: launch_ring<128, 64, 3, M3, 4, false, true>(ctx, a, grid); break;
-        case 71: return fie_launch_conv_halo(ctx, a, 0);
-        case 73: return fie_launch_conv_halo(ctx, a, 1);
-        case 72: return fie_launch_conv_halo(ctx, a, 2);
-        case 76: return fie_launch_conv_halo(ctx, a, 5);
-        case 74: return fie_launch_conv_halo(ctx, a, 4);
-        case 77: return fie_launch_conv_thin(ctx, a);
-        case 78: return fie_launch_conv_halo(ctx, a, 6);
-        case 81: return fie_launch_gemm8(ctx, a, MODE == 1, 0);
-        case 82: return fie_launch_gemm8(ctx, a, MODE == 1, 1);   // A/B: second DMA piece of a phase issued from inside the MFMA cluster (measured slower)
-    }
-    FIE_LAUNCH_CHECK();
-    return FIE_OK;
+    const LaunchFn fn = MODE == 1 ? t->conv : t->gemm;
+    FIE_REQUIRE(fn != nullptr, "tile code %d (%dx%d%s) is built for the GEMM view only", code, t->bm, t->bn, (t->flags & kAlt) ? ", alternating refill" : "");
+    return fn(ctx, a, grid);
 }
 
 // ---- per-shape autotune (fie_gemm_autotune): the first eager launch of a shape times every eligible tile on a scratch output
@@ -891,25 +929,21 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
 // (tools/cold_weights.py).
 constexpr size_t kFlushBytes = 384u << 20;
 
-// What the tuner times besides the rule's code `guess`, in timing order: plain tile codes, then split-K encodings code + 10000 * s (s = 2..4).
-// autotune below times exactly this list; fie_debug_tune_candidates reports it (tests/test_launch_table_gpu.py runs every entry at the product's shapes).
+// What the tuner times besides the rule's code `guess` (kCandF16 / kCandW8 / kCandX8 and the split lists above, filtered): autotune below times exactly this list; fie_debug_tune_candidates reports it (tests/test_launch_table_gpu.py runs every entry at the product's shapes).
 template <int MODE>
 std::vector<int> tune_candidates(const fie_ctx* ctx, const GemmArgs& a, int guess) {
-    static const int kRing[] = {43, 46, 42, 44, 51, 52, 54, 96, 81, 63, 47, 48, 64, 72, 78};      // 47 (128x96): FIE_TUNE_47=0 leaves it out
     static const bool use47 = !(getenv("FIE_TUNE_47") && getenv("FIE_TUNE_47")[0] == '0');
-    static const int kW8[] = {43, 42, 62, 52, 54};
-    static const int kX8[] = {43, 42, 47, 51, 52, 54, 62, 63};
     std::vector<int> out;
     auto blocks = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
     const bool x8 = a.w_scale && a.a_scale != 0.f;
-    const int* cand = x8 ? kX8 : a.w_scale ? kW8 : kRing;
-    const int ncand = x8 ? 8 : a.w_scale ? 5 : 15;
+    const int* cand = x8 ? kCandX8 : a.w_scale ? kCandW8 : kCandF16;
+    const size_t ncand = x8 ? std::size(kCandX8) : a.w_scale ? std::size(kCandW8) : std::size(kCandF16);
     auto excluded = [&](int c) {
         for (int e : ctx->tune_exclude)
             if (e == c) return e != 0;
         return false;
     };
-    for (int i = 0; i < ncand; ++i) {
+    for (size_t i = 0; i < ncand; ++i) {
         const int c = cand[i];
         if (c == guess || excluded(c)) continue;
         if ((c == 43 || c == 46) && blocks(64, 64) > 64 * ctx->num_cus) continue;       // tens of thousands of tiny tiles: never wins
@@ -928,18 +962,14 @@ std::vector<int> tune_candidates(const fie_ctx* ctx, const GemmArgs& a, int gues
     // to 2-4 blocks, reduced in the launch (gemm_common.h: splitk_reduce).  Changes the fp32 summation order, so unlike the tile choice
     // it is visible in the last bit of some f16 outputs; fixed per (shape, choice), hence deterministic within a process.
     if ((!a.w_scale || x8) && ctx->sk_ws && ctx->splitk_mode && !excluded(10000)) {
-        struct SplitCand { int code, bm, bn, per_cu; };
-        static const SplitCand kSplitF16[] = {{96, 256, 128, 1}, {95, 128, 128, 1}, {47, 128, 96, 1}, {54, 192, 128, 2}, {52, 128, 128, 2}};
-        static const SplitCand kSplitX8[] = {{62, 256, 128, 1}, {51, 128, 128, 1}, {47, 128, 96, 1}, {54, 192, 128, 2}, {52, 128, 128, 2}};
-        const SplitCand* sc = x8 ? kSplitX8 : kSplitF16;
-        for (int ci = 0; ci < 5; ++ci) {
-            const SplitCand& c = sc[ci];
+        for (const SplitCand& c : x8 ? kSplitX8 : kSplitF16) {
             if (excluded(c.code)) continue;
-            const int64_t nb = blocks(c.bm, c.bn) * (a.oscat == 2 ? 4 : 1);
+            const Tile& t = *find_tile(c.code);
+            const int64_t nb = blocks(t.bm, t.bn) * (a.oscat == 2 ? 4 : 1);
             if (nb >= ctx->num_cus * c.per_cu) continue;                 // the grid already fills the chip
             for (int sp = 2; sp <= 4; ++sp) {
                 if (nb * sp > (int64_t)ctx->num_cus * c.per_cu * 21 / 20) break;
-                if (splitk_fit(ctx, a, c.code, c.bm, c.bn, sp) != sp) continue;
+                if (splitk_fit(ctx, a, t, sp) != sp) continue;
                 out.push_back(c.code + 10000 * sp);
             }
         }
@@ -1019,7 +1049,7 @@ int launch(fie_ctx* ctx, GemmArgs& a) {
         else if (a.N % 128 == 0 && blocks(256, 128) >= 150 && (a.N >= 1536 || a.M >= 16384)) code = 96;
         else code = 42;
         const int forced = ctx->force_tile % 1000;
-        if (forced && is_ln_code(forced) && (forced == 64) == (a.act == FIE_ACT_GEGLU)) code = forced;
+        if (forced && find_tile(forced) && find_tile(forced)->ln && (forced == 64) == (a.act == FIE_ACT_GEGLU)) code = forced;
         return run_code<MODE>(ctx, a, code, -1, dma_ok, 1);
     }
     int code = heuristic_code<MODE>(ctx, a, dma_ok);
@@ -1067,7 +1097,7 @@ int launch(fie_ctx* ctx, GemmArgs& a) {
     // tuner keys carry neither the map's height and width nor the epilogue: one key covers 144x112 and 168x96 (M 16128), and 78 refuses GroupNorm
     // sums and activations.  A remembered halo-resident code the launch is not eligible for (72 met on a map of whole patches, then the same key
     // on a bucket map; 78 met without sums, then with them) falls back to the rule instead of failing
-    if (MODE == 1 && !pinned && ((code >= 71 && code <= 76 && !fie_conv_halo_ok(a)) || (code == 78 && !fie_conv_halo_edge_ok(a)))) {
+    if (MODE == 1 && !pinned && ((is_family(code, kHalo) && !fie_conv_halo_ok(a)) || (is_family(code, kHaloEdge) && !fie_conv_halo_edge_ok(a)))) {
         code = heuristic_code<MODE>(ctx, a, dma_ok);
         order = -1;
         split = 1;
@@ -1110,37 +1140,12 @@ __global__ void pack_conv_kernel(const half_t* src, int Cout, int Cin, int cin_p
     }
 }
 
-template <int MODE>
-hipError_t ring_attrs() {
-    hipError_t e = ring_attr<128, 64, 3, MODE, 4>();
-    if (e == hipSuccess) e = ring_attr<64, 64, 3, MODE, 4>();
-    if (e == hipSuccess) e = ring_attr<128, 128, 3, MODE, 8>();
-    if (e == hipSuccess) e = ring_attr<256, 256, 2, MODE, 8>();
-    if (e == hipSuccess) e = ring_attr<256, 128, 3, MODE, 8>();
-    if (e == hipSuccess && MODE == 0) e = ring_attr<256, 320, 2, 0, 8>();
-    if (e == hipSuccess && MODE == 0) e = ring_attr<256, 320, 2, 0, 8, false, false, true>();
-    if (e == hipSuccess) e = ring_attr<128, 128, 2, MODE, 8>();
-    if (e == hipSuccess) e = ring_attr<128, 96, 3, MODE, 4>();
-    if (e == hipSuccess) e = ring_attr<128, 80, 3, MODE, 4>();
-    if (e == hipSuccess) e = ring_attr<192, 128, 2, MODE, 8>();
-    if (e == hipSuccess) e = ring_attr<64, 64, 2, MODE, 4>();
-    if (e == hipSuccess) e = ring_attr<128, 64, 2, MODE, 4>();
-    if (e == hipSuccess) e = ring_attr<128, 128, 3, MODE, 8, true>();
-    if (e == hipSuccess) e = ring_attr<256, 128, 3, MODE, 8, true>();
-    if (e == hipSuccess) e = ring_attr<256, 128, 3, MODE, 8, false, true>();
-    if (e == hipSuccess) e = ring_attr<256, 128, 3, MODE, 8, true, true>();
-    if (e == hipSuccess) e = ring_attr<128, 64, 3, MODE, 4, false, true>();
-    return e;
-}
-
 }  // namespace
 
 int fie_gemm_init(void) {
-    hipError_t e = ring_attrs<0>();
-    if (e == hipSuccess) e = ring_attrs<2>();
-    if (e == hipSuccess) e = ring_attr_ln<128, 64, 3, 4>();
-    if (e == hipSuccess) e = ring_attr_ln<256, 128, 3, 8, true>();
-    if (e == hipSuccess) e = ring_attr_ln<256, 320, 2, 8, false, true>();
+    hipError_t e = hipSuccess;
+    for (const Tile& t : kTiles)
+        if (e == hipSuccess && t.attr) e = t.attr();
     if (e != hipSuccess) {
         fie_set_error("gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         return FIE_EHIP;

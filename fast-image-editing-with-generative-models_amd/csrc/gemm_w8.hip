@@ -14,6 +14,7 @@
 // 64-byte-per-row weight image: a DMA piece is 16 rows x 64 B, 16-byte chunks XOR-swizzled by (row >> 2) & 3 (rows r and r + 4 would
 // otherwise share banks for the ds_read_b64 fragment reads), applied on the SOURCE chunk and on the read.
 #include "gemm_common.h"
+#include "gemm_tiles.h"
 
 using namespace fie_gemm;
 
@@ -214,19 +215,24 @@ __global__ __launch_bounds__(256) void pack_f8_kernel(const half_t* src, int64_t
 
 }  // namespace
 
+// one tile of FIE_W8_TILES (gemm_tiles.h): its two views' dynamic-LDS attribute, and its launch
+template <int BM, int BN, int ST, int NW>
+static hipError_t w8_attr() {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm3w8_kernel<BM, BN, ST, 0, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, w8_lds<BM, BN, ST>());
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm3w8_kernel<BM, BN, ST, 2, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, w8_lds<BM, BN, ST>());
+    return e;
+}
+
+template <int BM, int BN, int ST, int NW>
+static void launch_w8(fie_ctx* ctx, const GemmArgs& a, int conv, dim3 grid) {
+    fie_launch(ctx, conv ? gemm3w8_kernel<BM, BN, ST, 2, NW> : gemm3w8_kernel<BM, BN, ST, 0, NW>, grid, dim3(NW * 64), w8_lds<BM, BN, ST>(), a);
+}
+
 int fie_gemm_w8_init(void) {
     hipError_t e = hipSuccess;
-    auto set = [&](const void* f, int lds) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds); };
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<256, 128, 3, 0, 8>), w8_lds<256, 128, 3>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<256, 128, 3, 2, 8>), w8_lds<256, 128, 3>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<128, 64, 3, 0, 4>), w8_lds<128, 64, 3>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<128, 64, 3, 2, 4>), w8_lds<128, 64, 3>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<64, 64, 3, 0, 4>), w8_lds<64, 64, 3>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<64, 64, 3, 2, 4>), w8_lds<64, 64, 3>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<128, 128, 2, 0, 8>), w8_lds<128, 128, 2>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<128, 128, 2, 2, 8>), w8_lds<128, 128, 2>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<192, 128, 2, 0, 8>), w8_lds<192, 128, 2>());
-    set(reinterpret_cast<const void*>(&gemm3w8_kernel<192, 128, 2, 2, 8>), w8_lds<192, 128, 2>());
+#define FIE_W8_ATTR(code, BM, BN, ST, NW) if (e == hipSuccess) e = w8_attr<BM, BN, ST, NW>();
+    FIE_W8_TILES(FIE_W8_ATTR)
+#undef FIE_W8_ATTR
     if (e != hipSuccess) {
         fie_set_error("gemm_w8: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         return FIE_EHIP;
@@ -234,21 +240,14 @@ int fie_gemm_w8_init(void) {
     return FIE_OK;
 }
 
-template <int BM, int BN, int NW, int ST = 3>
-static void launch_w8(fie_ctx* ctx, const GemmArgs& a, int conv, dim3 grid) {
-    constexpr int lds = w8_lds<BM, BN, ST>();
-    if (conv) fie_launch(ctx, (gemm3w8_kernel<BM, BN, ST, 2, NW>), grid, dim3(NW * 64), lds, a);
-    else fie_launch(ctx, (gemm3w8_kernel<BM, BN, ST, 0, NW>), grid, dim3(NW * 64), lds, a);
-}
-
-// code: 62 (256x128 x 3 stages, 8 waves), 42 (128x64), 43 (64x64), 52 / 54 (128x128 / 192x128 x 2 stages, 8 waves: two and more blocks per CU)
 int fie_launch_gemm_w8(fie_ctx* ctx, const GemmArgs& a, int conv, int code) {
     const dim3 grid((unsigned)(a.nbm * a.nbn));
-    if (code == 62) launch_w8<256, 128, 8>(ctx, a, conv, grid);
-    else if (code == 54) launch_w8<192, 128, 8, 2>(ctx, a, conv, grid);
-    else if (code == 52) launch_w8<128, 128, 8, 2>(ctx, a, conv, grid);
-    else if (code == 42) launch_w8<128, 64, 4>(ctx, a, conv, grid);
-    else launch_w8<64, 64, 4>(ctx, a, conv, grid);
+    switch (code) {
+#define FIE_W8_CASE(code, BM, BN, ST, NW) case code: launch_w8<BM, BN, ST, NW>(ctx, a, conv, grid); break;
+        FIE_W8_TILES(FIE_W8_CASE)
+#undef FIE_W8_CASE
+        default: fie_set_error("fie_launch_gemm_w8: tile code %d not built", code); return FIE_EINVAL;
+    }
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }

@@ -11,6 +11,7 @@
 // (lane = (row 0-15, k-block 0-3): two ds_read_b128), operands swapped (weights first) so a lane owns 4 consecutive output channels.
 // Entry: fie_gemm_x8_f16 (include/fie.h).
 #include "gemm_common.h"
+#include "gemm_tiles.h"
 
 using namespace fie_gemm;
 
@@ -242,14 +243,10 @@ __global__ void quant_f8_kernel(const half_t* x, int64_t ldx, unsigned char* y, 
 }  // namespace
 
 int fie_gemm_x8_init(void) {
-    hipError_t e = x8_attr<128, 64, 3, 4>();
-    if (e == hipSuccess) e = x8_attr<64, 64, 3, 4>();
-    if (e == hipSuccess) e = x8_attr<128, 96, 3, 4>();
-    if (e == hipSuccess) e = x8_attr<128, 128, 3, 8>();
-    if (e == hipSuccess) e = x8_attr<128, 128, 2, 8>();
-    if (e == hipSuccess) e = x8_attr<192, 128, 2, 8>();
-    if (e == hipSuccess) e = x8_attr<256, 128, 3, 8>();
-    if (e == hipSuccess) e = x8_attr<256, 320, 2, 8>();
+    hipError_t e = hipSuccess;
+#define FIE_X8_ATTR(code, BM, BN, ST, NW) if (e == hipSuccess) e = x8_attr<BM, BN, ST, NW>();
+    FIE_X8_TILES(FIE_X8_ATTR)
+#undef FIE_X8_ATTR
     if (e != hipSuccess) {
         fie_set_error("gemm_x8: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         return FIE_EHIP;
@@ -257,20 +254,14 @@ int fie_gemm_x8_init(void) {
     return FIE_OK;
 }
 
-// code: 42 / 43 / 47 (128x64 / 64x64 / 128x96, 4 waves, 3 stages), 51 / 62 (128x128 / 256x128, 8 waves, 3 stages), 52 / 54 (128x128 / 192x128, 2 stages),
-// 63 (256x320, 2 stages); the grid carries the split-K factor (a.splitk)
+// the tiles of FIE_X8_TILES (gemm_tiles.h); the grid carries the split-K factor (a.splitk)
 int fie_launch_gemm_x8(fie_ctx* ctx, const GemmArgs& a, int code, int conv) {
     const dim3 grid((unsigned)(a.nbm * a.nbn * (a.splitk > 1 ? a.splitk : 1)));
     if (conv && code == 63) { fie_set_error("fie_launch_gemm_x8: tile code 63 is built for the GEMM view only"); return FIE_EINVAL; }
     switch (code) {
-        case 42: launch_x8<128, 64, 3, 4>(ctx, a, grid, conv); break;
-        case 43: launch_x8<64, 64, 3, 4>(ctx, a, grid, conv); break;
-        case 47: launch_x8<128, 96, 3, 4>(ctx, a, grid, conv); break;
-        case 51: launch_x8<128, 128, 3, 8>(ctx, a, grid, conv); break;
-        case 52: launch_x8<128, 128, 2, 8>(ctx, a, grid, conv); break;
-        case 54: launch_x8<192, 128, 2, 8>(ctx, a, grid, conv); break;
-        case 62: launch_x8<256, 128, 3, 8>(ctx, a, grid, conv); break;
-        case 63: launch_x8<256, 320, 2, 8>(ctx, a, grid, 0); break;
+#define FIE_X8_CASE(code, BM, BN, ST, NW) case code: launch_x8<BM, BN, ST, NW>(ctx, a, grid, conv); break;
+        FIE_X8_TILES(FIE_X8_CASE)
+#undef FIE_X8_CASE
         default: fie_set_error("fie_launch_gemm_x8: tile code %d not built", code); return FIE_EINVAL;
     }
     FIE_LAUNCH_CHECK();

@@ -378,6 +378,147 @@ def test_gemm_conv_every_shipped_kernel(fie, code):
             fie.force_tile(0)
 
 
+# What fie_debug_last_gemm_kernel prints for each tile code, read off the rule the launch table replaced (code >= 90: "gemm3_kernel+prefetch" -- also for
+# 94 / 97, which do not prefetch --, >= 80: gemm8, 77: thin, 71 / 73: halo, 72 / 74 / 76: halo2, 78: halo2+edge, >= 40: gemm3, else gemm_kernel) and its tile sizes
+TILE_NAMES = {1: "gemm_kernel<128x128>", 2: "gemm_kernel<128x64>", 3: "gemm_kernel<64x64>", 42: "gemm3_kernel<128x64>", 43: "gemm3_kernel<64x64>",
+              44: "gemm3_kernel<128x64>", 46: "gemm3_kernel<64x64>", 47: "gemm3_kernel<128x96>", 48: "gemm3_kernel<128x80>", 51: "gemm3_kernel<128x128>",
+              52: "gemm3_kernel<128x128>", 54: "gemm3_kernel<192x128>", 61: "gemm3_kernel<256x256>", 62: "gemm3_kernel<256x128>", 63: "gemm3_kernel<256x320>",
+              64: "gemm3_kernel<256x320>", 94: "gemm3_kernel+prefetch<128x64>", 95: "gemm3_kernel+prefetch<128x128>", 96: "gemm3_kernel+prefetch<256x128>",
+              97: "gemm3_kernel+prefetch<256x128>", 98: "gemm3_kernel+prefetch<256x128>", 81: "gemm8_kernel<256x256>", 82: "gemm8_kernel<256x256>",
+              71: "conv_halo_kernel<256x128>", 73: "conv_halo_kernel<256x128>", 72: "conv_halo2_kernel<256x128>", 74: "conv_halo2_kernel<256x128>",
+              76: "conv_halo2_kernel<256x128>", 78: "conv_halo2_kernel+edge<256x128>", 77: "conv_thin_kernel<64x16>"}
+STAMP_CODES = (94, 97, 98, 73, 74)
+F8_SIZES = {42: "128x64", 43: "64x64", 47: "128x96", 51: "128x128", 52: "128x128", 54: "192x128", 62: "256x128", 63: "256x320"}
+
+
+def test_launch_table_rows(fie):
+    """Every row of the launch table (csrc/gemm_conv.hip kTiles), in each view and precision it is built for: forced with force_tile, the output against the
+    fp32 torch reference (3e-3 of max-abs: fp16 storage + fp32 accumulation, as everywhere in this file; the fp8 flows against the fp32 product of the SAME
+    quantised operands), last_gemm_kernel against the literal string, the stamp buffer written by the stamp codes and by no other, and the error of a code
+    with no kernel in a view.  A row whose attribute setter and launch disagree fails here with a launch error (every tile beyond 64 KiB of LDS).
+    Shapes: the smallest that reach every path -- GEMM 384 x 640 x 320 (N divisible by 320, 128 and 80, five K-steps, a partial row tile for every bm).
+    Every code can be forced; the LN-folded builds (42 / 96 / 64) are forced through gemm_ln."""
+    from fie_amd import hip
+    q8 = lambda t: t.float().clamp(-448, 448).to(torch.float8_e4m3fn).float()
+    m, n, k = 384, 640, 320
+    a, w, bias = rnd(m, k, seed=1), rnd(n, k, seed=2, scale=k ** -0.5), rnd(n, seed=3)
+    lin = a.float() @ w.float().T + bias.float()
+    ad, bd, wp = a.to(DEV), bias.to(DEV), fie.pack_linear(w.to(DEV))
+    stamps = torch.zeros(1 << 16, dtype=torch.int32, device=DEV)
+
+    def conv_case(b, h, w_, cin, cout, seed):
+        x, wt, cb = rnd(b, h, w_, cin, seed=seed), rnd(cout, cin, 3, 3, seed=seed + 1, scale=(9 * cin) ** -0.5), rnd(cout, seed=seed + 2)
+        return x, wt, cb, F.conv2d(x.float().permute(0, 3, 1, 2), wt.float(), cb.float(), padding=1)
+
+    def run_conv(code, case, wpc, **kw):
+        x, _, cb, ref = case
+        stamps.zero_()
+        fie.force_tile(code)
+        out = fie.conv3x3(x.to(DEV), wpc, ref.shape[1], bias=cb.to(DEV), **kw)
+        assert hip.last_gemm_kernel(fie) == f"{TILE_NAMES[code]} (conv3x3, tile code {code})"
+        assert rel_err(out.permute(0, 3, 1, 2), ref) < 3e-3, code
+        assert bool(stamps.any()) == (code in STAMP_CODES), code
+
+    def refused(message, call):
+        with pytest.raises(hip.FieError) as e:
+            call()
+        assert str(e.value) == "libfie_hip error -1: " + message
+
+    try:
+        fie.gemm_stamps(stamps)
+        # ---- f16, GEMM view: the lean epilogue (bias only) and the full one (+ SiLU)
+        for code in (1, 2, 3, 42, 43, 44, 46, 47, 48, 51, 52, 54, 61, 62, 63, 64, 94, 95, 96, 97, 98, 81, 82):
+            fie.force_tile(code)
+            for act, ref in ((hip.ACT_NONE, lin), (hip.ACT_SILU, F.silu(lin))):
+                stamps.zero_()
+                out = fie.gemm(ad, wp, n, bias=bd, act=act)
+                assert hip.last_gemm_kernel(fie) == f"{TILE_NAMES[code]} (gemm, tile code {code})"
+                assert rel_err(out, ref) < 3e-3, (code, act)
+                assert bool(stamps.any()) == (code in STAMP_CODES), code
+        # ---- f16, LayerNorm folded in
+        g, bta = 1 + 0.2 * rnd(k, seed=4), 0.1 * rnd(k, seed=5)
+        y = F.layer_norm(a.float(), (k,), g.float(), bta.float(), 1e-5) @ w.float().T + bias.float()
+        for code, geglu in ((42, False), (96, False), (64, True)):
+            wf, tab = fie.fold_layernorm(w, bias, g, bta, geglu=geglu)
+            fie.force_tile(code)
+            out = fie.gemm_ln(ad, wf, n, tab, act=hip.ACT_GEGLU if geglu else hip.ACT_NONE)
+            assert hip.last_gemm_kernel(fie) == f"{TILE_NAMES[code]} (gemm, tile code {code})"
+            assert rel_err(out, y[:, : n // 2] * F.gelu(y[:, n // 2:]) if geglu else y) < 3e-3, code
+        # ---- f16, conv view: 1x32x32, 128 -> 128; 78 on a map with a side that is no multiple of 16; 77 on its own test's small ragged shape
+        case = conv_case(1, 32, 32, 128, 128, 10)
+        wpc = fie.pack_conv3x3(case[1].to(DEV))
+        for code in (1, 2, 3, 42, 43, 44, 46, 47, 48, 51, 52, 54, 61, 62, 94, 95, 96, 97, 98, 81, 82, 71, 72, 73, 74, 76):
+            run_conv(code, case, wpc)
+        case78 = conv_case(1, 24, 40, 128, 128, 20)
+        run_conv(78, case78, fie.pack_conv3x3(case78[1].to(DEV)))
+        case77 = conv_case(2, 40, 24, 64, 12, 30)
+        run_conv(77, case77, fie.pack_conv3x3(case77[1].to(DEV)))
+        # ---- a code with no kernel in the view
+        for code, note in ((63, "256x320"), (64, "256x320, alternating refill")):
+            fie.force_tile(code)
+            refused(f"tile code {code} ({note}) is built for the GEMM view only", lambda: fie.conv3x3(case[0].to(DEV), wpc, 128))
+        fie.force_tile(66)
+        refused("unknown tile code 66", lambda: fie.gemm(ad, wp, n))
+        refused("unknown tile code 66", lambda: fie.conv3x3(case[0].to(DEV), wpc, 128))
+        fie.force_tile(72)
+        with pytest.raises(hip.FieError, match=r"tile code 72 \(halo-resident conv\)"):
+            fie.gemm(ad, wp, n)
+        fie.force_tile(77)
+        with pytest.raises(hip.FieError, match=r"thin conv \(tile code 77\)"):
+            fie.gemm(ad, wp, n)
+        # ---- split-K suffix (16 K-steps)
+        a16, w16 = rnd(m, 1024, seed=6), rnd(n, 1024, seed=7, scale=1 / 32)
+        fie.force_tile(20096)
+        out = fie.gemm(a16.to(DEV), fie.pack_linear(w16.to(DEV)), n)
+        assert hip.last_gemm_kernel(fie) == "gemm3_kernel+prefetch<256x128> (gemm, tile code 96, split-K 2)"
+        assert rel_err(out, a16.float() @ w16.float().T) < 3e-3
+        # ---- fp8 weights: the five W8 tiles in both views, and codes that run on another tile's kernel
+        fie.w8 = True
+        wp8, wpc8 = fie.pack_linear(w.to(DEV)), fie.pack_conv3x3(case[1].to(DEV))
+        wq = wp8.q.view(torch.float8_e4m3fn).float().cpu()[:n, :k] * wp8.scale[:n].cpu()[:, None]
+        ref8 = q8(a) @ wq.T + bias.float()
+        wqc = (wpc8.q.view(torch.float8_e4m3fn).float().cpu()[:128, :9 * 128] * wpc8.scale[:128].cpu()[:, None]).reshape(128, 3, 3, 128).permute(0, 3, 1, 2)
+        refc8 = F.conv2d(q8(case[0]).permute(0, 3, 1, 2), wqc, case[2].float(), padding=1)
+        for code, runs in ((42, 42), (43, 43), (52, 52), (54, 54), (62, 62), (96, 62), (2, 42), (46, 43), (1, 62), (47, 62), (81, 62), (77, 62)):
+            fie.force_tile(code)
+            if code != 77:
+                out = fie.gemm(ad, wp8, n, bias=bd)
+                assert hip.last_gemm_kernel(fie) == f"gemm3w8_kernel<{F8_SIZES[runs]}> (gemm, fp8 weights, tile code {runs})"
+                assert rel_err(out, ref8) < 3e-3, code
+            out = fie.conv3x3(case[0].to(DEV), wpc8, 128, bias=case[2].to(DEV))
+            assert hip.last_gemm_kernel(fie) == f"gemm3w8_kernel<{F8_SIZES[runs]}> (conv3x3, fp8 weights, tile code {runs})"
+            assert rel_err(out.permute(0, 3, 1, 2), refc8) < 3e-3, code
+        # ---- fp8 activations x fp8 weights: K 384 / Cin 128; the eight X8 tiles (63: GEMM view only, 256x128 stands in for it as a conv), stand-ins
+        kx = 384
+        ax, wx = rnd(m, kx, seed=8), rnd(n, kx, seed=9, scale=kx ** -0.5)
+        wpx = fie.pack_linear(wx.to(DEV))
+        ax8 = fie.quantize_f8(ax.to(DEV))
+        refx = q8(ax) @ (wpx.q.view(torch.float8_e4m3fn).float().cpu()[:n, :kx] * wpx.scale[:n].cpu()[:, None]).T + bias.float()
+        x8 = fie.quantize_f8(case[0].view(-1, 128).to(DEV)).view(1, 32, 32, 128)
+        for code, runs, runs_conv in ((42, 42, 42), (43, 43, 43), (47, 47, 47), (51, 51, 51), (52, 52, 52), (54, 54, 54), (62, 62, 62), (63, 63, 62), (64, 63, 62),
+                                      (96, 62, 62), (81, 62, 62), (61, 62, 62), (95, 51, 51), (44, 42, 42), (2, 42, 42), (46, 43, 43), (3, 43, 43), (1, 43, 43)):
+            fie.force_tile(code)
+            out = fie.gemm(ax8, wpx, n, bias=bd)
+            assert hip.last_gemm_kernel(fie) == f"gemm3x8_kernel<{F8_SIZES[runs]}> (gemm, fp8 activations x fp8 weights, tile code {runs})"
+            assert rel_err(out, refx) < 3e-3, code
+            out = fie.conv3x3(x8, wpc8, 128, bias=case[2].to(DEV))
+            assert hip.last_gemm_kernel(fie) == f"gemm3x8_kernel<{F8_SIZES[runs_conv]}> (gemm, fp8 activations x fp8 weights, tile code {runs_conv})"
+            assert rel_err(out.permute(0, 3, 1, 2), refc8) < 3e-3, code
+        for code in (48, 82, 94, 97, 98, 77):
+            fie.force_tile(code)
+            refused(f"tile code {code} has no fp8-activation kernel", lambda: fie.gemm(ax8, wpx, n))
+        a16q = fie.quantize_f8(a16.to(DEV))
+        wp16 = fie.pack_linear(w16.to(DEV))
+        fie.force_tile(20062)
+        out = fie.gemm(a16q, wp16, n)
+        assert hip.last_gemm_kernel(fie) == "gemm3x8_kernel<256x128> (gemm, fp8 activations x fp8 weights, tile code 62, split-K 2)"
+        assert rel_err(out, q8(a16) @ (wp16.q.view(torch.float8_e4m3fn).float().cpu()[:n, :1024] * wp16.scale[:n].cpu()[:, None]).T) < 3e-3
+    finally:
+        fie.w8 = False
+        fie.force_tile(0)
+        fie.gemm_stamps(None)
+
+
 @pytest.mark.parametrize("code", [63, 64])
 def test_gemm_view_only_tiles(fie, code):
     """Tile code built for the GEMM view only: 63 (256x320, 8 waves, wave tile 128x80, two-stage ring: the exact-fit tile of the FF1
