@@ -112,6 +112,7 @@ SIGNATURES = {
     "fie_lcm_step_masked_f32": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P, _P, _P, _P],
     "fie_pixels_out_composite_f16_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
     "fie_pixels_out_composite_f32_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
+    "fie_fullres_paste_rgb_u8": [_P, _P, _I, _I, _P, _L, _P, _L, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _L, _P],
     "fie_metrics_workspace_bytes": [_I, _I, _I],
     "fie_metrics_pairs_u8": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _L],
     "fie_clip_mask_rgb_u8": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
@@ -940,14 +941,7 @@ class Context:
         return self._resize(rgb_u8, h, w, out_h, out_w, (3,), lib().fie_resize_rgb_u8, filter="bicubic", out=out)
 
     def _resize(self, src, h, w, out_h, out_w, chan, entry, filter="lanczos", out=None):
-        from . import resize
-        tabs = []
-        for n_in, n_out in ((w, out_w), (h, out_h)):
-            key = (n_in, n_out) if filter == "lanczos" else (filter, n_in, n_out)
-            if n_in != n_out and key not in self._resize_tables:
-                kk, bounds, ks = resize.coefficients(n_in, n_out, filter)
-                self._resize_tables[key] = (torch.from_numpy(kk).to(self.device), torch.from_numpy(bounds).to(self.device), ks)
-            tabs.append(self._resize_tables.get(key) if n_in != n_out else (None, None, 0))
+        tabs = [self._axis_tables(w, out_w, filter), self._axis_tables(h, out_h, filter)]
         if out is None:
             out = torch.empty((out_h, out_w) + chan, device=src.device, dtype=torch.uint8)
         assert out.shape == (out_h, out_w) + chan and out.dtype == torch.uint8 and out.is_contiguous()
@@ -956,18 +950,22 @@ class Context:
         _chk(entry(self.h, _p(src), h, w, _p(out), out_h, out_w, _p(kx), _p(bx), ksx, _p(ky), _p(by), ksy, _p(tmp)))
         return out
 
-    def mask_prep(self, mask_l, blur=0.0):
-        """Edit-size u8 [H, W] mask on the device (white = edit) -> (mask_px f32 [H, W], mask_lat u8 [H/8 * W/8]): one launch of
-        fie_mask_prep.  mask_px is the binary mask L >= 128, or with blur = r > 0 its Gaussian feather (fie_amd/mask.py: gaussian_taps)."""
+    def _feather_taps(self, blur):
+        """The feather's Gaussian taps (fie_amd/mask.py: gaussian_taps) on the device, cached per sigma."""
         from . import mask as hmask
-        self.sync_stream()
-        h, w = mask_l.shape
-        assert mask_l.dtype == torch.uint8 and mask_l.is_contiguous()
         cache = self.__dict__.setdefault("_mask_taps", {})
         key = float(blur)
         if key not in cache:
             cache[key] = torch.from_numpy(hmask.gaussian_taps(key)).to(self.device)
-        taps = cache[key]
+        return cache[key]
+
+    def mask_prep(self, mask_l, blur=0.0):
+        """Edit-size u8 [H, W] mask on the device (white = edit) -> (mask_px f32 [H, W], mask_lat u8 [H/8 * W/8]): one launch of
+        fie_mask_prep.  mask_px is the binary mask L >= 128, or with blur = r > 0 its Gaussian feather (fie_amd/mask.py: gaussian_taps)."""
+        self.sync_stream()
+        h, w = mask_l.shape
+        assert mask_l.dtype == torch.uint8 and mask_l.is_contiguous()
+        taps = self._feather_taps(blur)
         m_px = torch.empty((h, w), device=self.device, dtype=torch.float32)
         m_lat = torch.empty(((h // 8) * (w // 8),), device=self.device, dtype=torch.uint8)
         _chk(lib().fie_mask_prep(self.h, _p(mask_l), h, w, _p(taps), (taps.numel() - 1) // 2, _p(m_px), _p(m_lat)))
@@ -981,6 +979,48 @@ class Context:
         out = self._alloc((h, w, 3), torch.uint8)
         _chk((lib().fie_pixels_out_composite_f32_u8 if self.f32 else lib().fie_pixels_out_composite_f16_u8)(
             self.h, _p(x_nhwc), ld, h, w, _p(source_u8), _p(mask_px), _p(out)))
+        return out
+
+    def _axis_tables(self, n_in, n_out, filter="lanczos"):
+        """(taps, bounds, ksize) of one axis of the 8-bit resample on the device, cached per (in, out) size; (None, None, 0) when the axis keeps
+        its size."""
+        from . import resize
+        if n_in == n_out:
+            return None, None, 0
+        key = (n_in, n_out) if filter == "lanczos" else (filter, n_in, n_out)
+        if key not in self._resize_tables:
+            kk, bounds, ks = resize.coefficients(n_in, n_out, filter)
+            self._resize_tables[key] = (torch.from_numpy(kk).to(self.device), torch.from_numpy(bounds).to(self.device), ks)
+        return self._resize_tables[key]
+
+    def fullres_paste(self, res_u8, source_u8, mask_l=None, blur=0.0, out=None):
+        """The full-resolution back end of an edit (fie_fullres_paste_rgb_u8; DESIGN.md section 13).  res_u8: u8 [h, w, 3], the edit-size result;
+        source_u8: u8 [H, W, 3], the source as uploaded; mask_l: None or u8 [H, W] (white = edit).  -> u8 [H, W, 3]: Pillow's LANCZOS resize of the
+        result to (W, H), bit for bit, and with a mask the source byte where the mask's feather (sigma `blur`, in pixels of the H x W image) is 0, the
+        resized byte where it is 1, the rounded blend between.  source_u8, mask_l and `out` may be views into larger images (unit strides inside a
+        row, any row pitch, any byte offset); `out` may be source_u8.  Two launches on the current stream, no synchronisation."""
+        self.sync_stream()
+        h, w, _ = res_u8.shape
+        H, W, _ = source_u8.shape
+        rows_ok = lambda t: t.dtype == torch.uint8 and t.stride(-1) == 1 and (t.dim() == 2 or t.stride(1) == 3)
+        if res_u8.dtype != torch.uint8 or not res_u8.is_contiguous() or res_u8.shape[2] != 3 or source_u8.shape[2] != 3 or not rows_ok(source_u8):
+            raise ValueError("fullres_paste: res_u8 must be a contiguous u8 [h, w, 3] tensor, source_u8 a u8 [H, W, 3] tensor with contiguous rows")
+        if out is None:
+            out = torch.empty((H, W, 3), device=self.device, dtype=torch.uint8)
+        if tuple(out.shape) != (H, W, 3) or not rows_ok(out):
+            raise ValueError(f"fullres_paste: out must be a u8 {(H, W, 3)} tensor with contiguous rows")
+        taps, radius = None, 0
+        if mask_l is not None:
+            if tuple(mask_l.shape) != (H, W) or not rows_ok(mask_l):
+                raise ValueError(f"fullres_paste: mask_l must be a u8 {(H, W)} tensor with contiguous rows, got {tuple(mask_l.shape)} {mask_l.dtype}")
+            taps = self._feather_taps(blur)
+            radius = (taps.numel() - 1) // 2
+        kx, bx, ksx = self._axis_tables(w, W)
+        ky, by, ksy = self._axis_tables(h, H)
+        tmp = torch.empty((h, W, 3), device=self.device, dtype=torch.uint8) if w != W else None
+        _chk(lib().fie_fullres_paste_rgb_u8(self.h, _p(res_u8), h, w, _p(source_u8), source_u8.stride(0), _p(mask_l),
+                                            mask_l.stride(0) if mask_l is not None else 0, H, W, _p(kx), _p(bx), ksx, _p(ky), _p(by), ksy,
+                                            _p(taps), radius, _p(out), out.stride(0), _p(tmp)))
         return out
 
     def metrics_pairs(self, a, b, mask=None):

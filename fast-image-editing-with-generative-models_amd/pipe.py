@@ -24,6 +24,15 @@ F16 = torch.float16
 _PIPE_SEQ = itertools.count()
 
 
+class DeviceOutput:
+    """What an `after_device` hook returns when the work it queued REPLACES the image the call returns: `out` (a u8 device tensor, or a list of
+    them -- one per image of a batch call, of any sizes) goes to the host instead of the edit-size result, `extra` comes back as `.extra`."""
+    __slots__ = ("out", "extra")
+
+    def __init__(self, out, extra=None):
+        self.out, self.extra = out, extra
+
+
 class HipImg2ImgPipeline:
     def __init__(self, ctx, cfgs, sds, tokenizers=None, sched_cfg=None, noise_dtype=None, weight_dtype="f16"):
         """cfgs / sds: dicts with keys unet, controlnet, vae, clip_l, clip_g (configs / diffusers-named state dicts).
@@ -594,7 +603,8 @@ class HipImg2ImgPipeline:
         no host wait in front of the edit, a repeated job in the rare case that they had not.  `mask_image` / `mask_blur` / `paste_back`
         (additive): a mask-restricted edit (prepare(); a list of masks for a batch call).  `after_device` (additive): a callable given the u8 result
         while it is still on the device, on the slot's stream behind the device job and outside its graph; it may queue more work there (FastEditor
-        scores the edit) and whatever it returns comes back as `.extra`, complete once the image has reached the host."""
+        scores the edit) and whatever it returns comes back as `.extra`, complete once the image has reached the host.  A hook that returns a
+        `DeviceOutput` replaces the image: its tensor(s) take the final device-to-host copy (FastEditor's full-resolution back end)."""
         if slot and not self.use_graph:
             raise ValueError("slots > 0 need hipGraph replay (the eager path shares per-image state)")
         caller, st = torch.cuda.current_stream(self.ctx.device), self.slot_stream(slot)
@@ -605,18 +615,33 @@ class HipImg2ImgPipeline:
         caller.wait_stream(st)
         return out
 
-    def _to_host(self, out_u8, slot):
+    def _to_host(self, out_u8, slot, varying=False):
         """D2H of the u8 result through a pinned staging buffer of the slot (a pageable `.cpu()` costs ~3x as much), then one
-        host memcpy so the caller owns its array.  Synchronises the current stream only."""
-        key = (slot, tuple(out_u8.shape))
-        host = self._host_out.get(key)
-        if host is None:
-            host = self._host_out[key] = torch.empty(out_u8.shape, dtype=torch.uint8, pin_memory=True)
-        host.copy_(out_u8, non_blocking=True)
+        host memcpy so the caller owns its array.  Synchronises the current stream only.  A list of tensors (a DeviceOutput of a batch call) comes
+        back as a list of arrays behind the one synchronisation.  `varying`: the shapes follow the caller's images (a DeviceOutput), so the staging
+        buffers are kept per image position and grown, not per shape."""
+        outs = out_u8 if isinstance(out_u8, (list, tuple)) else [out_u8]
+        hosts = []
+        for i, o in enumerate(outs):
+            if varying:
+                key, n = (slot, "varying", i), o.numel()
+                flat = self._host_out.get(key)
+                if flat is None or flat.numel() < n:
+                    flat = self._host_out[key] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+                host = flat[:n].view(o.shape)
+            else:
+                key = (slot, tuple(o.shape))
+                host = self._host_out.get(key)
+                if host is None:
+                    host = self._host_out[key] = torch.empty(o.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(o, non_blocking=True)
+            hosts.append(host)
         self.ctx.fetch_device_errors()                   # 16 bytes behind the image: a kernel that had to give up does not stay silent
         torch.cuda.current_stream(self.ctx.device).synchronize()
         self.ctx.check_device_errors(fetch=False)
-        return host.numpy().copy()
+        if isinstance(out_u8, (list, tuple)):
+            return [h.numpy().copy() for h in hosts]
+        return hosts[0].numpy().copy()
 
     def _call(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
               controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_args=(None, 0, True), after_device=None):
@@ -624,6 +649,8 @@ class HipImg2ImgPipeline:
             """One device job, the caller's after_device hook behind it, then the result on the host: -> (u8 array, hook's return)."""
             out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
             extra = after_device(out_u8) if after_device is not None else None
+            if isinstance(extra, DeviceOutput):             # the hook's own output travels instead of the edit-size image
+                return self._to_host(extra.out, slot, varying=True), extra.extra
             return self._to_host(out_u8, slot), extra       # device -> host sync, as `.images[0]` implies upstream
 
         if isinstance(prompt, (list, tuple)):            # [additive] a batch: lists of prompts / images / generators
@@ -633,7 +660,8 @@ class HipImg2ImgPipeline:
             arr, extra = run(job)
             if post_check is not None and post_check():
                 arr, extra = run(job)
-            arr = arr[None] if arr.ndim == 3 else arr
+            if not isinstance(arr, list):
+                arr = arr[None] if arr.ndim == 3 else arr
             if output_type == "np":
                 return types.SimpleNamespace(images=list(arr), extra=extra)
             return types.SimpleNamespace(images=[Image.fromarray(a) for a in arr], extra=extra)

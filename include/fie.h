@@ -553,6 +553,24 @@ int fie_pixels_out_composite_f16_u8(fie_ctx* ctx, const void* src, int64_t ld_in
 int fie_pixels_out_composite_f32_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, const uint8_t* source,
                                     const float* mask, uint8_t* dst);
 
+/* ---- Full-resolution back end of an edit: the edit-size result at the source's size, composited against the
+ * source's own bytes.  res: u8 [h, w, 3], the edit-size result.  The output is H x W: up = Pillow's 8-bit LANCZOS resize of res to
+ * (W, H), bit-exact (kx / bx / ksx, ky / by / ksy: the tables of fie_resize_rgb_u8 for w -> W and h -> H; a table is NULL on an axis
+ * that keeps its size).  mask_l == NULL: dst = up.  Otherwise mask_l is u8 H x W (white = edit, rows mask_pitch bytes apart) and, with
+ * M = (mask_l >= 128) feathered as fie_mask_prep feathers it (taps: f32 [2 * radius + 1], radius <= 64; {1.0f} with radius 0; same
+ * passes, same summation order, clamp-to-edge at the borders of the H x W image), dst = source where M <= 0, up where M >= 1,
+ * rint(M up + (1 - M) source) between.  source, dst: u8 H x W x 3 with rows source_pitch / dst_pitch bytes apart (>= 3 W; any value,
+ * any base alignment): a caller composites a region in place inside a larger image by pointing both at the region's first pixel
+ * with the image's pitch -- no byte outside the H x W x 3 region is read or written, and dst may be source.  tmp: u8 [h, W, 3]
+ * scratch, needed when w != W.  Two launches (one when w == W), asynchronous on the ctx stream: the horizontal resample into tmp, then
+ * one kernel per 64 x 16 output tile that stages the binary mask and its halo in LDS, feathers it, resamples its columns of tmp
+ * vertically, blends and stores.  No H x W f32 mask and no H x W resized image is written to memory; a tile whose mask, halo included,
+ * is all zero copies the source bytes. */
+int fie_fullres_paste_rgb_u8(fie_ctx* ctx, const uint8_t* res, int h, int w, const uint8_t* source, int64_t source_pitch,
+                             const uint8_t* mask_l, int64_t mask_pitch, int H, int W, const int* kx, const int* bx, int ksx,
+                             const int* ky, const int* by, int ksy, const float* taps, int radius, uint8_t* dst, int64_t dst_pitch,
+                             uint8_t* tmp);
+
 /* ---- Edit metrics on the device: SSE and SSIM of n pairs of u8 images in one pass.
  *   a, b: u8 [n, H, W, 3] (H, W >= 11: the 11-tap window's reflect padding); mask: NULL, or u8 [n, H, W] with non-zero = edited region.
  *   result: n rows of four 8-byte fields (8-byte aligned), written by the device:

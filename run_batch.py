@@ -90,6 +90,32 @@ def add_resolution_args(p):
     return p
 
 
+def add_region_args(p):
+    """[additive] full-resolution output and mask-region crops.  Kept apart from build_parser() for the same reason as
+    add_mask_args."""
+    p.add_argument("--output_size", type=str, default="edit", choices=["edit", "source"],
+                   help="[additive] 'edit': outputs at the size the edit ran at (--resolution); 'source': outputs at each source image's own size, "
+                        "composited there against the source's own pixels (with --use_mask)")
+    p.add_argument("--region", type=str, default="none", choices=["none", "mask"],
+                   help="[additive] 'mask' (needs --use_mask): edit only a crop around each item's mask at the model's native size and return the "
+                        "source-size image with the crop composited in (implies --output_size source)")
+    p.add_argument("--region_padding", type=int, default=32, help="[additive] with --region mask: pixels of context around the mask's bounding box")
+    return p
+
+
+def region_kwargs(args, have_mask):
+    """The --output_size / --region / --region_padding flags (absent on a parser without add_region_args) -> edit()'s keyword arguments."""
+    region = getattr(args, "region", "none")
+    if region == "mask" and not have_mask:
+        raise ValueError("--region mask needs --use_mask")
+    kw = {}
+    if region == "mask":
+        kw.update(region="mask", region_padding=getattr(args, "region_padding", 32))
+    elif getattr(args, "output_size", "edit") == "source":
+        kw.update(output_size="source")
+    return kw
+
+
 def add_metrics_args(p):
     """[additive] inline metrics.  Kept apart from build_parser() for the same reason as add_mask_args."""
     p.add_argument("--metrics", action="store_true",
@@ -204,6 +230,7 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     with_metrics = getattr(args, "metrics", False)
     if with_metrics:
         extra = dict(extra, metrics=True)
+    extra = dict(extra, **region_kwargs(args, use_mask))
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
     def flush():
@@ -309,7 +336,10 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    args = add_dino_args(add_clip_args(add_metrics_args(add_resolution_args(add_mask_args(build_parser()))))).parse_args(argv)
+    parser = add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_mask_args(build_parser()))))))
+    args = parser.parse_args(argv)
+    if args.region == "mask" and not args.use_mask:
+        parser.error("--region mask needs --use_mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets

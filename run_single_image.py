@@ -48,6 +48,13 @@ def build_parser():
     a("--resolution", type=str, default="square",
       help="[additive] output size: 'square' (1024x1024, the reference's), 'auto' (the SDXL aspect-ratio bucket nearest the source's) or WxH "
            "(multiples of 64, 512..2048, at most 1024^2 pixels)")
+    a("--output_size", type=str, default="edit", choices=["edit", "source"],
+      help="[additive] 'edit': the output at the size the edit ran at (--resolution); 'source': the output at the input image's own size, "
+           "composited there against the input's own pixels (with --mask)")
+    a("--region", type=str, default="none", choices=["none", "mask"],
+      help="[additive] 'mask' (needs --mask): edit only a crop around the mask at the model's native size and return the source-size image with "
+           "the crop composited in (implies --output_size source)")
+    a("--region_padding", type=int, default=32, help="[additive] with --region mask: pixels of context around the mask's bounding box")
     a("--clip_score_dir", type=str, default=None,
       help="[additive] with --compute_metrics: a local transformers CLIPModel directory (openai/clip-vit-base-patch16 is the reference's): fills the "
            "CLIP score.  Default: FIE_CLIP_SCORE_DIR, else <FIE_WEIGHTS_DIR>/clip_score when it exists")
@@ -75,7 +82,10 @@ def save_plot(path, source_img, edited_img, model, prompt):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.region == "mask" and args.mask is None:
+        parser.error("--region mask needs --mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets
@@ -116,6 +126,11 @@ def main(argv=None):
         print(f"      Mask: {args.mask} (blur {args.mask_blur}, paste-back {'off' if args.no_paste_back else 'on'})")
     if args.resolution != "square":
         extra.update(resolution=args.resolution)
+    if args.region == "mask":
+        extra.update(region="mask", region_padding=args.region_padding)
+        print(f"      Region: the mask's box + {args.region_padding} px, output at the source's size")
+    elif args.output_size == "source":
+        extra.update(output_size="source")
     t0 = time.time()
     edited_img = editor.edit(image=source_img, prompt=args.prompt, negative_prompt=args.negative_prompt,
                              num_inference_steps=args.steps, guidance_scale=args.guidance,

@@ -19,7 +19,8 @@ import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory
 from fie_amd import buckets, hip, stack
 from fie_amd import mask as hmask
 from fie_amd import metrics as hmetrics
-from fie_amd.pipe import HipImg2ImgPipeline
+from fie_amd import region as hregion
+from fie_amd.pipe import DeviceOutput, HipImg2ImgPipeline
 
 
 class FastEditor:
@@ -101,6 +102,7 @@ class FastEditor:
         self.pipe = HipImg2ImgPipeline(ctx, cfgs, sds, tokenizers=toks, noise_dtype=noise_dtype or self.dtype, weight_dtype=weight_dtype)
         self.controlnet = self.pipe.controlnet
         self._tls = threading.local()          # .slot: graph slot of the calling worker thread (set_in_flight)
+        self._fullres_out = {}                 # (slot, image) -> flat u8 buffer on the device, grown to the largest source: the full-resolution back end's output (output_size="source")
         self._metric_rows = {}                 # (slot, images) -> pinned int64 [images, 4]: where an edit's metric rows land (metrics=True)
         self.clip_scorer = None                # fie_amd.clip_score.ClipScorer: only from a directory, never a made-up number
         self._clip_rows = {}                   # (slot, rows) -> pinned f32 [rows, 2]: where an edit's CLIP score rows land
@@ -160,7 +162,7 @@ class FastEditor:
 
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
-             paste_back=True, *, resolution=None, metrics=False):
+             paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32):
         """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
         [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
         latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
@@ -173,10 +175,32 @@ class FastEditor:
         evaluate.py would score had the result been saved losslessly.  No additional host wait.  With
         `FastEditor(clip_score_dir=...)` the dict also holds `clip_score` (the result against `prompt`) and, with a mask,
         `clip_score_edited` (the result zeroed outside the edited region).  With `FastEditor(dino_dir=...)` the dict also holds `dino_distance`: the
-        structure distance between the ORIGINAL source and the result; None when the source or the result is not square."""
-        size = buckets.target_size(resolution, image.size)
+        structure distance between the ORIGINAL source and the result; None when the source or the result is not square.
+        [additive] `output_size`: None / "edit" returns the result at the edit size (above); "source" returns it at the source image's own
+        (width, height): the u8 result LANCZOS-resized on the device, bit-exact with `result.resize(image.size, Image.LANCZOS)`, and -- with a mask
+        and `paste_back` -- composited THERE against the source as uploaded: the caller's own bytes where the feathered mask is 0, the resized
+        result where it is 1, the rounded blend between (csrc/fullres.hip).  `mask_blur` is in pixels of the image the composite
+        runs on: the output image here, the edit-size image without `output_size`.  The latent blending is unchanged.  With `metrics=True` the
+        scored pair is the original source and this source-size output.
+        [additive] `region`: None edits the whole image; "mask" (needs a mask) or an explicit (l, t, r, b) box in source pixels runs the edit on
+        that crop of the source alone -- the model sees the region at its native size -- and returns the source-size image with the crop composited
+        in: exactly the source converted to RGB with `edit(image.crop(box), prompt, mask=mask.crop(box), output_size="source", ...)` pasted at the
+        box's corner.  The box of "mask" is the selection's bounding box grown by `region_padding` pixels and to the target's aspect
+        (fie_amd/region.py: mask_box).  A region implies output_size="source" (output_size="edit" with one is a ValueError).  With `metrics=True`
+        the scored pair is the region crop and its output, `bg_*` through the crop's mask: outside the region the output IS the source, so
+        whole-image numbers would only dilute the edit's by the region's share of the area."""
+        full = hregion.check_output(output_size, region)
         hmask.check_args(mask_blur, paste_back, mask is not None)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
+        if region is not None:
+            box = hregion.resolve(region, image.size, mask_l, region_padding, resolution)
+            res = self.edit(image.crop(box), prompt, negative_prompt, strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
+                            canny_low_threshold, canny_high_threshold, seed, None if mask_l is None else mask_l[box[1]:box[3], box[0]:box[2]],
+                            mask_blur, paste_back, resolution=resolution, metrics=metrics, output_size="source")
+            if metrics:
+                return hregion.paste(image, res[0], box), res[1]
+            return hregion.paste(image, res, box)
+        size = buckets.target_size(resolution, image.size)
         generator = None
         if seed is not None:
             generator = torch.Generator(device=self.device).manual_seed(seed)
@@ -188,19 +212,41 @@ class FastEditor:
         # the same stream, and whether the rounds had reached the fixed point is read when the result is on the host (the flags travelled
         # with it).  Common case: no host wait in front of the edit.  Rare case (a weak chain across more than 15 tiles): the remaining rounds
         # run and the device job is repeated on the final edge map -- same result as preprocess_image() + the pipeline call, always
-        origs, omasks = ([], []) if metrics else (None, None)
+        origs, omasks = ([], []) if metrics or full else (None, None)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False,
                                                                  original=origs)
             mask_dev = self._mask_device(mask_l, size, original=omasks)
+        hook = self._scorer(slot, origs, omasks, [prompt]) if metrics else None
+        if full:        # the edit-size job runs with its own paste-back off: the composite happens at the source's size, behind it
+            hook = self._fullres(slot, origs, omasks if paste_back else [None], mask_blur, hook)
         res = self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev,
                         control_image=control_dev, strength=strength, num_inference_steps=num_inference_steps,
                         guidance_scale=guidance_scale, controlnet_conditioning_scale=controlnet_conditioning_scale,
-                        generator=generator, post_check=finish, mask_image=mask_dev, mask_blur=mask_blur, paste_back=paste_back,
-                        after_device=self._scorer(slot, origs, omasks, [prompt]) if metrics else None)
+                        generator=generator, post_check=finish, mask_image=mask_dev, mask_blur=0 if full else mask_blur,
+                        paste_back=paste_back and not full, after_device=hook)
         if not metrics:
             return res.images[0]
         return res.images[0], self._scores(res.extra, [mask_l is not None])[0]
+
+    def _fullres(self, slot, origs, omasks, blur, then=None):
+        """The `after_device` hook of an edit with output_size="source": queues, on the edit's stream behind its result and outside its graph, the
+        full-resolution back end of every image of the job (hip.Context.fullres_paste: two launches each, into a buffer of the slot) and hands its
+        output to the pipeline's final device-to-host copy in place of the edit-size image.  `origs`: the sources as uploaded; `omasks`: the masks
+        as uploaded (None: that image is a pure resize); `then`: the scorer of metrics=True, which then scores the source-size outputs."""
+        ctx = self.pipe.ctx
+
+        def backend(out_u8):
+            batch = out_u8.dim() == 4
+            outs = []
+            with self.pipe.eager_lock:                    # the context's stream binding is shared by the threads of in-flight edits
+                for i, (o, src, m) in enumerate(zip(list(out_u8) if batch else [out_u8], origs, omasks)):
+                    buf = self._fullres_out.get((slot, i))           # grown, never shrunk: source sizes follow the caller's images
+                    if buf is None or buf.numel() < src.numel():
+                        buf = self._fullres_out[(slot, i)] = torch.empty(src.numel(), device=src.device, dtype=torch.uint8)
+                    outs.append(ctx.fullres_paste(o.contiguous(), src, m, blur if m is not None else 0.0, out=buf[:src.numel()].view(src.shape)))
+            return DeviceOutput(outs if batch else outs[0], then(outs if batch else outs[0]) if then is not None else None)
+        return backend
 
     def _scorer(self, slot, origs, omasks, prompts=None):
         """The `after_device` hook of an edit with metrics=True: queues, on the edit's stream behind its result, the LANCZOS resizes to
@@ -216,7 +262,7 @@ class FastEditor:
         stack = lambda ts: ts[0][None] if len(ts) == 1 else torch.stack(ts)
 
         def score(out_u8):
-            outs = [out_u8] if out_u8.dim() == 3 else list(out_u8)
+            outs = list(out_u8) if isinstance(out_u8, list) or out_u8.dim() == 4 else [out_u8]
             with self.pipe.eager_lock:                    # the context's stream binding is shared by the threads of in-flight edits
                 a = stack([to512(o) for o in origs])
                 b = stack([to512(o) for o in outs])
@@ -300,18 +346,37 @@ class FastEditor:
 
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
-                   paste_back=True, *, resolution=None, metrics=False):
+                   paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
         edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
         `masks`: None, or one mask per image as edit()'s `mask` (None in the list: that image is edited everywhere).
         `resolution`: as edit()'s, per image.  Images of different target sizes ("auto" on mixed aspect ratios) run as one device job per
         size, in the order of each size's first image; the results come back in input order.
-        `metrics=True`: returns (images, [dict per image]) as edit() does; all images of a device job are scored in one launch."""
+        `metrics=True`: returns (images, [dict per image]) as edit() does; all images of a device job are scored in one launch.
+        `output_size` / `region` / `region_padding`: as edit()'s; every image comes back at its own source's size, the back end queued per image
+        behind the job.  `region` may also be a LIST with one entry per image (None, "mask" or a box): each image gets its own box, images are
+        grouped by the target size of their crops, and an image whose entry is None is edited whole and returned at its source's size."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
             raise ValueError(f"{len(masks)} masks for {len(images)} images: one mask (or None) per image")
+        regions = list(region) if isinstance(region, list) else [region] * len(images)
+        if len(regions) != len(images):
+            raise ValueError(f"{len(regions)} regions for {len(images)} images: one region (or None) per image")
+        has_region = any(r is not None for r in regions)
+        full = hregion.check_output(output_size, "mask" if has_region else None)
+        if has_region:
+            hmask.check_args(mask_blur, paste_back, masks is not None and any(m is not None for m in masks))
+            mls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks or [None] * len(images), images)]
+            boxes = [hregion.resolve(r, im.size, m, region_padding, resolution) for r, im, m in zip(regions, images, mls)]
+            cut = lambda a, b: a if a is None or b is None else a[b[1]:b[3], b[0]:b[2]]
+            res = self.edit_batch([im if b is None else im.crop(b) for im, b in zip(images, boxes)], prompts, negative_prompts, strength,
+                                  num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold,
+                                  seed, None if masks is None else [cut(m, b) for m, b in zip(mls, boxes)], mask_blur, paste_back,
+                                  resolution=resolution, metrics=metrics, output_size="source")
+            outs = [o if b is None else hregion.paste(im, o, b) for im, o, b in zip(images, res[0] if metrics else res, boxes)]
+            return (outs, res[1]) if metrics else outs
         sizes = [buckets.target_size(resolution, im.size) for im in images]
         groups = {}
         for i, sz in enumerate(sizes):
@@ -324,7 +389,7 @@ class FastEditor:
                                       num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                       controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
                                       canny_high_threshold=canny_high_threshold, seed=seed, masks=pick(masks, idx), mask_blur=mask_blur,
-                                      paste_back=paste_back, resolution=sz, metrics=metrics)
+                                      paste_back=paste_back, resolution=sz, metrics=metrics, output_size=output_size)
                 res, ms = res if metrics else (res, [None] * len(idx))
                 for i, r, m in zip(idx, res, ms):
                     out[i], mets[i] = r, m
@@ -337,23 +402,25 @@ class FastEditor:
             gens = [torch.Generator(device=self.device).manual_seed(seed) for _ in images]
         slot = getattr(self._tls, "slot", 0)
         srcs, ctls = [], []
-        origs, omasks = ([], []) if metrics else (None, None)
+        origs, omasks = ([], []) if metrics or full else (None, None)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             for im in images:
-                one = [] if metrics else None
+                one = [] if metrics or full else None
                 s_dev, c_dev = self._canny_device(im, canny_low_threshold, canny_high_threshold, size=size, original=one)
                 srcs.append(s_dev)
                 ctls.append(c_dev)
-                if metrics:
+                if one is not None:
                     origs.append(one[0])
             mask_devs = [self._mask_device(m, size, original=omasks) for m in mask_ls] if mask_ls is not None else None
-        if metrics and mask_ls is None:
+        if (metrics or full) and mask_ls is None:
             omasks = [None] * len(images)
+        hook = self._scorer(slot, origs, omasks, list(prompts)) if metrics else None
+        if full:
+            hook = self._fullres(slot, origs, omasks if paste_back else [None] * len(images), mask_blur, hook)
         res = self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls,
                         strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                         controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens, mask_image=mask_devs,
-                        mask_blur=mask_blur, paste_back=paste_back,
-                        after_device=self._scorer(slot, origs, omasks, list(prompts)) if metrics else None)
+                        mask_blur=0 if full else mask_blur, paste_back=paste_back and not full, after_device=hook)
         if not metrics:
             return res.images
         return res.images, self._scores(res.extra, [m is not None for m in omasks])
