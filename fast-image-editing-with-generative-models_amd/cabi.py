@@ -334,7 +334,10 @@ def run_edit(pipe, job, step_cache=True):
     """The device side of one edit (pipe.run_device's job, one image) with EVERY model call going through a C-ABI forward: the call sequence a
     non-Python host would issue for the pipeline call at /root/reference/src/pipeline.py:261-272.  Returns the u8 HWC image on the device.
     A masked job (pipe.prepare(..., mask_image=...)) takes the masked entries: fie_latent_prep_src, fie_lcm_step_masked and, with the
-    paste-back, fie_pixels_out_composite_* (INTEGRATION.md, "Mask-restricted edits")."""
+    paste-back, fie_pixels_out_composite_* ("Mask-restricted edits").  The masked-content modes are not
+    part of this walk: a job prepared with one is refused rather than run as "original"."""
+    if job.get("content"):
+        raise NotImplementedError(f"run_edit: masked_content={job['content']!r} is not part of the C-ABI walk")
     ctx = pipe.ctx
     dev = ctx.device
     h, w = job["hw"]

@@ -112,6 +112,10 @@ SIGNATURES = {
     "fie_lcm_step_masked_f32": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P, _P, _P, _P],
     "fie_pixels_out_composite_f16_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
     "fie_pixels_out_composite_f32_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
+    "fie_mask_fill_workspace_bytes": [_I, _I],
+    "fie_mask_fill_rgb_u8": [_P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "fie_latent_prep_src_content": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I, _P, _P, _I],
+    "fie_latent_prep_src_content_f32": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I, _P, _P, _I],
     "fie_fullres_paste_rgb_u8": [_P, _P, _I, _I, _P, _L, _P, _L, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _L, _P],
     "fie_metrics_workspace_bytes": [_I, _I, _I],
     "fie_metrics_pairs_u8": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _L],
@@ -179,7 +183,8 @@ def lib():
             fn.argtypes = args
             fn.restype = _L if name in ("fie_groupnorm_workspace_bytes", "fie_canny_workspace_bytes", "fie_time_embed_workspace_bytes", "fie_gn_stats_bytes", "fie_debug_oplog_read", "fie_debug_tune_candidates_read", "fie_vae_decode_workspace_bytes",
                                        "fie_vae_encode_workspace_bytes", "fie_clip_text_workspace_bytes", "fie_unet_workspace_bytes", "fie_controlnet_workspace_bytes",
-                                       "fie_unet_step_cache_bytes", "fie_metrics_workspace_bytes", "fie_selfsim_workspace_bytes") else _I
+                                       "fie_unet_step_cache_bytes", "fie_metrics_workspace_bytes", "fie_selfsim_workspace_bytes",
+                                       "fie_mask_fill_workspace_bytes") else _I
         _lib.fie_last_error.restype = ctypes.c_char_p
         _lib.fie_last_error.argtypes = []
         _lib.fie_debug_last_gemm_kernel.restype = ctypes.c_char_p
@@ -971,6 +976,32 @@ class Context:
         _chk(lib().fie_mask_prep(self.h, _p(mask_l), h, w, _p(taps), (taps.numel() - 1) // 2, _p(m_px), _p(m_lat)))
         return m_px, m_lat
 
+    def mask_fill(self, src_u8, mask_l, ctl_u8=None, fill=True):
+        """The masked-content pre-pass of a masked edit (fie_mask_fill_rgb_u8).  src_u8: u8 [H, W, 3]; mask_l: u8 [H, W]
+        (hole = L >= 128); ctl_u8: None or the u8 [H, W, 3] edge map.  -> (filled, cleared): the source with the hole replaced by the push-pull
+        continuation of its surroundings (None with fill=False: nothing is computed for it), and the edge map set to 0 inside the hole (None
+        without ctl_u8).  No synchronisation; the pyramid's workspace is a fresh allocation of the caller's stream (a capture keeps it)."""
+        self.sync_stream()
+        h, w = mask_l.shape
+        if mask_l.dtype != torch.uint8 or not mask_l.is_contiguous() or tuple(src_u8.shape) != (h, w, 3) or src_u8.dtype != torch.uint8 \
+                or not src_u8.is_contiguous():
+            raise ValueError(f"mask_fill: contiguous u8 [H, W, 3] image and u8 [H, W] mask, got {tuple(src_u8.shape)} {src_u8.dtype} and "
+                             f"{tuple(mask_l.shape)} {mask_l.dtype}")
+        if ctl_u8 is not None and (tuple(ctl_u8.shape) != (h, w, 3) or ctl_u8.dtype != torch.uint8 or not ctl_u8.is_contiguous()):
+            raise ValueError(f"mask_fill: the edge map must be contiguous u8 {(h, w, 3)}, got {tuple(ctl_u8.shape)} {ctl_u8.dtype}")
+        if not fill and ctl_u8 is None:
+            raise ValueError("mask_fill: nothing to do (fill=False and no edge map)")
+        ws = out = None
+        if fill:
+            nbytes = lib().fie_mask_fill_workspace_bytes(h, w)
+            if nbytes < 0:
+                raise FieError(f"mask_fill: {h} x {w} is outside 1 .. 2^24 pixels")
+            ws = self._alloc((nbytes // 16, 4), torch.int32)
+            out = self._alloc((h, w, 3), torch.uint8)
+        cleared = self._alloc((h, w, 3), torch.uint8) if ctl_u8 is not None else None
+        _chk(lib().fie_mask_fill_rgb_u8(self.h, _p(src_u8), _p(mask_l), h, w, _p(ws), _p(out), _p(ctl_u8), _p(cleared)))
+        return out, cleared
+
     def pixels_out_composite(self, x_nhwc, source_u8, mask_px):
         """pixels_out() with the paste-back: the source bytes where mask_px == 0, the decoded ones where it is 1, the rounded blend between."""
         self.sync_stream()
@@ -1202,6 +1233,15 @@ class Context:
         _chk((lib().fie_latent_prep_src_f32 if self.f32 else lib().fie_latent_prep_src)(
             self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab), float(sqrt_1mab), _p(latents), _p(model_in),
             model_in.shape[0], _p(z0)))
+
+    def latent_prep_src_content(self, moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in, z0, mask_lat, mode):
+        """latent_prep_src() with a masked-content mode (fie_amd/mask.py: CONTENT_MODES names them): where mask_lat != 0 the initial latent is
+        the init noise itself ("latent_noise") or sqrt_1mab * noise ("latent_nothing"); everything else keeps latent_prep_src's bits."""
+        from . import mask as hmask
+        self.sync_stream()
+        _chk((lib().fie_latent_prep_src_content_f32 if self.f32 else lib().fie_latent_prep_src_content)(
+            self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab), float(sqrt_1mab), _p(latents), _p(model_in),
+            model_in.shape[0], _p(z0), _p(mask_lat), hmask.CONTENT_MODES.index(mode)))
 
     def lcm_step_masked(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
                         inv_sf, decode_in, mask_lat, z0, noise_init):

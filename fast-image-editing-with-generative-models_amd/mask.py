@@ -8,6 +8,7 @@ import math
 import numpy as np
 from PIL import Image
 
+CONTENT_MODES = ("original", "fill", "latent_noise", "latent_nothing")     # masked_content; the index is the C ABI's FIE_CONTENT_* code
 MAX_BLUR = 21          # radius ceil(3 r) <= 64: the LDS bound of fie_mask_prep
 
 
@@ -44,6 +45,15 @@ def check_args(mask_blur, paste_back, have_mask=True):
     if r > 0 and not paste_back:
         raise ValueError("mask_blur feathers the paste-back: it needs paste_back=True")
     return r
+
+
+def check_content(masked_content, have_mask=True):
+    """The argument rules of `masked_content` (what the model starts from inside the mask); returns the mode's name."""
+    if not isinstance(masked_content, str) or masked_content not in CONTENT_MODES:
+        raise ValueError(f"masked_content={masked_content!r}: one of {', '.join(repr(m) for m in CONTENT_MODES)}")
+    if masked_content != "original" and not have_mask:
+        raise ValueError(f"masked_content={masked_content!r} needs a mask")
+    return masked_content
 
 
 def blur_radius(r):

@@ -138,20 +138,22 @@ class HipImg2ImgPipeline:
 
     def prepare(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                 num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
-                mask_image=None, mask_blur=0, paste_back=True):
+                mask_image=None, mask_blur=0, paste_back=True, *, masked_content="original"):
         """`image` / `control_image`: PIL images, or u8 [H, W, 3] tensors already on the device (FastEditor.edit keeps the
         resized source and its device-side Canny map in HBM instead of bouncing them through PIL).  `mask_image` (additive, diffusers'
         name): restricts the edit to its white region -- a PIL image, a uint8 / bool [H, W] array, or a u8 [H, W]
-        device tensor, at the image's size; `mask_blur` feathers and `paste_back` (default) enables the paste-back of the source."""
+        device tensor, at the image's size; `mask_blur` feathers and `paste_back` (default) enables the paste-back of the source.
+        `masked_content` (additive; needs a mask): what the model starts from inside the mask -- "original" the source, "fill" a smooth
+        continuation of the surroundings, "latent_noise" pure noise, "latent_nothing" the zero latent plus noise."""
         return self._prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back)
+                             controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content)
 
     def _mask_job(self, mask_image, mask_blur, paste_back, h, w):
-        """Mask tensors of one image: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back).  The mask is
-        binarised / downsampled / feathered on the device (fie_mask_prep) on the current stream, in front of the job."""
+        """Mask tensors of one image: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back, the edit-size L mask
+        u8 [1, h, w]).  The mask is binarised / downsampled / feathered on the device (fie_mask_prep) on the current stream, in front of the job."""
         r = hmask.check_args(mask_blur, paste_back, mask_image is not None)
         if mask_image is None:
-            return None, None
+            return None, None, None
         if torch.is_tensor(mask_image):
             if mask_image.dim() != 2 or mask_image.dtype != torch.uint8:
                 raise ValueError("a mask tensor must be u8 [H, W]")
@@ -162,10 +164,10 @@ class HipImg2ImgPipeline:
             lm = torch.from_numpy(hmask.to_l_array(mask_image, (w, h))).to(self.ctx.device)
         with self.eager_lock:                             # the context's stream binding is shared by the threads of in-flight edits
             m_px, m_lat = self.ctx.mask_prep(lm, r)
-        return m_lat[None], (m_px[None] if paste_back else None)
+        return m_lat[None], (m_px[None] if paste_back else None), lm[None]
 
     def _prepare(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                 controlnet_conditioning_scale, generator, mask_image=None, mask_blur=0, paste_back=True):
+                 controlnet_conditioning_scale, generator, mask_image=None, mask_blur=0, paste_back=True, masked_content="original"):
         """Host side of one call: argument checks, tokenisation, RNG draws (in upstream order: posterior sample, init
         noise, one per non-final step) and the H2D copies.  Returns the device-resident job for run_device()."""
         ctx = self.ctx
@@ -179,7 +181,8 @@ class HipImg2ImgPipeline:
         w, h = size_of(image)
         if h % 8 or w % 8:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {h} and {w}.")
-        mask_lat, mask_px = self._mask_job(mask_image, mask_blur, paste_back, h, w)
+        content = hmask.check_content(masked_content, mask_image is not None)
+        mask_lat, mask_px, mask_l = self._mask_job(mask_image, mask_blur, paste_back, h, w)
         steps = self.scheduler.plan(num_inference_steps, strength)
         if not steps:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of "
@@ -213,16 +216,29 @@ class HipImg2ImgPipeline:
             guidance=float(guidance_scale), cn_scale=float(controlnet_conditioning_scale),
             time_ids=const[0], t_dev=const[1],
             noises=[self._randn((1, 4, lh, lw), generator) for _ in range(n_noise)],
-            mask_lat=mask_lat, mask_px=mask_px, mask_cfg=None if mask_lat is None else (float(mask_blur), bool(paste_back)))
+            mask_lat=mask_lat, mask_px=mask_px, mask_cfg=None if mask_lat is None else (float(mask_blur), bool(paste_back)),
+            **self._content_job(content, mask_l, mask_lat))
+
+    @staticmethod
+    def _content_job(content, mask_l, content_lat):
+        """The job entries of a masked-content mode; none with "original", whose job is what it was.  `mask_l`: the edit-size
+        L mask u8 [1, h, w], read inside the device job by the fill and the edge-map clear; `content_lat`: u8 [1, h/8 * w/8], where the latent
+        modes replace the initial latents -- the image's mask_lat, or zeros for an image of a batch that has no mask of its own."""
+        if content == "original":
+            return {}
+        out = dict(content=content, mask_l=mask_l)
+        if content in ("latent_noise", "latent_nothing"):
+            out["content_lat"] = content_lat
+        return out
 
     def prepare_batch(self, prompts, negative_prompts, images, control_images, strength=0.8, num_inference_steps=4,
                       guidance_scale=1.5, controlnet_conditioning_scale=0.5, generators=None, mask_image=None, mask_blur=0,
-                      paste_back=True):
+                      paste_back=True, *, masked_content="original"):
         """[additive] n independent edits as ONE device job (BASELINE config "batch=8"): the UNet / ControlNet / CLIP run
         at batch n * nb, the VAE per image.  Rows are image-major ([img0 uncond, img0 cond, img1 uncond, ...]); each
         image keeps its own generator, so image i of a batch draws exactly the noise a single call with that generator
         draws (upstream: a list of generators, one per prompt).  `mask_image`: None, or one mask per image (None in the
-        list = edit everywhere)."""
+        list = edit everywhere).  `masked_content`: one mode for the call (prepare()); an image without a mask is edited as ever."""
         n = len(prompts)
         if not (n == len(images) == len(control_images)) or n == 0:
             raise ValueError("prompts, images and control_images must be non-empty lists of one length")
@@ -231,11 +247,13 @@ class HipImg2ImgPipeline:
             raise ValueError(f"{len(masks)} masks for {n} images: one mask (or None) per image")
         masked = any(m is not None for m in masks)
         hmask.check_args(mask_blur, paste_back, masked)
+        content = hmask.check_content(masked_content, masked)
         negative_prompts = negative_prompts or [""] * n
         generators = generators or [None] * n
         jobs = [self._prepare(prompts[i], negative_prompts[i], images[i], control_images[i], strength, num_inference_steps,
                               guidance_scale, controlnet_conditioning_scale, generators[i], masks[i],
-                              mask_blur if masks[i] is not None else 0, paste_back) for i in range(n)]
+                              mask_blur if masks[i] is not None else 0, paste_back,
+                              content if masks[i] is not None else "original") for i in range(n)]
         if any(j["hw"] != jobs[0]["hw"] for j in jobs):
             raise ValueError("all images of a batch must have one size")
         if masked:                                        # an image without a mask edits everywhere: an all-ones mask
@@ -245,6 +263,9 @@ class HipImg2ImgPipeline:
                     j["mask_lat"] = torch.ones((1, (h // 8) * (w // 8)), device=self.ctx.device, dtype=torch.uint8)
                     j["mask_px"] = torch.ones((1, h, w), device=self.ctx.device, dtype=torch.float32) if paste_back else None
                     j["mask_cfg"] = (float(mask_blur), bool(paste_back))
+                    # no mask of its own: an empty hole -- nothing filled, no edge cleared, no latent replaced
+                    j.update(self._content_job(content, torch.zeros((1, h, w), device=self.ctx.device, dtype=torch.uint8),
+                                               torch.zeros((1, (h // 8) * (w // 8)), device=self.ctx.device, dtype=torch.uint8)))
         if n == 1:
             return jobs[0]                                # the single-image job (and its graph)
         nb, t77 = jobs[0]["nb"], jobs[0]["ids_g"].shape[1]
@@ -257,8 +278,8 @@ class HipImg2ImgPipeline:
         job["ctl_u8"] = torch.stack([j["ctl_u8"] for j in jobs])
         job["t_dev"] = [t.repeat(n, 1) for t in jobs[0]["t_dev"]]
         job["noises"] = [z for j in jobs for z in j["noises"]]          # image-major: image i owns [i*k, (i+1)*k)
-        for k in ("mask_lat", "mask_px"):
-            if job[k] is not None:
+        for k in self._MASK_KEYS:
+            if job.get(k) is not None:
                 job[k] = torch.cat([j[k] for j in jobs], dim=0)
         return job
 
@@ -296,6 +317,15 @@ class HipImg2ImgPipeline:
         n = job.get("n", 1)                               # images in this job (prepare_batch); rows are image-major
         imgs = job["img_u8"] if n > 1 else job["img_u8"][None]
         ctls = job["ctl_u8"] if n > 1 else job["ctl_u8"][None]
+        srcs = imgs                                       # what the VAE encodes; `imgs` keeps feeding the composites
+        content = job.get("content")                      # a masked-content mode other than "original" 
+        if content is not None:
+            # inside the job, on the main stream in front of the fork: a replay (and a job repeated on a finished edge map) recomputes the filled
+            # source and the cleared edge map from its own buffers; the side stream's wait below orders its edge-map embedding behind them
+            pre = [ctx.mask_fill(imgs[i], job["mask_l"][i], ctls[i], fill=content == "fill") for i in range(n)]
+            ctls = [c for _, c in pre]
+            if content == "fill":
+                srcs = [f for f, _ in pre]
         side.wait_stream(main)
         with torch.cuda.stream(side):
             if self.cpp_walks:
@@ -326,14 +356,17 @@ class HipImg2ImgPipeline:
         model_in = torch.empty((n * nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
         sf = self.cfgs["vae"]["scaling_factor"]
         for i in range(n):
-            x_img = ctx.pixels_in(imgs[i], True)
+            x_img = ctx.pixels_in(srcs[i], True)
             moments = cabi.vae_encode(self.vae, x_img) if self.cpp_walks else self.vae.encode_moments(x_img)[0]
             if mask_lat is None:
                 ctx.latent_prep(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
                                 steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb])
-            else:
+            elif job.get("content_lat") is None:
                 ctx.latent_prep_src(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
                                     steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb], z0[i])
+            else:
+                ctx.latent_prep_src_content(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
+                                            steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb], z0[i], job["content_lat"][i], content)
         next_noise = 2
         main.wait_stream(side)
         self._mark("clip+vae_encode")
@@ -455,6 +488,7 @@ class HipImg2ImgPipeline:
     MAX_FORKED_GRAPHS = 6
 
     _TENSOR_KEYS = ("ids_l", "ids_g", "eos_rows", "img_u8", "ctl_u8", "time_ids")
+    _MASK_KEYS = ("mask_lat", "mask_px", "mask_l", "content_lat")      # the last two: a masked-content mode's
 
     def run_device_graphed(self, job, slot=0):
         """run_device() replayed from a hipGraph: the ~2 500 launches of one edit are captured once per
@@ -464,7 +498,7 @@ class HipImg2ImgPipeline:
         flight on different streams of one GPU."""
         base = (job["hw"], job["nb"], tuple(st["t"] for st in job["steps"]), job["guidance"], job["cn_scale"], slot, job.get("n", 1))
         if job.get("mask_lat") is not None:              # masked: (masked, mask_blur, paste_back); an unmasked key is what it was
-            base = base + ((True,) + job["mask_cfg"],)
+            base = base + ((True,) + job["mask_cfg"] + ((job["content"],) if job.get("content") else ()),)      # + the masked-content mode, unless "original"
         # A forked graph owns extra runtime streams; past ~8 such graphs in one process new ones start sharing hardware queues
         # with their own launch stream and replay 50 % slower (measured: 82 -> 125 ms, tools/edit_ab.py).  Beyond the budget a
         # new key is captured on one stream instead (87 ms): slower than a healthy forked graph, never pathological.
@@ -506,7 +540,7 @@ class HipImg2ImgPipeline:
 
     def _tensor_keys(self, job):
         """The job tensors a graph reads from its static buffers: the mask tensors of a masked job join them."""
-        return self._TENSOR_KEYS + tuple(k for k in ("mask_lat", "mask_px") if job.get(k) is not None)
+        return self._TENSOR_KEYS + tuple(k for k in self._MASK_KEYS if job.get(k) is not None)
 
     def _capture(self, key, job, slot):
         static = dict(job)
@@ -594,14 +628,16 @@ class HipImg2ImgPipeline:
 
     def __call__(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                  num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
-                 output_type="pil", slot=0, post_check=None, mask_image=None, mask_blur=0, paste_back=True, after_device=None, **unused):
+                 output_type="pil", slot=0, post_check=None, mask_image=None, mask_blur=0, paste_back=True, after_device=None, *,
+                 masked_content="original", **unused):
         """`slot` (additive): independent hipGraph instance + stream, so that several calls may be in flight from different
         host threads on one GPU (graph mode only).  `post_check` (additive): a callable run after the result has reached the host
         (the stream is idle then); when it returns True the device-resident inputs have changed meanwhile and the device job is run
         again.  FastEditor.edit() passes the second half of its asynchronous device Canny: the edge map is computed with a fixed
         number of hysteresis rounds in front of the edit, and whether they had reached the fixed point is only looked at here --
         no host wait in front of the edit, a repeated job in the rare case that they had not.  `mask_image` / `mask_blur` / `paste_back`
-        (additive): a mask-restricted edit (prepare(); a list of masks for a batch call).  `after_device` (additive): a callable given the u8 result
+        (additive): a mask-restricted edit (prepare(); a list of masks for a batch call); `masked_content`: what it starts from inside the mask
+        (prepare()).  `after_device` (additive): a callable given the u8 result
         while it is still on the device, on the slot's stream behind the device job and outside its graph; it may queue more work there (FastEditor
         scores the edit) and whatever it returns comes back as `.extra`, complete once the image has reached the host.  A hook that returns a
         `DeviceOutput` replaces the image: its tensor(s) take the final device-to-host copy (FastEditor's full-resolution back end)."""
@@ -611,7 +647,8 @@ class HipImg2ImgPipeline:
         st.wait_stream(caller)                           # device-resident inputs may still be in flight on the caller's stream
         with torch.cuda.stream(st):
             out = self._call(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back), after_device)
+                             controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back), after_device,
+                             masked_content)
         caller.wait_stream(st)
         return out
 
@@ -644,7 +681,8 @@ class HipImg2ImgPipeline:
         return hosts[0].numpy().copy()
 
     def _call(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-              controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_args=(None, 0, True), after_device=None):
+              controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_args=(None, 0, True), after_device=None,
+              masked_content="original"):
         def run(job):
             """One device job, the caller's after_device hook behind it, then the result on the host: -> (u8 array, hook's return)."""
             out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
@@ -656,7 +694,8 @@ class HipImg2ImgPipeline:
         if isinstance(prompt, (list, tuple)):            # [additive] a batch: lists of prompts / images / generators
             job = self.prepare_batch(list(prompt), negative_prompt if isinstance(negative_prompt, (list, tuple)) else None,
                                      list(image), list(control_image), strength, num_inference_steps, guidance_scale,
-                                     controlnet_conditioning_scale, generator if isinstance(generator, (list, tuple)) else None, *mask_args)
+                                     controlnet_conditioning_scale, generator if isinstance(generator, (list, tuple)) else None, *mask_args,
+                                     masked_content=masked_content)
             arr, extra = run(job)
             if post_check is not None and post_check():
                 arr, extra = run(job)
@@ -666,7 +705,7 @@ class HipImg2ImgPipeline:
                 return types.SimpleNamespace(images=list(arr), extra=extra)
             return types.SimpleNamespace(images=[Image.fromarray(a) for a in arr], extra=extra)
         job = self.prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps,
-                           guidance_scale, controlnet_conditioning_scale, generator, *mask_args)
+                           guidance_scale, controlnet_conditioning_scale, generator, *mask_args, masked_content=masked_content)
         if output_type == "latent":
             self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
             res = job["_result"]

@@ -553,6 +553,35 @@ int fie_pixels_out_composite_f16_u8(fie_ctx* ctx, const void* src, int64_t ld_in
 int fie_pixels_out_composite_f32_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, const uint8_t* source,
                                     const float* mask, uint8_t* dst);
 
+/* ---- Masked-content modes of a mask-restricted edit: what the model starts from inside the mask.
+ *   fie_mask_fill_rgb_u8    src u8 [H, W, 3], mask_l u8 [H, W] (hole = L >= 128), any H, W >= 1 with H * W <= 2^24.
+ *      out (optional) u8 [H, W, 3]: src with the hole replaced by a smooth continuation of its surroundings, known pixels byte-identical.
+ *      The fill is a push-pull pyramid in integer arithmetic, exact to the bit (DESIGN.md section 14 defines it; tests/masked_content_oracle.py
+ *      restates it in numpy): per level the sums of the known pixels and their count over 2x2 children, sides ceil-halved to 1x1; from the top
+ *      down a cell with known pixels is their mean in 1/256 units, one without the 9-3-3-1 bilinear tap of the level above (32768 at the top).
+ *      ctl_in / ctl_out (optional, a pair) u8 [H, W, 3]: the ControlNet's edge map with every pixel of the hole set to 0.  With out == NULL
+ *      the op only clears the edge map (one launch; src and workspace may be NULL).  out may be src, ctl_out may be ctl_in.
+ *      workspace: fie_mask_fill_workspace_bytes(H, W) bytes (-1 for sizes the op refuses), 16-byte aligned: the pyramid above the image.
+ *      Launches: one per level below the first of <= 1024 cells in each direction, one single-block kernel for that level and all above
+ *      it, one for the image (11 at 1024 x 1024).  Asynchronous on the ctx stream; no block waits for another, no atomics.
+ *   fie_latent_prep_src_content   fie_latent_prep_src, then for FIE_CONTENT_LATENT_NOISE / _NOTHING a select over the latent pixels with
+ *      mask_lat != 0: latents_out = noise (the init noise itself), or sqrt_1mab * noise (add_noise of the zero latent, one f32 product);
+ *      model_in is cast from the selected value; z0_out and every value outside the mask keep fie_latent_prep_src's bits.
+ *      FIE_CONTENT_ORIGINAL / _FILL: fie_latent_prep_src alone (the fill acts on the image in front of the VAE encode). */
+#define FIE_CONTENT_ORIGINAL 0
+#define FIE_CONTENT_FILL 1
+#define FIE_CONTENT_LATENT_NOISE 2
+#define FIE_CONTENT_LATENT_NOTHING 3
+int64_t fie_mask_fill_workspace_bytes(int H, int W);
+int fie_mask_fill_rgb_u8(fie_ctx* ctx, const uint8_t* src, const uint8_t* mask_l, int H, int W, void* workspace, uint8_t* out,
+                         const uint8_t* ctl_in, uint8_t* ctl_out);
+int fie_latent_prep_src_content(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW,
+                                float scaling_factor, float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in,
+                                int copies, float* z0_out, const uint8_t* mask_lat, int mode);
+int fie_latent_prep_src_content_f32(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW,
+                                    float scaling_factor, float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in,
+                                    int copies, float* z0_out, const uint8_t* mask_lat, int mode);
+
 /* ---- Full-resolution back end of an edit: the edit-size result at the source's size, composited against the
  * source's own bytes.  res: u8 [h, w, 3], the edit-size result.  The output is H x W: up = Pillow's 8-bit LANCZOS resize of res to
  * (W, H), bit-exact (kx / bx / ksx, ky / by / ksy: the tables of fie_resize_rgb_u8 for w -> W and h -> H; a table is NULL on an axis

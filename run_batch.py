@@ -79,6 +79,10 @@ def add_mask_args(p):
     p.add_argument("--use_mask", action="store_true",
                    help="[additive] restrict each edit to the item's PIE-Bench `mask` (run-length code over the 512x512 image); the "
                         "background is pasted back from the source.  An item without a mask fails loudly")
+    p.add_argument("--masked_content", type=str, default="original", choices=["original", "fill", "latent_noise", "latent_nothing"],
+                   help="[additive] with --use_mask: what the model starts from inside the mask -- 'original' the source, 'fill' a smooth continuation "
+                        "of the surroundings (object removal), 'latent_noise' pure noise, 'latent_nothing' the zero latent plus noise; the three new "
+                        "modes also clear the edge map inside the mask")
     return p
 
 
@@ -231,6 +235,11 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     if with_metrics:
         extra = dict(extra, metrics=True)
     extra = dict(extra, **region_kwargs(args, use_mask))
+    masked_content = getattr(args, "masked_content", "original")
+    if masked_content != "original":
+        if not use_mask:
+            raise ValueError("--masked_content needs --use_mask")
+        extra = dict(extra, masked_content=masked_content)
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
     def flush():
@@ -340,6 +349,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.region == "mask" and not args.use_mask:
         parser.error("--region mask needs --use_mask")
+    if args.masked_content != "original" and not args.use_mask:
+        parser.error("--masked_content needs --use_mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets

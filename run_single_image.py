@@ -45,6 +45,10 @@ def build_parser():
     a("--mask", type=str, default=None, help="[additive] mask image (white = edit): only that region changes")
     a("--mask_blur", type=float, default=0, help="[additive] with --mask: Gaussian feather (sigma, pixels) of the paste-back seam")
     a("--no_paste_back", action="store_true", help="[additive] with --mask: blend in latent space only, no paste-back of the source")
+    a("--masked_content", type=str, default="original", choices=["original", "fill", "latent_noise", "latent_nothing"],
+      help="[additive] with --mask: what the model starts from inside the mask -- 'original' the source, 'fill' a smooth continuation of the "
+           "surroundings (object removal), 'latent_noise' pure noise, 'latent_nothing' the zero latent plus noise; the three new modes also clear "
+           "the edge map inside the mask")
     a("--resolution", type=str, default="square",
       help="[additive] output size: 'square' (1024x1024, the reference's), 'auto' (the SDXL aspect-ratio bucket nearest the source's) or WxH "
            "(multiples of 64, 512..2048, at most 1024^2 pixels)")
@@ -86,6 +90,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.region == "mask" and args.mask is None:
         parser.error("--region mask needs --mask")
+    if args.masked_content != "original" and args.mask is None:
+        parser.error("--masked_content needs --mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets
@@ -124,6 +130,9 @@ def main(argv=None):
             return
         extra.update(mask=Image.open(args.mask), mask_blur=args.mask_blur, paste_back=not args.no_paste_back)
         print(f"      Mask: {args.mask} (blur {args.mask_blur}, paste-back {'off' if args.no_paste_back else 'on'})")
+        if args.masked_content != "original":
+            extra.update(masked_content=args.masked_content)
+            print(f"      Masked content: {args.masked_content}")
     if args.resolution != "square":
         extra.update(resolution=args.resolution)
     if args.region == "mask":
