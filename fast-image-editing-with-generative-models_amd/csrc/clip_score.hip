@@ -6,19 +6,18 @@
 //   patches   fie_clip_patches_u8_*: centre crop, /255, (x - mean) / std, patchify and cast in one pass over the resized u8 image.  Row r = (image,
 //             patch) of the output is the patch in the K order of the patch-embedding weight [C, 3, ps, ps] viewed as [C, 3 ps ps]: k = (c ps + py) ps
 //             + px, so the patch convolution is a plain GEMM.  One work item = 16 contiguous output bytes (8 f16 / 4 f32: consecutive px of one
-//             patch row and channel).
+//             patch row and channel); the decode and the normalisation constants are csrc/image_ops.h's, shared with csrc/dino.hip.
 //   embed     fie_vit_embed_*: x[b, 0] = cls + pos[0], x[b, 1 + i] = patch_gemm[b, i] + pos[1 + i].  (The GEMM epilogue's residual operand cannot
 //             do it: output rows of an image are 1 + P apart, its input rows P.)
 //   score     fie_clip_score_*: one wave per (image, text) pair; lane l adds elements l, l + 64, ... of the three fp32 sums in that order, the
 //             wave adds the lanes by a fixed shuffle tree.  No atomics and no dependence on n or the pair's position; a zero norm gives 0.
-#include <algorithm>
 #include "gemm_common.h"
+#include "image_ops.h"
 
 namespace {
 
 using fie_gemm::static_for;
-
-struct ClipNorm { float mean[3], std[3]; };
+using namespace fie_img;
 
 __global__ __launch_bounds__(256) void clip_mask_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ mask, int H, int W, int MH, int MW,
                                                         const int* __restrict__ ytab, const int* __restrict__ xtab, uint8_t* __restrict__ dst, int64_t total) {
@@ -37,25 +36,19 @@ __global__ __launch_bounds__(256) void clip_mask_kernel(const uint8_t* __restric
 // items: (row = image * P + patch, 16-byte chunk of the row)
 template <typename T>
 __global__ __launch_bounds__(256) void clip_patches_kernel(const uint8_t* __restrict__ src, int H, int W, int top, int left, int grid_w, int P, int ps,
-                                                           ClipNorm nm, T* __restrict__ out, int64_t total) {
+                                                           ChannelNorm nm, T* __restrict__ out, int64_t total) {
     constexpr int E = 16 / (int)sizeof(T);
     const int K = 3 * ps * ps, nch = K / E;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = i / nch;
-        const int k0 = (int)(i - row * nch) * E;
-        const int b = (int)(row / P), p = (int)(row - (int64_t)b * P);
-        const int gy = p / grid_w, gx = p - gy * grid_w;
-        const int c = k0 / (ps * ps), rem = k0 - c * ps * ps;
-        const int py = rem / ps, px = rem - py * ps;
-        const uint8_t* s = src + (((int64_t)b * H + top + gy * ps + py) * W + left + gx * ps + px) * 3 + c;
-        const float mean = c == 0 ? nm.mean[0] : (c == 1 ? nm.mean[1] : nm.mean[2]);
-        const float std = c == 0 ? nm.std[0] : (c == 1 ? nm.std[1] : nm.std[2]);
+        const PatchItem t = patch_item<E>(i, nch, P, grid_w, ps);
+        const uint8_t* s = src + (((int64_t)t.b * H + top + t.gy * ps + t.py) * W + left + t.gx * ps + t.px) * 3 + t.c;
+        const float mean = channel_pick(nm.mean[0], nm.mean[1], nm.mean[2], t.c), std = channel_pick(nm.std[0], nm.std[1], nm.std[2], t.c);
         alignas(16) T v[E];
         static_for([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             v[j] = (T)(((float)s[j * 3] / 255.0f - mean) / std);
         }, std::make_integer_sequence<int, E>{});
-        *reinterpret_cast<uint4*>(out + row * K + k0) = *reinterpret_cast<const uint4*>(v);
+        *reinterpret_cast<uint4*>(out + t.row * K + t.k0) = *reinterpret_cast<const uint4*>(v);
     }
 }
 
@@ -92,9 +85,7 @@ __global__ __launch_bounds__(64) void clip_score_kernel(const T* __restrict__ im
         const float x = (float)a[j], y = (float)b[j];
         dot += x * y; na += x * x; nb += y * y;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        dot += __shfl_down(dot, o, 64); na += __shfl_down(na, o, 64); nb += __shfl_down(nb, o, 64);
-    }
+    dot = wave_sum(dot); na = wave_sum(na); nb = wave_sum(nb);
     if (lane == 0) {
         const float den = sqrtf(na) * sqrtf(nb);
         const float s = den > 0.f ? 100.0f * (dot / den) : 0.f;
@@ -102,8 +93,6 @@ __global__ __launch_bounds__(64) void clip_score_kernel(const T* __restrict__ im
         out[pair * 2 + 1] = fmaxf(s, 0.f);
     }
 }
-
-inline int blocks_for(int64_t items) { return (int)std::min<int64_t>((items + 255) / 256, 4096); }
 
 template <typename T>
 int clip_patches_t(fie_ctx* ctx, const uint8_t* src, int n, int H, int W, int top, int left, int size, int patch, const float* mean, const float* std,
@@ -115,15 +104,12 @@ int clip_patches_t(fie_ctx* ctx, const uint8_t* src, int n, int H, int W, int to
     FIE_REQUIRE(top >= 0 && left >= 0 && top + size <= H && left + size <= W, "fie_clip_patches_u8: crop %d x %d at (%d, %d) leaves the %d x %d image", size, size,
                 top, left, H, W);
     FIE_REQUIRE((uintptr_t)out % 16 == 0, "fie_clip_patches_u8: the output must be 16-byte aligned");
-    ClipNorm nm;
-    for (int c = 0; c < 3; ++c) {
-        FIE_REQUIRE(std[c] != 0.f, "fie_clip_patches_u8: image_std[%d] is 0", c);
-        nm.mean[c] = mean[c]; nm.std[c] = std[c];
-    }
+    ChannelNorm nm;
+    if (const int rc = channel_norm("fie_clip_patches_u8", mean, std, &nm)) return rc;
     const int g = size / patch, P = g * g;
     const int64_t total = (int64_t)n * P * (3 * patch * patch / (16 / (int)sizeof(T)));
     FIE_DESC(ctx, "clip_patches n=%d %dx%d crop=%d@(%d,%d) patch=%d", n, H, W, size, top, left, patch);
-    fie_launch(ctx, clip_patches_kernel<T>, dim3(blocks_for(total)), dim3(256), 0, src, H, W, top, left, g, P, patch, nm, (T*)out, total);
+    fie_launch(ctx, clip_patches_kernel<T>, dim3(grid_1d(total, kPatchBlocks)), dim3(256), 0, src, H, W, top, left, g, P, patch, nm, (T*)out, total);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
@@ -135,7 +121,7 @@ int vit_embed_t(fie_ctx* ctx, const void* patches, const void* cls, const void* 
     FIE_REQUIRE(((uintptr_t)patches | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)out) % 16 == 0, "fie_vit_embed: operands must be 16-byte aligned");
     const int64_t total = (int64_t)n * (P + 1) * (C / 8);
     FIE_DESC(ctx, "vit_embed n=%d tokens=%d C=%d", n, P + 1, C);
-    fie_launch(ctx, vit_embed_kernel<T>, dim3(blocks_for(total)), dim3(256), 0, (const T*)patches, (const T*)cls, (const T*)pos, P, C, (T*)out, total);
+    fie_launch(ctx, vit_embed_kernel<T>, dim3(grid_1d(total, kPatchBlocks)), dim3(256), 0, (const T*)patches, (const T*)cls, (const T*)pos, P, C, (T*)out, total);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
@@ -162,7 +148,7 @@ int fie_clip_mask_rgb_u8(fie_ctx* ctx, const uint8_t* src, const uint8_t* mask, 
     FIE_REQUIRE((MH == H || ytab) && (MW == W || xtab), "fie_clip_mask_rgb_u8: a %d x %d mask for a %d x %d image needs the NEAREST index tables", MH, MW, H, W);
     const int64_t total = (int64_t)n * H * W;
     FIE_DESC(ctx, "clip_mask n=%d %dx%d mask %dx%d", n, H, W, MH, MW);
-    fie_launch(ctx, clip_mask_kernel, dim3(blocks_for(total)), dim3(256), 0, src, mask, H, W, MH, MW, ytab, xtab, dst, total);
+    fie_launch(ctx, clip_mask_kernel, dim3(grid_1d(total, kPatchBlocks)), dim3(256), 0, src, mask, H, W, MH, MW, ytab, xtab, dst, total);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }

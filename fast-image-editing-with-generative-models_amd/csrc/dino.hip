@@ -4,7 +4,7 @@
 //             horizontal pass first -- then (x - mean) / std, patchify and cast.  Taps and bounds come from the host (fie_amd/resize.py:
 //             aa_coefficients).  Launch 1: the horizontal pass of u8 / 255 into an fp32 [n, H, OW, 3] scratch image.  Launch 2: vertical pass,
 //             normalisation, patchify and cast in one; its work item is 16 contiguous output bytes, as in fie_clip_patches_u8_*, and its rows are in
-//             the same K order.  Up-scaling and the identity size run through the same tables (identity: taps {1, 0}, exact).
+//             the same K order (csrc/image_ops.h: patch_item, one decode for both).  Up-scaling and the identity size run through the same tables (identity: taps {1, 0}, exact).
 //   selfsim   fie_selfsim_mse_*: mean over T x T of (S_b - S_a)^2 with S = K K^T / max(|k_i| |k_j|, 1e-8), the T x T matrices never stored.
 //             Launch 1: row norms, one wave per key row, fp32 sums in a fixed order.  Launch 2: one block per 64 x 64 tile (i <= j: S is symmetric,
 //             tiles above the diagonal count twice) of one pair; each of its four waves owns 32 x 32 entries of BOTH Gram tiles as 2 x 2 MFMA
@@ -14,16 +14,13 @@
 //             fp64: lanes by a shuffle tree, the four waves in wave order -> ONE partial per block, an ordinary store.  Launch 3: one block per pair adds
 //             the partials in tile order in fp64 and divides by T^2.  No atomics: a pair's bits depend neither on n nor on its position; both
 //             Gram tiles run the same instruction sequence, so an identical pair gives exactly 0.
-#include <algorithm>
 #include "gemm_common.h"
+#include "image_ops.h"
 
 namespace {
 
 using fie_gemm::static_for;
-
-struct DinoNorm { float mean[3], std[3]; };
-
-inline int blocks_for(int64_t items) { return (int)std::min<int64_t>((items + 255) / 256, 4096); }
+using namespace fie_img;
 
 // items: (image, y, ox, c) of the scratch image [n, H, OW, 3]
 __global__ __launch_bounds__(256) void dino_hpass_kernel(const uint8_t* __restrict__ src, int H, int W, int OW, const float* __restrict__ wx,
@@ -48,22 +45,16 @@ __global__ __launch_bounds__(256) void dino_hpass_kernel(const uint8_t* __restri
 // items: (row = image * P + patch, 16-byte chunk of the row)
 template <typename T>
 __global__ __launch_bounds__(256) void dino_vpass_patches_kernel(const float* __restrict__ tmp, int H, int OW, const float* __restrict__ wy,
-                                                                 const int* __restrict__ by, int ksy, int grid_w, int P, int ps, DinoNorm nm,
+                                                                 const int* __restrict__ by, int ksy, int grid_w, int P, int ps, ChannelNorm nm,
                                                                  T* __restrict__ out, int64_t total) {
     constexpr int E = 16 / (int)sizeof(T);
     const int K = 3 * ps * ps, nch = K / E;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = i / nch;
-        const int k0 = (int)(i - row * nch) * E;
-        const int b = (int)(row / P), p = (int)(row - (int64_t)b * P);
-        const int gy = p / grid_w, gx = p - gy * grid_w;
-        const int c = k0 / (ps * ps), rem = k0 - c * ps * ps;
-        const int py = rem / ps, px = rem - py * ps;
-        const int oy = gy * ps + py, ox = gx * ps + px;
+        const PatchItem it = patch_item<E>(i, nch, P, grid_w, ps);
+        const int b = it.b, c = it.c, oy = it.gy * ps + it.py, ox = it.gx * ps + it.px;
         const int y0 = by[oy * 2], cnt = min(by[oy * 2 + 1], ksy);
         const float* w = wy + (int64_t)oy * ksy;
-        const float mean = c == 0 ? nm.mean[0] : (c == 1 ? nm.mean[1] : nm.mean[2]);
-        const float std = c == 0 ? nm.std[0] : (c == 1 ? nm.std[1] : nm.std[2]);
+        const float mean = channel_pick(nm.mean[0], nm.mean[1], nm.mean[2], c), std = channel_pick(nm.std[0], nm.std[1], nm.std[2], c);
         float t[E];
         for (int j = 0; j < cnt; ++j) {
             const float* s = tmp + (((int64_t)b * H + min(y0 + j, H - 1)) * OW + ox) * 3 + c;
@@ -78,18 +69,12 @@ __global__ __launch_bounds__(256) void dino_vpass_patches_kernel(const float* __
             constexpr int e = decltype(ec)::value;
             v[e] = (T)(((cnt > 0 ? t[e] : 0.f) - mean) / std);
         }, std::make_integer_sequence<int, E>{});
-        *reinterpret_cast<uint4*>(out + row * K + k0) = *reinterpret_cast<const uint4*>(v);
+        *reinterpret_cast<uint4*>(out + it.row * K + it.k0) = *reinterpret_cast<const uint4*>(v);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- self-similarity MSE
 constexpr int kTile = 64;                  // entries of S per block edge; a wave owns 32 x 32 of them
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // one wave per key row (rows of both sides of all pairs: grid = 2 * n * T / 4 blocks of 4 waves); norms [2][n * T]
 template <typename T>
@@ -104,7 +89,7 @@ __global__ __launch_bounds__(256) void selfsim_norm_kernel(const T* __restrict__
         const float x = (float)k[j];
         s += x * x;
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    s = wave_sum(s);
     if (lane == 0) norms[r] = sqrtf(s);
 }
 
@@ -233,19 +218,16 @@ int dino_patches_t(fie_ctx* ctx, const uint8_t* src, int n, int H, int W, int OH
     FIE_REQUIRE(patch > 0 && patch % 8 == 0 && OH % patch == 0 && OW % patch == 0,
                 "fie_dino_patches_u8: resized size %d x %d / patch size %d: the patch size must divide both edges and be a multiple of 8", OH, OW, patch);
     FIE_REQUIRE((uintptr_t)out % 16 == 0 && (uintptr_t)tmp % 4 == 0, "fie_dino_patches_u8: the output must be 16-byte aligned");
-    DinoNorm nm;
-    for (int c = 0; c < 3; ++c) {
-        FIE_REQUIRE(std[c] != 0.f, "fie_dino_patches_u8: image_std[%d] is 0", c);
-        nm.mean[c] = mean[c]; nm.std[c] = std[c];
-    }
+    ChannelNorm nm;
+    if (const int rc = channel_norm("fie_dino_patches_u8", mean, std, &nm)) return rc;
     const int gw = OW / patch, P = (OH / patch) * gw;
     const int64_t t1 = (int64_t)n * H * OW * 3;
     const int64_t t2 = (int64_t)n * P * (3 * patch * patch / (16 / (int)sizeof(T)));
     FIE_DESC(ctx, "dino_hpass n=%d %dx%d -> width %d taps=%d", n, H, W, OW, ksx);
-    fie_launch(ctx, dino_hpass_kernel, dim3(blocks_for(t1)), dim3(256), 0, src, H, W, OW, wx, bx, ksx, tmp, t1);
+    fie_launch(ctx, dino_hpass_kernel, dim3(grid_1d(t1, kPatchBlocks)), dim3(256), 0, src, H, W, OW, wx, bx, ksx, tmp, t1);
     FIE_LAUNCH_CHECK();
     FIE_DESC(ctx, "dino_vpass_patches n=%d %dx%d -> %dx%d taps=%d patch=%d", n, H, OW, OH, OW, ksy, patch);
-    fie_launch(ctx, dino_vpass_patches_kernel<T>, dim3(blocks_for(t2)), dim3(256), 0, (const float*)tmp, H, OW, wy, by, ksy, gw, P, patch, nm, (T*)out, t2);
+    fie_launch(ctx, dino_vpass_patches_kernel<T>, dim3(grid_1d(t2, kPatchBlocks)), dim3(256), 0, (const float*)tmp, H, OW, wy, by, ksy, gw, P, patch, nm, (T*)out, t2);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }

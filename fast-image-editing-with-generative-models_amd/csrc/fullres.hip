@@ -1,16 +1,18 @@
 // Full-resolution back end of an edit (include/fie.h: fie_fullres_paste_rgb_u8): the edit-size u8 result goes to the
 // source's resolution (Pillow's 8-bit LANCZOS, as csrc/resize.hip) and is composited there against the source's own bytes through the
-// binarised, optionally feathered source-size mask (the arithmetic of mask_prep_kernel and pixels_out_composite_kernel, csrc/mask.hip).
+// binarised, optionally feathered source-size mask (as mask_prep_kernel and pixels_out_composite_kernel, csrc/mask.hip).  The resample, the
+// feather and the blend are the functions of csrc/image_ops.h that those kernels call too.
 //   launch 1   the horizontal resample of the result into tmp [h, W, 3] (fie_resize_rgb_u8 on one axis), when the width changes;
 //   launch 2   one kernel over 64 x 16 output tiles: binary mask + clamped R-halo in LDS, the two feather passes, the vertical resample of
 //              the tile's columns from tmp, the blend, the store.
 // Neither the f32 mask nor the up-sampled image exists in memory at the output's resolution: per output pixel the kernel reads 1 mask byte,
 // 3 source bytes and the taps' rows of tmp, and writes 3 bytes.  A tile whose staged mask (halo included) is all zero copies the source.
-#include "fie_internal.h"
+#include "image_ops.h"
 
 namespace {
 
-constexpr int kPrecisionBits = 32 - 8 - 2;      // Pillow's 8-bit resample (csrc/resize.hip)
+using namespace fie_img;
+
 constexpr int kTW = 64, kTH = 16;               // output pixels per workgroup: one wave per tile row, four rows per wave
 constexpr int kMaxRadius = 64;                  // LDS at R = 64: 144 x 192 mask bytes + 144 x 64 floats = 63 KB
 constexpr int kRowBytes = kTW * 3;
@@ -69,28 +71,14 @@ __global__ __launch_bounds__(256) void fullres_paste_kernel(FullresArgs p) {
     uint8_t* dst_tile = p.dst + (int64_t)y0 * p.dst_pitch + (int64_t)x0 * 3;
 
     if (p.mask) {
-        int any = 0;
-        for (int i = tid; i < BW * BH; i += 256) {
-            const int r = i / BW, c = i - r * BW;
-            const int gy = min(max(y0 - R + r, 0), p.H - 1), gx = min(max(x0 - R + c, 0), p.W - 1);
-            const uint8_t b = p.mask[(int64_t)gy * p.mask_pitch + gx] >= 128 ? 1 : 0;
-            bin[i] = b;
-            any |= b;
-        }
-        any = __syncthreads_or(any);
-        if (!any) {                               // block-uniform: the feather is 0 on the whole tile, the output is the source
+        // block-uniform: no bit staged (halo included) means the feather is 0 on the whole tile, the output is the source
+        if (!__syncthreads_or(feather_stage<kTW, kTH>(bin, p.mask, p.mask_pitch, p.H, p.W, x0, y0, R, tid))) {
             tile_io<false>(io, src_tile, p.source_pitch, rows, nb, tid);
             __syncthreads();
             tile_io<true>(io, dst_tile, p.dst_pitch, rows, nb, tid);
             return;
         }
-        for (int i = tid; i < BH * kTW; i += 256) {      // mask_prep_kernel's horizontal pass: taps summed k = 0 .. 2R in f32
-            const int r = i / kTW, c = i - r * kTW;
-            const uint8_t* row = bin + r * BW + c;
-            float s = 0.f;
-            for (int k = 0; k <= 2 * R; ++k) s += p.taps[k] * (float)row[k];
-            hrow[i] = s;
-        }
+        feather_hpass<kTW, kTH>(hrow, bin, p.taps, R, tid);
         __syncthreads();
         tile_io<false>(io, src_tile, p.source_pitch, rows, nb, tid);
         __syncthreads();
@@ -102,27 +90,18 @@ __global__ __launch_bounds__(256) void fullres_paste_kernel(FullresArgs p) {
         if (y >= p.H || x >= p.W) continue;
         float m = 1.f;
         if (p.mask) {
-            m = 0.f;
-            for (int k = 0; k <= 2 * R; ++k) m += p.taps[k] * hrow[(ty + k) * kTW + tx];
+            m = feather_vsum<kTW>(hrow, p.taps, R, tx, ty);
             if (m <= 0.f) continue;               // io already holds the source bytes
         }
         int up[3];
-        if (p.ky) {                               // resize_v_kernel's arithmetic on this pixel's column
+        if (p.ky) {                               // the vertical pass of this pixel's column, as resize_v_kernel runs it
             const int ymin = p.by[2 * y], n = p.by[2 * y + 1];
             const int* k = p.ky + (int64_t)y * p.ksy;
             const uint8_t* col = p.vin + ((int64_t)ymin * p.W + x) * 3;
-            int s[3] = {1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1)};
-            for (int t = 0; t < n; ++t) {
-                const int w = k[t];
-                const uint8_t* px = col + (int64_t)t * p.W * 3;
+            int s[3] = {kResampleHalf, kResampleHalf, kResampleHalf};
+            for (int t = 0; t < n; ++t) resample_tap<3>(s, col + (int64_t)t * p.W * 3, k[t]);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) s[c] += px[c] * w;
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int v = s[c] >> kPrecisionBits;
-                up[c] = v < 0 ? 0 : (v > 255 ? 255 : v);
-            }
+            for (int c = 0; c < 3; ++c) up[c] = resample_clip8(s[c]);
         } else {
             const uint8_t* px = p.vin + ((int64_t)y * p.W + x) * 3;
 #pragma unroll
@@ -130,10 +109,7 @@ __global__ __launch_bounds__(256) void fullres_paste_kernel(FullresArgs p) {
         }
         uint8_t* o = io + ty * kRowBytes + tx * 3;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float d = (float)up[c], s = (float)o[c];
-            o[c] = m >= 1.f ? (uint8_t)up[c] : (uint8_t)rintf(m * d + (1.f - m) * s);      // pixels_out_composite_kernel's blend
-        }
+        for (int c = 0; c < 3; ++c) o[c] = blend_u8(m, (float)up[c], o[c]);
     }
     __syncthreads();
     tile_io<true>(io, dst_tile, p.dst_pitch, rows, nb, tid);

@@ -6,16 +6,19 @@
 //   LCM step    today's K8 plus, per latent pixel, lat = m_lat ? lat : (sab_prev z0 + s1mab_prev n_init), or z0 on the last step;
 //   composite   today's pixels_out, then the source u8 where m == 0, the decoded byte where m == 1, rint(m d + (1-m) src) between.
 // lcm_step_kernel, latent_prep_kernel and pixels_out_kernel (pointwise.hip) are untouched: an unmasked edit launches exactly what it did.
-#include "fie_internal.h"
+#include "image_ops.h"
 
 namespace {
+
+using namespace fie_img;
 
 constexpr int kMaskTile = 16;          // 16 x 16 output pixels per workgroup
 constexpr int kMaskMaxRadius = 64;     // LDS: (16 + 2R)^2 bytes of binary mask + (16 + 2R) x 16 floats of the horizontal pass
 
 // One launch: binarise, latent downsample and the feather (R = 0: taps = {1}, m_px is the binary mask).  The binary mask of the tile
 // and its clamped R-halo is staged in LDS; the horizontal pass runs over every staged row, the vertical pass over its result: the
-// separable filter in the order a host restatement computes it (taps summed k = 0 .. 2R in f32).
+// separable filter in the order a host restatement computes it (taps summed k = 0 .. 2R in f32): csrc/image_ops.h's feather, which the
+// fused paste of csrc/fullres.hip runs on its own tiles.
 __global__ __launch_bounds__(256) void mask_prep_kernel(const uint8_t* __restrict__ L, int H, int W, const float* __restrict__ taps, int R,
                                                         float* __restrict__ m_px, uint8_t* __restrict__ m_lat) {
     extern __shared__ __attribute__((aligned(16))) uint8_t mp_smem[];
@@ -23,26 +26,14 @@ __global__ __launch_bounds__(256) void mask_prep_kernel(const uint8_t* __restric
     uint8_t* bin = mp_smem;                                              // [T][T]
     float* hrow = reinterpret_cast<float*>(mp_smem + ((T * T + 15) & ~15));   // [T][16]
     const int x0 = blockIdx.x * kMaskTile, y0 = blockIdx.y * kMaskTile, tid = threadIdx.x;
-    for (int i = tid; i < T * T; i += 256) {
-        const int r = i / T, c = i - r * T;
-        const int gy = min(max(y0 - R + r, 0), H - 1), gx = min(max(x0 - R + c, 0), W - 1);
-        bin[i] = L[(int64_t)gy * W + gx] >= 128 ? 1 : 0;
-    }
+    feather_stage<kMaskTile, kMaskTile>(bin, L, W, H, W, x0, y0, R, tid);
     __syncthreads();
-    for (int i = tid; i < T * kMaskTile; i += 256) {
-        const int r = i / kMaskTile, c = i - r * kMaskTile;
-        const uint8_t* row = bin + r * T + c;
-        float s = 0.f;
-        for (int k = 0; k <= 2 * R; ++k) s += taps[k] * (float)row[k];
-        hrow[i] = s;
-    }
+    feather_hpass<kMaskTile, kMaskTile>(hrow, bin, taps, R, tid);
     __syncthreads();
     const int ty = tid / kMaskTile, tx = tid - ty * kMaskTile;
     const int y = y0 + ty, x = x0 + tx;
     if (y >= H || x >= W) return;
-    float s = 0.f;
-    for (int k = 0; k <= 2 * R; ++k) s += taps[k] * hrow[(ty + k) * kMaskTile + tx];
-    m_px[(int64_t)y * W + x] = s;
+    m_px[(int64_t)y * W + x] = feather_vsum<kMaskTile>(hrow, taps, R, tx, ty);
     if ((y & 7) == 0 && (x & 7) == 0) m_lat[(int64_t)(y >> 3) * (W >> 3) + (x >> 3)] = bin[(ty + R) * T + tx + R];
 }
 
@@ -148,8 +139,7 @@ __global__ void pixels_out_composite_kernel(const T* src, int64_t ld, int64_t nq
                 float x = (float)src[i * ld + c] * 0.5f + 0.5f;
                 x = fminf(fmaxf(x, 0.f), 1.f);
                 const float d = x * 255.0f;
-                const float s = (float)sb[p * 3 + c];
-                ob[p * 3 + c] = m <= 0.f ? sb[p * 3 + c] : (uint8_t)rintf(m >= 1.f ? d : m * d + (1.f - m) * s);
+                ob[p * 3 + c] = blend_u8(m, d, sb[p * 3 + c]);
             }
         }
         uint32_t* dw = reinterpret_cast<uint32_t*>(dst + q * 12);
@@ -157,17 +147,12 @@ __global__ void pixels_out_composite_kernel(const T* src, int64_t ld, int64_t nq
     }
 }
 
-inline unsigned grid_for(int64_t n) {
-    int64_t g = (n + 255) / 256;
-    return (unsigned)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
-}
-
 template <typename T>
 int latent_prep_src_t(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW, float sf, float sqrt_ab,
                       float sqrt_1mab, float* latents_out, void* model_in, int copies, float* z0_out) {
     FIE_REQUIRE(ctx && moments && eps_post && noise && latents_out && model_in && z0_out && HW > 0 && copies > 0,
                 "fie_latent_prep_src: bad argument");
-    fie_launch(ctx, latent_prep_src_kernel<T>, dim3(grid_for(HW)), dim3(256), 0, (const T*)moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab,
+    fie_launch(ctx, latent_prep_src_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, (const T*)moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab,
                latents_out, (T*)model_in, copies, z0_out);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
@@ -184,7 +169,7 @@ int lcm_step_masked_t(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, flo
     FIE_REQUIRE(sqrt_ab_t > 0.f, "fie_lcm_step_masked: sqrt(alpha_bar_t) must be positive");
     LcmMaskedArgs<T> p = {(const T*)eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out,
                           sqrt_ab_prev, sqrt_1mab_prev, (T*)model_in, copies, inv_scaling, (T*)decode_in, mask_lat, z0, noise_init};
-    fie_launch(ctx, lcm_step_masked_kernel<T>, dim3(grid_for(HW)), dim3(256), 0, p);
+    fie_launch(ctx, lcm_step_masked_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, p);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
@@ -195,7 +180,7 @@ int pixels_out_composite_t(fie_ctx* ctx, const void* src, int64_t ld_in, int H, 
     const int64_t n = (int64_t)H * W;
     FIE_REQUIRE(n % 4 == 0, "fie_pixels_out_composite: H*W must be a multiple of 4");
     FIE_REQUIRE(((uintptr_t)source | (uintptr_t)dst) % 4 == 0 && (uintptr_t)mask % 16 == 0, "fie_pixels_out_composite: misaligned buffer");
-    fie_launch(ctx, pixels_out_composite_kernel<T>, dim3(grid_for(n / 4)), dim3(256), 0, (const T*)src, ld_in, n / 4, source, mask, dst);
+    fie_launch(ctx, pixels_out_composite_kernel<T>, dim3(grid_1d(n / 4, kPointwiseBlocks)), dim3(256), 0, (const T*)src, ld_in, n / 4, source, mask, dst);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }

@@ -7,7 +7,7 @@
 //   latent prep   fie_latent_prep_src, then a select over the latent pixels inside the mask: the init noise itself, or sqrt_1mab * noise.
 // Levels are ordered by kernel boundaries (and, inside the one-block kernel that owns every level of <= 1024 cells, by __syncthreads):
 // no block waits for another, nothing synchronises with the host, every launch goes through fie_launch.
-#include "fie_internal.h"
+#include "image_ops.h"
 
 namespace {
 
@@ -191,10 +191,8 @@ __global__ __launch_bounds__(256) void latent_content_kernel(const uint8_t* __re
     }
 }
 
-inline unsigned fill_grid(int64_t n) {
-    const int64_t g = (n + 255) / 256;
-    return (unsigned)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
-}
+using fie_img::grid_1d;
+using fie_img::kPointwiseBlocks;
 
 template <typename T>
 int latent_prep_src_content_t(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW, float sf, float sqrt_ab,
@@ -204,7 +202,7 @@ int latent_prep_src_content_t(fie_ctx* ctx, const void* moments, const float* ep
     const int rc = sizeof(T) == 2 ? fie_latent_prep_src(ctx, moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab, latents_out, model_in, copies, z0_out)
                                   : fie_latent_prep_src_f32(ctx, moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab, latents_out, model_in, copies, z0_out);
     if (rc != FIE_OK || mode < FIE_CONTENT_LATENT_NOISE) return rc;
-    fie_launch(ctx, latent_content_kernel<T>, dim3(fill_grid(HW)), dim3(256), 0, mask_lat, noise, HW, sqrt_1mab,
+    fie_launch(ctx, latent_content_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, mask_lat, noise, HW, sqrt_1mab,
                mode == FIE_CONTENT_LATENT_NOTHING ? 1 : 0, latents_out, (T*)model_in, copies);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
@@ -231,22 +229,22 @@ int fie_mask_fill_rgb_u8(fie_ctx* ctx, const uint8_t* src, const uint8_t* mask_l
     const FillPlan p = fill_plan(H, W);
     uint4* ws = (uint4*)workspace;
     if (out && p.K > 0) {
-        fie_launch(ctx, fill_push0_kernel, dim3(fill_grid((int64_t)p.h[1] * p.w[1])), dim3(256), 0, src, mask_l, H, W, ws + p.off[1], p.h[1], p.w[1]);
+        fie_launch(ctx, fill_push0_kernel, dim3(grid_1d((int64_t)p.h[1] * p.w[1], kPointwiseBlocks)), dim3(256), 0, src, mask_l, H, W, ws + p.off[1], p.h[1], p.w[1]);
         FIE_LAUNCH_CHECK();
         for (int k = 2; k <= p.kt; ++k) {
-            fie_launch(ctx, fill_push_kernel, dim3(fill_grid((int64_t)p.h[k] * p.w[k])), dim3(256), 0, (const uint4*)(ws + p.off[k - 1]), p.h[k - 1],
+            fie_launch(ctx, fill_push_kernel, dim3(grid_1d((int64_t)p.h[k] * p.w[k], kPointwiseBlocks)), dim3(256), 0, (const uint4*)(ws + p.off[k - 1]), p.h[k - 1],
                        p.w[k - 1], ws + p.off[k], p.h[k], p.w[k]);
             FIE_LAUNCH_CHECK();
         }
         fie_launch(ctx, fill_top_kernel, dim3(1), dim3(256), 0, ws + p.off[p.kt], p.h[p.kt], p.w[p.kt]);
         FIE_LAUNCH_CHECK();
         for (int k = p.kt - 1; k >= 1; --k) {
-            fie_launch(ctx, fill_resolve_kernel, dim3(fill_grid((int64_t)p.h[k] * p.w[k])), dim3(256), 0, ws + p.off[k], p.h[k], p.w[k],
+            fie_launch(ctx, fill_resolve_kernel, dim3(grid_1d((int64_t)p.h[k] * p.w[k], kPointwiseBlocks)), dim3(256), 0, ws + p.off[k], p.h[k], p.w[k],
                        (const uint4*)(ws + p.off[k + 1]), p.h[k + 1], p.w[k + 1]);
             FIE_LAUNCH_CHECK();
         }
     }
-    fie_launch(ctx, fill_final_kernel, dim3(fill_grid((int64_t)H * W)), dim3(256), 0, src, mask_l, H, W,
+    fie_launch(ctx, fill_final_kernel, dim3(grid_1d((int64_t)H * W, kPointwiseBlocks)), dim3(256), 0, src, mask_l, H, W,
                (const uint4*)(out && p.K > 0 ? ws + p.off[1] : nullptr), p.K > 0 ? p.h[1] : 0, p.K > 0 ? p.w[1] : 0, out, ctl_in, ctl_out);
     FIE_LAUNCH_CHECK();
     return FIE_OK;

@@ -11,7 +11,7 @@
 //              store.  A second launch of one block per (pair, variant) adds the partials in tile order.  No atomics, so neither block order
 //              nor the batch a pair travels in can move a bit.
 // LDS: 2 x 5 292 B of bytes + 2 x 7 056 B of floats + 26 880 B of row moments = 51.6 KB, three blocks per CU.
-#include "fie_internal.h"
+#include "image_ops.h"
 
 namespace {
 
@@ -30,16 +30,7 @@ __device__ __forceinline__ int reflect_clamp(int i, int n) {
     return min(max(i, 0), n - 1);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
+using fie_img::wave_sum;
 
 // grid (tiles_x, tiles_y, n * nvar); variant 1 = the background pair
 __global__ __launch_bounds__(256) void metrics_tile_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, const uint8_t* __restrict__ M,

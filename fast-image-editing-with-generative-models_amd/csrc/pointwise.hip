@@ -1,7 +1,7 @@
 // K7-K10, K12-embed: small element-wise kernels of the denoising loop (include/fie.h).  All are latency/HBM-bound;
 // scheduler scalars are computed on the host in fp32/fp64 and passed by value (c_skip ~ 1e-8 underflows
 // in fp16, so the LCM update is done in fp32 on an fp32 master copy of the latents).
-#include "fie_internal.h"
+#include "image_ops.h"
 
 namespace {
 
@@ -231,10 +231,8 @@ __global__ void lcm_step_kernel(LcmArgs<T> p) {
     }
 }
 
-inline unsigned grid_for(int64_t n) {
-    int64_t g = (n + 255) / 256;
-    return (unsigned)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
-}
+using fie_img::grid_1d;
+using fie_img::kPointwiseBlocks;
 
 template <typename T>
 int sinusoid_t(fie_ctx* ctx, const float* vals, int B, int nvals, int dim, void* out, int64_t ld_out, int col0) {
@@ -250,7 +248,7 @@ template <typename T>
 int clip_embed_t(fie_ctx* ctx, const int32_t* ids, int B, int Tn, int C, const void* tok, const void* pos, void* out) {
     FIE_REQUIRE(ctx && ids && tok && pos && out, "fie_clip_embed: NULL argument");
     FIE_REQUIRE(B > 0 && Tn > 0 && C > 0 && C % 8 == 0, "fie_clip_embed: bad shape");
-    fie_launch(ctx, clip_embed_kernel<T>, dim3(grid_for((int64_t)B * Tn * C / 8)), dim3(256), 0, ids, B * Tn, Tn, C, (const T*)tok, (const T*)pos, (T*)out);
+    fie_launch(ctx, clip_embed_kernel<T>, dim3(grid_1d((int64_t)B * Tn * C / 8, kPointwiseBlocks)), dim3(256), 0, ids, B * Tn, Tn, C, (const T*)tok, (const T*)pos, (T*)out);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
@@ -259,7 +257,7 @@ template <typename T>
 int pixels_in_t(fie_ctx* ctx, const uint8_t* src, int H, int W, int normalize, void* dst, int copies) {
     FIE_REQUIRE(ctx && src && dst && H > 0 && W > 0 && copies > 0, "fie_pixels_in: bad argument");
     const int64_t n = (int64_t)H * W;
-    fie_launch(ctx, pixels_in_kernel<T>, dim3(grid_for(n)), dim3(256), 0, src, n, normalize, (T*)dst, copies);
+    fie_launch(ctx, pixels_in_kernel<T>, dim3(grid_1d(n, kPointwiseBlocks)), dim3(256), 0, src, n, normalize, (T*)dst, copies);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
@@ -268,7 +266,7 @@ template <typename T>
 int pixels_out_t(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, uint8_t* dst) {
     FIE_REQUIRE(ctx && src && dst && H > 0 && W > 0 && ld_in >= 3, "fie_pixels_out: bad argument");
     const int64_t n = (int64_t)H * W;
-    fie_launch(ctx, pixels_out_kernel<T>, dim3(grid_for(n)), dim3(256), 0, (const T*)src, ld_in, n, dst);
+    fie_launch(ctx, pixels_out_kernel<T>, dim3(grid_1d(n, kPointwiseBlocks)), dim3(256), 0, (const T*)src, ld_in, n, dst);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
@@ -277,7 +275,7 @@ template <typename T>
 int latent_prep_t(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW, float sf, float sqrt_ab,
                   float sqrt_1mab, float* latents_out, void* model_in, int copies) {
     FIE_REQUIRE(ctx && moments && eps_post && noise && latents_out && model_in && HW > 0 && copies > 0, "fie_latent_prep: bad argument");
-    fie_launch(ctx, latent_prep_kernel<T>, dim3(grid_for(HW)), dim3(256), 0, (const T*)moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab, latents_out, (T*)model_in, copies);
+    fie_launch(ctx, latent_prep_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, (const T*)moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab, latents_out, (T*)model_in, copies);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
@@ -292,7 +290,7 @@ int lcm_step_t(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guid
     FIE_REQUIRE(sqrt_ab_t > 0.f, "fie_lcm_step: sqrt(alpha_bar_t) must be positive");
     LcmArgs<T> p = {(const T*)eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out,
                     sqrt_ab_prev, sqrt_1mab_prev, (T*)model_in, copies, inv_scaling, (T*)decode_in};
-    fie_launch(ctx, lcm_step_kernel<T>, dim3(grid_for(HW)), dim3(256), 0, p);
+    fie_launch(ctx, lcm_step_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, p);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }

@@ -3,16 +3,12 @@
 // restated here is Pillow's src/libImaging/Resample.c: separable, horizontal pass first, 22-bit fixed-point coefficients,
 // each pass rounded and clipped to u8).  The coefficient / bounds tables are Pillow's precompute_coeffs +
 // normalize_coeffs_8bpc restated on the host (fie_amd/resize.py) and uploaded once per (in, out) size pair.
-#include "fie_internal.h"
+// The fixed-point arithmetic of one output pixel is csrc/image_ops.h's (shared with the fused paste of csrc/fullres.hip).
+#include "image_ops.h"
 
 namespace {
 
-constexpr int kPrecisionBits = 32 - 8 - 2;
-
-__device__ __forceinline__ uint8_t clip8(int v) {
-    v >>= kPrecisionBits;
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
+using namespace fie_img;
 
 // out[y][ox][c] = clip8(half + sum_x in[y][xmin + x][c] * k[ox][x]); C = 3 (RGB) or 1 (a mode-L mask: Pillow runs the same 8-bit
 // passes on one band)
@@ -26,15 +22,11 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const uint8_t* in, int H,
     const uint8_t* row = in + ((size_t)y * W + xmin) * C;
     int s[C];
 #pragma unroll
-    for (int c = 0; c < C; ++c) s[c] = 1 << (kPrecisionBits - 1);
-    for (int x = 0; x < n; ++x) {
-        const int w = k[x];
-#pragma unroll
-        for (int c = 0; c < C; ++c) s[c] += row[C * x + c] * w;
-    }
+    for (int c = 0; c < C; ++c) s[c] = kResampleHalf;
+    for (int x = 0; x < n; ++x) resample_tap<C>(s, row + C * x, k[x]);
     uint8_t* o = out + ((size_t)y * OW + ox) * C;
 #pragma unroll
-    for (int c = 0; c < C; ++c) o[c] = clip8(s[c]);
+    for (int c = 0; c < C; ++c) o[c] = resample_clip8(s[c]);
 }
 
 // out[oy][x][c] = clip8(half + sum_y in[ymin + y][x][c] * k[oy][y])
@@ -48,16 +40,11 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const uint8_t* in, int W,
     const uint8_t* col = in + ((size_t)ymin * W + x) * C;
     int s[C];
 #pragma unroll
-    for (int c = 0; c < C; ++c) s[c] = 1 << (kPrecisionBits - 1);
-    for (int y = 0; y < n; ++y) {
-        const int w = k[y];
-        const uint8_t* px = col + (size_t)y * W * C;
-#pragma unroll
-        for (int c = 0; c < C; ++c) s[c] += px[c] * w;
-    }
+    for (int c = 0; c < C; ++c) s[c] = kResampleHalf;
+    for (int y = 0; y < n; ++y) resample_tap<C>(s, col + (size_t)y * W * C, k[y]);
     uint8_t* o = out + ((size_t)oy * W + x) * C;
 #pragma unroll
-    for (int c = 0; c < C; ++c) o[c] = clip8(s[c]);
+    for (int c = 0; c < C; ++c) o[c] = resample_clip8(s[c]);
 }
 
 template <int C>

@@ -10,153 +10,17 @@ import subprocess
 
 import torch
 
+from . import header
+
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("FIE_LIB_PATH") or os.path.join(_CSRC, "libfie_hip.so")      # FIE_LIB_PATH: A/B builds of the same sources (tools/)
 
-ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU, ACT_GEGLU = 0, 1, 2, 3, 4
+_P, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 
-_c = ctypes
-_P, _I, _L, _F = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float
-
-# name -> argtypes, mirrors include/fie.h one to one (tests/test_cabi_cpu.py checks every symbol is exported)
-SIGNATURES = {
-    "fie_version": [],
-    "fie_ctx_create": [_I, _P, _c.POINTER(_P)],
-    "fie_ctx_set_stream": [_P, _P],
-    "fie_ctx_error_flag": [_P, _P],
-    "fie_ctx_destroy": [_P],
-    "fie_weights_register": [_P, _c.c_char_p, _P, _L, _L],
-    "fie_weights_clear": [_P],
-    "fie_vae_decode_workspace_bytes": [_P, _I, _I],
-    "fie_vae_decode_f16": [_P, _P, _P, _P, _P, _L],
-    "fie_vae_encode_workspace_bytes": [_P],
-    "fie_vae_encode_f16": [_P, _P, _P, _P, _P, _L],
-    "fie_clip_text_workspace_bytes": [_P],
-    "fie_clip_text_forward_f16": [_P, _P, _c.c_char_p, _P, _P, _P, _P, _P, _L],
-    "fie_unet_num_residuals": [_P],
-    "fie_unet_workspace_bytes": [_P],
-    "fie_unet_forward_f16": [_P, _P, _c.c_char_p, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L],
-    "fie_controlnet_workspace_bytes": [_P],
-    "fie_controlnet_forward_f16": [_P, _P, _c.c_char_p, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _L],
-    "fie_add_f16": [_P, _P, _P, _P, _L],
-    "fie_copy_rows_f16": [_P, _P, _L, _P, _L, _I, _I],
-    "fie_program_begin": [_P, _c.POINTER(_P)],
-    "fie_program_end": [_P],
-    "fie_program_launches": [_P],
-    "fie_program_run": [_P, _P],
-    "fie_program_destroy": [_P, _P],
-    "fie_graph_register": [_P, _c.c_char_p, _P],
-    "fie_unet_forward": [_P],
-    "fie_controlnet_forward": [_P],
-    "fie_vae_encode": [_P],
-    "fie_vae_decode": [_P],
-    "fie_clip_text_forward": [_P],
-    "fie_gemm_f16": [_P, _P, _L, _I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _I, _P, _L, _F, _I],
-    "fie_gemm_ln_f16": [_P, _P, _L, _P, _L, _P, _F, _P, _L, _I, _I, _I, _I],
-    "fie_conv3x3_nhwc_f16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _I, _P, _P, _L, _P, _L, _F, _I],
-    "fie_pack_rows_f8": [_P, _P, _L, _I, _I, _P, _L, _I, _P, _I],
-    "fie_pack_conv3x3_f8": [_P, _P, _I, _I, _I, _P, _L, _I, _P],
-    "fie_gemm_w8_f16": [_P, _P, _L, _I, _P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P, _P, _L, _I, _P, _L, _F, _I],
-    "fie_conv3x3_w8_nhwc_f16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _L, _I, _P, _P, _L, _P, _L, _F, _I],
-    "fie_gemm_x8_f16": [_P, _P, _L, _P, _L, _P, _F, _P, _L, _I, _I, _I, _P, _P, _L, _I, _P, _L, _F, _I, _I, _F],
-    "fie_layernorm_f16_o8": [_P, _P, _L, _P, _L, _L, _I, _P, _P, _F, _F],
-    "fie_attention_f16_o8": [_P, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I, _F],
-    "fie_quantize_f8": [_P, _P, _L, _P, _L, _L, _I, _F],
-    "fie_amax_f16": [_P, _P, _L, _L, _I, _P],
-    "fie_groupnorm_coef_f16": [_P, _I, _I, _L, _I, _P, _P, _F, _P, _P, _I, _P],
-    "fie_conv3x3_gn_ok": [_P, _I, _I, _I, _I, _I, _I],
-    "fie_conv3x3_gn_nhwc_f16": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _L, _P, _L, _I, _P, _P, _L],
-    "fie_canny_rgb_device_begin_u8": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    "fie_canny_rgb_device_finish_u8": [_P, _I, _I, _P, _P, _P, _P],
-    "fie_weights_clear_prefix": [_P, _c.c_char_p],
-    "fie_step_cache_bind": [_P, _c.c_char_p, _P, _L],
-    "fie_step_cache_reset": [_P, _c.c_char_p],
-    "fie_unet_step_cache_bytes": [_P, _I],
-    "fie_groupnorm_nhwc_f16_o8": [_P, _P, _I, _P, _I, _P, _I, _L, _I, _P, _P, _F, _I, _P, _F],
-    "fie_groupnorm_stats_nhwc_f16_o8": [_P, _P, _I, _P, _I, _L, _I, _P, _P, _F, _I, _P, _P, _I, _F],
-    "fie_conv3x3_x8_nhwc_f16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _F, _P, _L, _I, _P, _P, _L, _P, _L, _F, _I],
-    "fie_attention_f16": [_P, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I],
-    "fie_groupnorm_workspace_bytes": [_I, _L, _I],
-    "fie_groupnorm_nhwc_f16": [_P, _P, _I, _P, _I, _P, _I, _L, _I, _P, _P, _F, _I, _P],
-    "fie_layernorm_f16": [_P, _P, _L, _P, _L, _L, _I, _P, _P, _F],
-    "fie_sinusoid_f16": [_P, _P, _I, _I, _I, _P, _L, _I],
-    "fie_time_embed_workspace_bytes": [_I],
-    "fie_time_embed_f16": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P],
-    "fie_clip_embed_f16": [_P, _P, _I, _I, _I, _P, _P, _P],
-    "fie_pixels_in_u8_f16": [_P, _P, _I, _I, _I, _P, _I],
-    "fie_pixels_out_f16_u8": [_P, _P, _L, _I, _I, _P],
-    "fie_latent_prep": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I],
-    "fie_lcm_step": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P],
-    "fie_pack_rows_f16": [_P, _P, _L, _I, _I, _P, _L, _I, _I],
-    "fie_pack_conv3x3_f16": [_P, _P, _I, _I, _I, _P, _L, _I],
-    "fie_canny_rgb_u8": [_P, _I, _I, _I, _I, _P],
-    "fie_gemm_f32": [_P, _P, _L, _I, _P, _L, _P, _L, _I, _P, _L, _I, _I, _I, _P, _P, _L, _I, _P, _L, _F, _I, _I, _I, _L, _L, _L, _L, _L, _L],
-    "fie_conv3x3_nhwc_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _I, _P, _P, _L, _P, _L, _F, _I],
-    "fie_softmax_rows_f32": [_P, _P, _L, _I, _L, _F, _I, _I],
-    "fie_groupnorm_nhwc_f32": [_P, _P, _I, _P, _I, _P, _I, _L, _I, _P, _P, _F, _I, _P],
-    "fie_layernorm_f32": [_P, _P, _L, _P, _L, _L, _I, _P, _P, _F],
-    "fie_sinusoid_f32": [_P, _P, _I, _I, _I, _P, _L, _I],
-    "fie_clip_embed_f32": [_P, _P, _I, _I, _I, _P, _P, _P],
-    "fie_pixels_in_u8_f32": [_P, _P, _I, _I, _I, _P, _I],
-    "fie_pixels_out_f32_u8": [_P, _P, _L, _I, _I, _P],
-    "fie_latent_prep_f32": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I],
-    "fie_lcm_step_f32": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P],
-    "fie_canny_workspace_bytes": [_I, _I],
-    "fie_canny_rgb_device_u8": [_P, _P, _I, _I, _I, _I, _P, _P, _c.POINTER(_I)],
-    "fie_resize_rgb_u8": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P],
-    "fie_resize_l_u8": [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P],
-    "fie_mask_prep": [_P, _P, _I, _I, _P, _I, _P, _P],
-    "fie_latent_prep_src": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I, _P],
-    "fie_latent_prep_src_f32": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I, _P],
-    "fie_lcm_step_masked": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P, _P, _P, _P],
-    "fie_lcm_step_masked_f32": [_P, _P, _L, _I, _F, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _I, _F, _P, _P, _P, _P],
-    "fie_pixels_out_composite_f16_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
-    "fie_pixels_out_composite_f32_u8": [_P, _P, _L, _I, _I, _P, _P, _P],
-    "fie_mask_fill_workspace_bytes": [_I, _I],
-    "fie_mask_fill_rgb_u8": [_P, _P, _P, _I, _I, _P, _P, _P, _P],
-    "fie_latent_prep_src_content": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I, _P, _P, _I],
-    "fie_latent_prep_src_content_f32": [_P, _P, _P, _P, _L, _F, _F, _F, _P, _P, _I, _P, _P, _I],
-    "fie_fullres_paste_rgb_u8": [_P, _P, _I, _I, _P, _L, _P, _L, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P, _L, _P],
-    "fie_metrics_workspace_bytes": [_I, _I, _I],
-    "fie_metrics_pairs_u8": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _L],
-    "fie_clip_mask_rgb_u8": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
-    "fie_clip_patches_u8_f16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "fie_clip_patches_u8_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-    "fie_vit_embed_f16": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "fie_vit_embed_f32": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "fie_clip_score_f16": [_P, _P, _L, _P, _L, _I, _I, _P],
-    "fie_clip_score_f32": [_P, _P, _L, _P, _L, _I, _I, _P],
-    "fie_dino_patches_u8_f16": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P],
-    "fie_dino_patches_u8_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P],
-    "fie_selfsim_workspace_bytes": [_I, _I],
-    "fie_selfsim_mse_f16": [_P, _P, _P, _L, _I, _I, _I, _P, _P],
-    "fie_selfsim_mse_f32": [_P, _P, _P, _L, _I, _I, _I, _P, _P],
-    "fie_debug_force_tile": [_P, _I],
-    "fie_debug_attn_variant": [_P, _I],
-    "fie_debug_gn_onepass": [_P, _I],
-    "fie_debug_tile_override": [_P, _c.c_char_p],
-    "fie_debug_last_gemm_kernel": [_P],
-    "fie_prefetch": [_P, _P, _L, _P, _I],
-    "fie_conv3x3_plus_nhwc_f16": [_P, _P, _I, _I, _I, _I, _P, _L, _P, _L, _I, _P, _P, _L, _F, _I, _P, _L, _I, _P, _L, _I],
-    "fie_conv_up2x_nhwc_f16": [_P, _P, _I, _I, _I, _I, _P, _L, _I, _P, _L, _I, _P, _P, _L, _F, _I],
-    "fie_gn_stats_target": [_P, _P, _L, _I],
-    "fie_gn_stats_bytes": [_I, _L, _I],
-    "fie_groupnorm_stats_nhwc_f16": [_P, _P, _I, _P, _I, _L, _I, _P, _P, _F, _I, _P, _P, _I],
-    "fie_gemm_autotune": [_P, _I],
-    "fie_gemm_autotune_report": [_P, ctypes.c_char_p, _I],
-    "fie_gemm_autotune_load": [_P, ctypes.c_char_p],
-    "fie_debug_tune_exclude": [_P, ctypes.c_char_p],
-    "fie_debug_gemm_probe": [_P, _I],
-    "fie_debug_epilogue_prefetch": [_P, _I],
-    "fie_debug_gemm_stamps": [_P, _P],
-    "fie_splitk_workspace": [_P, _P, _L],
-    "fie_debug_splitk": [_P, _I],
-    "fie_debug_oplog": [_P, _I],
-    "fie_debug_oplog_mark": [_P, _c.c_char_p],
-    "fie_debug_oplog_read": [_P, _c.c_char_p, _L],
-    "fie_debug_tune_candidates": [_P, _I],
-    "fie_debug_tune_candidates_read": [_P, _c.c_char_p, _L],
-}
+# include/fie.h is the one statement of the ABI (fie_amd/header.py reads it): the FIE_ACT_* codes, name -> argtypes of every declared function
+# (out-pointers are c_void_p: byref(), string buffers and ctypes arrays all pass), the return types and the config structs below
+ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU, ACT_GEGLU = (header.DEFINES["ACT_" + n] for n in ("NONE", "SILU", "GELU", "QUICK_GELU", "GEGLU"))
+SIGNATURES = {name: args for name, (_, args) in header.FUNCTIONS.items()}
 
 _lib = None
 
@@ -178,16 +42,9 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(there is no non-HIP fallback for the hot path)")
         _lib = ctypes.CDLL(LIB_PATH)
-        for name, args in SIGNATURES.items():
+        for name, (ret, args) in header.FUNCTIONS.items():
             fn = getattr(_lib, name)
-            fn.argtypes = args
-            fn.restype = _L if name in ("fie_groupnorm_workspace_bytes", "fie_canny_workspace_bytes", "fie_time_embed_workspace_bytes", "fie_gn_stats_bytes", "fie_debug_oplog_read", "fie_debug_tune_candidates_read", "fie_vae_decode_workspace_bytes",
-                                       "fie_vae_encode_workspace_bytes", "fie_clip_text_workspace_bytes", "fie_unet_workspace_bytes", "fie_controlnet_workspace_bytes",
-                                       "fie_unet_step_cache_bytes", "fie_metrics_workspace_bytes", "fie_selfsim_workspace_bytes",
-                                       "fie_mask_fill_workspace_bytes") else _I
-        _lib.fie_last_error.restype = ctypes.c_char_p
-        _lib.fie_last_error.argtypes = []
-        _lib.fie_debug_last_gemm_kernel.restype = ctypes.c_char_p
+            fn.argtypes, fn.restype = args, ret
     return _lib
 
 
@@ -231,22 +88,17 @@ GRAPH_NAMES = ("unet_forward", "controlnet_forward", "vae_encode", "vae_decode",
 
 class VaeConfig(ctypes.Structure):
     """include/fie.h: fie_vae_config (the C++ decoder walk, csrc/graphs.cpp)."""
-    _fields_ = [("latent_h", _I), ("latent_w", _I), ("num_blocks", _I), ("block_out_channels", _I * 8), ("layers_per_block", _I),
-                ("norm_num_groups", _I), ("norm_eps", _F), ("out_channels", _I), ("prefix", ctypes.c_char_p)]
+    _fields_ = header.STRUCTS["fie_vae_config"]
 
 
 class ClipConfig(ctypes.Structure):
     """include/fie.h: fie_clip_config."""
-    _fields_ = [("batch", _I), ("tokens", _I), ("hidden", _I), ("heads", _I), ("layers", _I), ("intermediate", _I), ("projection_dim", _I),
-                ("quick_gelu", _I), ("eps", _F)]
+    _fields_ = header.STRUCTS["fie_clip_config"]
 
 
 class UnetConfig(ctypes.Structure):
     """include/fie.h: fie_unet_config (UNet and ControlNet)."""
-    _fields_ = [("batch", _I), ("latent_h", _I), ("latent_w", _I), ("text_len", _I), ("num_blocks", _I), ("block_out_channels", _I * 4),
-                ("layers_per_block", _I), ("down_attn", (_I * 4) * 4), ("up_attn", (_I * 4) * 4), ("mid_attn", _I), ("mid_resnets", _I), ("head_dim", _I),
-                ("norm_num_groups", _I), ("norm_eps", _F), ("cross_attention_dim", _I), ("addition_time_embed_dim", _I), ("pooled_dim", _I),
-                ("num_cond_channels", _I), ("cond_channels", _I * 8)]
+    _fields_ = header.STRUCTS["fie_unet_config"]
 
 
 class Program:
@@ -1241,7 +1093,7 @@ class Context:
         self.sync_stream()
         _chk((lib().fie_latent_prep_src_content_f32 if self.f32 else lib().fie_latent_prep_src_content)(
             self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab), float(sqrt_1mab), _p(latents), _p(model_in),
-            model_in.shape[0], _p(z0), _p(mask_lat), hmask.CONTENT_MODES.index(mode)))
+            model_in.shape[0], _p(z0), _p(mask_lat), hmask.CONTENT_CODES[mode]))
 
     def lcm_step_masked(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
                         inv_sf, decode_in, mask_lat, z0, noise_init):

@@ -8,7 +8,11 @@ import math
 import numpy as np
 from PIL import Image
 
-CONTENT_MODES = ("original", "fill", "latent_noise", "latent_nothing")     # masked_content; the index is the C ABI's FIE_CONTENT_* code
+from . import header
+
+# masked_content: the names and codes are include/fie.h's FIE_CONTENT_* defines, in code order
+CONTENT_CODES = {n[len("CONTENT_"):].lower(): v for n, v in header.DEFINES.items() if n.startswith("CONTENT_")}
+CONTENT_MODES = tuple(sorted(CONTENT_CODES, key=CONTENT_CODES.get))
 MAX_BLUR = 21          # radius ceil(3 r) <= 64: the LDS bound of fie_mask_prep
 
 

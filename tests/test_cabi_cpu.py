@@ -26,8 +26,56 @@ def test_header_symbols_all_exported(lib):
     assert len(declared) >= 18
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/fie.h but not exported"
-    assert declared - {"fie_last_error"} == set(hip.SIGNATURES), "ctypes signature table out of sync with the header"
+    assert declared == set(hip.SIGNATURES), "ctypes signature table out of sync with the header"
     assert lib.fie_version() >= 100
+
+
+def test_signatures_known_answers(lib):
+    """The binding is computed from include/fie.h (fie_amd/header.py); these rows are written out by hand, one function per kind of type:
+    int64_t pitches between ints, a float, `const char*` in and out, an `int64_t` return, a `fie_ctx**` out-pointer."""
+    import ctypes
+    P, I, L, F, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_char_p
+    known = {
+        "fie_gemm_f16": (I, [P, P, L, I, P, L, P, L, P, L, I, I, I, P, P, L, I, P, L, F, I]),
+        "fie_fullres_paste_rgb_u8": (I, [P, P, I, I, P, L, P, L, I, I, P, P, I, P, P, I, P, I, P, L, P]),
+        "fie_selfsim_mse_f16": (I, [P, P, P, L, I, I, I, P, P]),
+        "fie_debug_oplog_read": (L, [P, S, L]),
+        "fie_last_error": (S, []),
+        "fie_debug_last_gemm_kernel": (S, [P]),
+        "fie_ctx_create": (I, [I, P, P]),
+    }
+    for name, (ret, args) in known.items():
+        assert hip.SIGNATURES[name] == args, name
+        fn = getattr(lib, name)
+        assert fn.restype is ret and list(fn.argtypes) == args, name
+    assert (hip.ACT_NONE, hip.ACT_SILU, hip.ACT_GELU, hip.ACT_QUICK_GELU, hip.ACT_GEGLU) == (0, 1, 2, 3, 4)
+    from fie_amd import header, mask
+    assert mask.CONTENT_CODES == {"original": 0, "fill": 1, "latent_noise": 2, "latent_nothing": 3}
+    for bad in ("int fie_x(unsigned n);", "size_t fie_x(void);", "typedef struct fie_s { short a; } fie_s;", "int fie_x(int (*cb)(int));"):
+        with pytest.raises(TypeError, match="include/fie.h"):
+            header.parse(bad)
+
+
+def test_config_structs_match_the_compiler(tmp_path):
+    """sizeof and every offsetof of the three config structs, as the host compiler lays out include/fie.h, against the generated ctypes classes."""
+    import shutil
+    import subprocess
+    classes = {"fie_vae_config": hip.VaeConfig, "fie_clip_config": hip.ClipConfig, "fie_unet_config": hip.UnetConfig}
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include "fie.h"', 'int main() {']
+    for cname, cls in classes.items():
+        lines.append(f'    std::printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'    std::printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
+    (tmp_path / "layout.cpp").write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    cmd = [cxx] if cxx else [shutil.which("hipcc") or "/opt/rocm/bin/hipcc", "-x", "c++"]
+    subprocess.run(cmd + ["-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.cpp"), "-o", str(tmp_path / "layout")], check=True)
+    got = dict(l.split() for l in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
+    import ctypes
+    want = {}
+    for cname, cls in classes.items():
+        want[cname] = str(ctypes.sizeof(cls))
+        want.update({f"{cname}.{f}": str(getattr(cls, f).offset) for f, _ in cls._fields_})
+    assert len(want) == 3 + 9 + 9 + 19 and got == want
 
 
 def test_no_gpu_means_loud_failure(lib):
