@@ -88,8 +88,8 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(GemmArgs p) {
     const int m0 = (b * p.OH + y0) * p.OW + x0, n0 = nt * BNH;
 
     const int live = p.probe == 1 ? 0 : 1;
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.A1, 0, (int)p.a1_bytes * live, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wt, 0, (int)p.w_bytes * live, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buf_rsrc(p.A1, (int)p.a1_bytes * live);
+    const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.Wt, (int)p.w_bytes * live);
 
     // ---- halo DMA: slot i of this wave = piece q = wave + 8 i (8 pixels x 128 B); lane = (pixel lane >> 3, chunk position lane & 7)
     unsigned h_off[HSLOTS];
@@ -299,9 +299,9 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
     const int ncol = n0 + wn * WN + fq * 4;                     // this lane's first output channel
 
     const int live = p.probe == 1 ? 0 : 1;
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.A1, 0, (int)p.a1_bytes * live, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wt, 0, (int)p.w_bytes * live, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)(((int64_t)(p.M - 1) * p.ldc + p.N) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buf_rsrc(p.A1, (int)p.a1_bytes * live);
+    const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.Wt, (int)p.w_bytes * live);
+    const __amdgpu_buffer_rsrc_t rs_c = buf_rsrc(p.C, (int)(((int64_t)(p.M - 1) * p.ldc + p.N) * 2));
 
     // ---- tile geometry: first output row, image, the patch's corner
     auto geom = [&](int tile, int& m0, int& img, int& y0, int& x0) {
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
     // bias of this lane's channels (zeros when absent): loaded once, a block keeps its column tile
     u32x2 bv[FN], rbv[FN];
     {
-        const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.bias), 0, p.bias ? p.N * 2 : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_b = buf_rsrc(p.bias, p.bias ? p.N * 2 : 0);
 #pragma unroll
         for (int i = 0; i < FN; ++i) {
             bv[i] = __builtin_amdgcn_raw_buffer_load_b64(rs_b, (unsigned)(ncol + i * 16) * 2u, 0, 0);
@@ -438,8 +438,8 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
     const int steps = 9 * nchunks + nside;
     int sb = 0;
     auto rot3 = [](int x) { return x % 3; };                 // (a scalar: tap + ring position)
-    const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A2, 0, SIDE ? (int)p.a2_bytes * live : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A3, 0, SIDE ? (int)p.a3_bytes * live : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x2 = buf_rsrc(p.A2, SIDE ? (int)p.a2_bytes * live : 0);
+    const __amdgpu_buffer_rsrc_t rs_x3 = buf_rsrc(p.A3, SIDE ? (int)p.a3_bytes * live : 0);
     auto w_soff = [&](int s) -> unsigned {                   // byte offset of tile-local K-step s in a packed weight row
         if (s < 9 * nchunks) { const int c = s / 9, t = s - 9 * c; return (unsigned)t * cin2 + (unsigned)c * (BK * 2); }
         return 9u * cin2 + (unsigned)(s - 9 * nchunks) * (BK * 2);
@@ -451,8 +451,8 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < FN; ++i) asm volatile("" : "+v"(bv[i]));
 
-    const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(p.gn_partial, 0, GN && p.gn_partial ? (p.M / (p.OH * p.OW)) * (p.gn_nch ? p.gn_nch : p.gn_rows >> 5) * p.gn_G * 8 : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.res), 0, RES && p.res ? (int)(((int64_t)(p.M - 1) * p.ldr + p.N) * 2) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_g = buf_rsrc(p.gn_partial, GN && p.gn_partial ? (p.M / (p.OH * p.OW)) * (p.gn_nch ? p.gn_nch : p.gn_rows >> 5) * p.gn_G * 8 : 0);
+    const __amdgpu_buffer_rsrc_t rs_r = buf_rsrc(p.res, RES && p.res ? (int)(((int64_t)(p.M - 1) * p.ldr + p.N) * 2) : 0);
 
     // ---- GNA: GroupNorm (+ SiLU) of the conv's INPUT applied on the resident halo (upstream resnet.py: norm -> nonlinearity -> conv; the separate
     // apply kernel -- one read and one write of the whole tensor -- disappears).  Every lane normalises, in place, the 16 bytes it DMA'd itself (its own
@@ -860,7 +860,7 @@ __global__ __launch_bounds__(512) void conv_halo2_kernel(GemmArgs p) {
         if constexpr (RB) {
             if (img != img_rb) {                                // the row bias of another image: an irregular load, so drain everything (always safe)
                 const int nimg = p.M / (p.OH * p.OW);
-                const __amdgpu_buffer_rsrc_t rs_rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.rowbias), 0, p.rowbias ? (int)(((int64_t)(nimg - 1) * p.ld_rowbias + p.N) * 2) : 0, 0x00020000);
+                const __amdgpu_buffer_rsrc_t rs_rb = buf_rsrc(p.rowbias, p.rowbias ? (int)(((int64_t)(nimg - 1) * p.ld_rowbias + p.N) * 2) : 0);
 #pragma unroll
                 for (int i = 0; i < FN; ++i) rbv[i] = __builtin_amdgcn_raw_buffer_load_b64(rs_rb, (unsigned)(img * (int)p.ld_rowbias + ncol + i * 16) * 2u, 0, 0);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

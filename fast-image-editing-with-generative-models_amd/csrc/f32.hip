@@ -3,12 +3,13 @@
 // reference-grade numerics, not speed, and doubles as an on-GPU fp32 check of the fp16 path at full size).
 // (include/fie.h: fie_gemm_f32, fie_conv3x3_nhwc_f32, fie_softmax_rows_f32)
 //
-// One contraction kernel serves Linear, 3x3 conv (same im2col gather as the fp16 kernels) and both attention products
+// One contraction kernel serves Linear, 3x3 conv (same im2col gather as the fp16 kernels: the row decode is gemm_addr.h's) and both attention products
 // (batched over (image, head) through blockIdx.z; the P V product reads V as a [K][N] matrix).  64x64x16 tile, 4 waves,
 // register-staged single LDS buffer (row stride 17 floats: conflict-free single-float fragment reads), swapped operands
 // as in the fp16 kernels (a lane owns 4 consecutive output columns).  Attention = Q K^T GEMM -> row softmax -> P V GEMM:
 // with 288 GB of HBM the fp32 score matrices (<= 3 GB) are simply materialised.
 #include "fie_internal.h"
+#include "gemm_addr.h"
 
 namespace {
 
@@ -48,6 +49,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(G32 p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
+    const fie_gemm::ConvGeom g = {p.M, p.OH, p.OW, p.H, p.W, p.Cin, p.stride, p.pt, p.pl, p.ups, 0};
     const int nk = (p.K + KB - 1) / KB;
     for (int kt = 0; kt < nk; ++kt) {
         float ra[4], rw[4];
@@ -59,13 +61,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(G32 p) {
             if (m < p.M && k < p.K) {
                 if (MODE == 1) {
                     const int tap = k / p.Cin, ci = k - tap * p.Cin;
+                    // row decode from gemm_addr.h; the tap decode, the padding test and the 64-bit index stay this kernel's own lines: tap_yx's
+                    // multiply-and-shift and conv_pixel's 32-bit index change its instruction count (profiles/gemm_addr_shared.md)
                     const int ky = tap / 3, kx = tap - 3 * ky;
-                    const int hw = p.OH * p.OW;
-                    const int b = m / hw, rem = m - b * hw;
-                    const int oh = rem / p.OW, ow = rem - oh * p.OW;
-                    const int ih = oh * p.stride - p.pt + ky, iw = ow * p.stride - p.pl + kx;
+                    const fie_gemm::ConvRow r = fie_gemm::conv_row(g, m);
+                    const int ih = r.ih0 + ky, iw = r.iw0 + kx;
                     if (ih >= 0 && ih < (p.H << p.ups) && iw >= 0 && iw < (p.W << p.ups))
-                        v = A1[((int64_t)(b * p.H + (ih >> p.ups)) * p.W + (iw >> p.ups)) * p.Cin + ci];
+                        v = A1[((int64_t)(r.b * p.H + (ih >> p.ups)) * p.W + (iw >> p.ups)) * p.Cin + ci];
                 } else {
                     v = k < p.K1 ? A1[(int64_t)m * p.lda1 + k] : p.A2[(int64_t)m * p.lda2 + (k - p.K1)];
                 }

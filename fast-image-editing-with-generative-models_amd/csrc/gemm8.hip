@@ -27,6 +27,8 @@
 //        barrier that opens group 0's next load segment).
 //   WAR  every wave drains its LDS reads (lgkmcnt(0)) BEFORE the first barrier of the reading phase, so a slot may be refilled
 //        one phase after its last read even though the other group is one barrier behind.
+//
+// Tile origin and the conv view's row / tap / pixel arithmetic: gemm_addr.h, shared with the ring kernels.
 #include "gemm_common.h"
 
 using namespace fie_gemm;
@@ -45,15 +47,14 @@ __global__ __launch_bounds__(512) void gemm8_kernel(GemmArgs p) {
     const int wm = wave >> 2, wn = wave & 3;
 
     const int bid = take_parity(p, xcd_remap(blockIdx.x, gridDim.x));
-    const int m0 = (p.order ? bid % p.nbm : bid / p.nbn) * 256;
-    const int n0 = (p.order ? bid / p.nbm : bid % p.nbn) * 256;
+    const int m0 = tile_m0<256>(p.order, p.nbm, p.nbn, bid), n0 = tile_n0<256>(p.order, p.nbm, p.nbn, bid);
     const int lr = lane >> 3;
     const int c8 = (lane & 7) ^ lr;
 
     const int live = p.probe == 1 ? 0 : 1;                           // probe 1: zero-record descriptors drop every load
-    const __amdgpu_buffer_rsrc_t rs_a1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A1, 0, (int)p.a1_bytes * live, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A2, 0, (int)p.a2_bytes * live, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wt, 0, (int)p.w_bytes * live, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a1 = buf_rsrc(p.A1, (int)p.a1_bytes * live);
+    const __amdgpu_buffer_rsrc_t rs_a2 = buf_rsrc(p.A2, (int)p.a2_bytes * live);
+    const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.Wt, (int)p.w_bytes * live);
     const int lm0 = p.probe == 2 ? 0 : m0, ln0 = p.probe == 2 ? 0 : n0;   // probe 2: all tiles load tile (0,0)
 
     // ---- DMA pieces (8 rows x 128 B per wave-instruction).  A half-tile has 16 pieces; this wave issues pieces `wave` and
@@ -67,32 +68,30 @@ __global__ __launch_bounds__(512) void gemm8_kernel(GemmArgs p) {
         for (int j = 0; j < 2; ++j)
             w_off[s][j] = (unsigned)(ln0 + wrow0 + 128 * j + 32 * s + lr) * (unsigned)p.ldw * 2u + c8 * 16u;
     unsigned a_off[2][2], a_off2[2][2];                             // GEMM: offsets into A1 / A2; conv: offsets of the current tap
-    int a_ih[2][2], a_iw[2][2];
+    const ConvGeom g = conv_geom(p, p.taps2);                       // behind take_parity, which sets this block's pt / pl
+    ConvRow a_row[2][2];
     unsigned a_img[2][2];
-    bool a_ok[2][2];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int m = lm0 + arow0 + 128 * j + 64 * s + lr;
-            a_ok[s][j] = m < p.M;
             if (MODE == 2) {
-                const int hw = p.OH * p.OW;
-                const int b = m / hw, rem = m - b * hw;
-                const int oh = rem / p.OW, ow = rem - oh * p.OW;
-                a_ih[s][j] = oh * p.stride - p.pt;
-                a_iw[s][j] = ow * p.stride - p.pl;
-                a_img[s][j] = (unsigned)b * (unsigned)(p.H * p.W) * (unsigned)p.Cin * 2u;
+                a_row[s][j] = conv_row(g, m);
+                a_img[s][j] = (unsigned)a_row[s][j].b * (unsigned)(p.H * p.W) * (unsigned)p.Cin * 2u;
                 a_off[s][j] = kOob;
                 a_off2[s][j] = 0;
             } else {
-                a_off[s][j] = a_ok[s][j] ? (unsigned)m * (unsigned)p.lda1 * 2u + c8 * 16u : kOob;
-                a_off2[s][j] = a_ok[s][j] ? (unsigned)m * (unsigned)p.lda2 * 2u + c8 * 16u : kOob;
-                a_ih[s][j] = a_iw[s][j] = 0;
+                const bool ok = m < p.M;
+                a_off[s][j] = ok ? (unsigned)m * (unsigned)p.lda1 * 2u + c8 * 16u : kOob;
+                a_off2[s][j] = ok ? (unsigned)m * (unsigned)p.lda2 * 2u + c8 * 16u : kOob;
+                a_row[s][j] = ConvRow{};
                 a_img[s][j] = 0;
             }
         }
-    int cs[2] = {0, 0}, ftap[2] = {0, 0};                            // conv: channel step inside the tap / tap of the next issue, per set
+    // conv: channel step inside the tap / tap of the next issue, per set.  No k_slice, no tap_fresh: the phased tiles never split K (their
+    // rows of the launch table carry no kSplitK), so every block starts at tap 0
+    int cs[2] = {0, 0}, ftap[2] = {0, 0};
     const int csteps = MODE == 2 ? p.Cin / BK : 1;
     const int k1_steps = p.K1 / BK;                                  // GEMM: K-tiles served by A1 (K1 % 64 == 0 unless K1 == K)
     const int nk = (p.K + BK - 1) / BK;
@@ -111,13 +110,15 @@ __global__ __launch_bounds__(512) void gemm8_kernel(GemmArgs p) {
         constexpr int S = decltype(setc)::value;
         if (MODE != 2 || kt >= nk) return;
         if (cs[S] == 0) {
-            const int ky = p.taps2 ? ftap[S] >> 1 : (ftap[S] * 11) >> 5, kx = p.taps2 ? ftap[S] & 1 : ftap[S] - 3 * ky;
+            const TapYX t = tap_yx(g, ftap[S]);
+            // The padding test is conv_inside's, written out: through the helper each of the two rows shifts the limits again (+6 scalar shifts in the
+            // three inlined copies of this lambda, and this kernel has no scalar register to spare: profiles/gemm_addr_shared.md)
             const int hlim = p.H << p.ups, wlim = p.W << p.ups;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int ih = a_ih[S][j] + ky, iw = a_iw[S][j] + kx;
-                const bool ok = a_ok[S][j] && ih >= 0 && ih < hlim && iw >= 0 && iw < wlim;
-                a_off[S][j] = ok ? a_img[S][j] + (unsigned)((ih >> p.ups) * p.W + (iw >> p.ups)) * (unsigned)p.Cin * 2u + c8 * 16u : kOob;
+                const int ih = a_row[S][j].ih0 + t.ky, iw = a_row[S][j].iw0 + t.kx;
+                const bool ok = a_row[S][j].ok && ih >= 0 && ih < hlim && iw >= 0 && iw < wlim;
+                a_off[S][j] = ok ? a_img[S][j] + (unsigned)conv_index(g, a_row[S][j], t.ky, t.kx) * (unsigned)p.Cin * 2u + c8 * 16u : kOob;
             }
         }
         so_a[S] = (unsigned)cs[S] * (BK * 2);

@@ -8,8 +8,11 @@
 // v_mfma_f32_16x16x32_f16, so a lane owns 4 CONSECUTIVE output channels of one output row (8-byte bias / residual loads and
 // stores; GEGLU value / gate pairs in one lane).  LDS images are rows of 128 B (one 64-deep K-step), 16-byte chunks
 // XOR-swizzled by (row & 7): applied on the SOURCE offset of the LDS-DMA and again on the ds_read_b128 fragment reads.
+// The address arithmetic of that view -- tile origin, output row -> input pixel, tap decode, padding test, split-K range -- is gemm_addr.h's (plain
+// integers, also built and tested on the host); the buffer descriptors of every kernel here come from buf_rsrc below.
 #pragma once
 #include "fie_internal.h"
+#include "gemm_addr.h"
 
 namespace fie_gemm {
 
@@ -73,6 +76,17 @@ __device__ __forceinline__ int take_parity(GemmArgs& p, int bid) {
     return bid >> 2;
 }
 
+// the conv view of A1 as gemm_addr.h takes it; call it after take_parity (which rewrites pt / pl).  taps2: p.taps2, or 0 in a kernel that is never
+// handed the 2x2 parity convs and so compiles the 3x3 decode alone
+__host__ __device__ __forceinline__ ConvGeom conv_geom(const GemmArgs& p, int taps2) { return {p.M, p.OH, p.OW, p.H, p.W, p.Cin, p.stride, p.pt, p.pl, p.ups, taps2}; }
+
+// Raw buffer descriptor over [ptr, ptr + bytes): a load past `bytes` returns zero and a store there is dropped (the kernels' range masks).
+// kBufRsrcFlags = dword 3 of the descriptor: DATA_FORMAT 32 (bits 17:12), everything else zero -- raw buffer, no swizzle, no index stride
+constexpr int kBufRsrcFlags = 0x00020000;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* ptr, int64_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, kBufRsrcFlags);
+}
+
 // f(integral_constant<int, 0>), f(integral_constant<int, 1>), ...: a loop whose index is a compile-time constant in every iteration
 template <class F, int... I>
 __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -121,12 +135,12 @@ __device__ __forceinline__ void epilogue_prefetch(const GemmArgs& p, EpiPre<FM, 
 #pragma unroll
         for (int i = 0; i < FN; ++i) pre.res[j][i] = (u32x2){0u, 0u};
     if (p.bias) {
-        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.bias), 0, p.N * 2, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rb = buf_rsrc(p.bias, p.N * 2);
 #pragma unroll
         for (int i = 0; i < FN; ++i) pre.bias[i] = __builtin_amdgcn_raw_buffer_load_b64(rb, (unsigned)(ncol + i * 16) * 2u, 0, 0);
     }
     if (p.res) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.res), 0, (int)(((int64_t)(p.M - 1) * p.ldr + p.N) * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(p.res, (int)(((int64_t)(p.M - 1) * p.ldr + p.N) * 2));
 #pragma unroll
         for (int j = 0; j < FM; ++j) {
             const int m = mrow + j * 16;
@@ -148,7 +162,7 @@ template <int FM, int FN, int WM, int WN>
 __device__ __forceinline__ void epilogue_lean(const GemmArgs& p, f32x4 (&acc)[FN][FM], int m0, int n0, int wm, int wn, int lane, const EpiPre<FM, FN>& pre) {
     const int fr = lane & 15, fq = lane >> 4;
     const int mrow = m0 + wm * WM + fr, ncol = n0 + wn * WN + fq * 4;
-    const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)(((int64_t)(p.M - 1) * p.ldc + p.N) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_c = buf_rsrc(p.C, (int)(((int64_t)(p.M - 1) * p.ldc + p.N) * 2));
 #pragma unroll
     for (int j = 0; j < FM; ++j) {
         const int m = mrow + j * 16;
@@ -174,7 +188,7 @@ __device__ __forceinline__ void epilogue_lean_scaled(const GemmArgs& p, f32x4 (&
                                                      const f32x4 (&ws)[FN]) {
     const int fr = lane & 15, fq = lane >> 4;
     const int mrow = m0 + wm * WM + fr, ncol = n0 + wn * WN + fq * 4;
-    const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)(((int64_t)(p.M - 1) * p.ldc + p.N) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_c = buf_rsrc(p.C, (int)(((int64_t)(p.M - 1) * p.ldc + p.N) * 2));
 #pragma unroll
     for (int j = 0; j < FM; ++j) {
         const int m = mrow + j * 16;
@@ -211,7 +225,7 @@ __device__ __forceinline__ void ln_dot(const f16x8& f, float& s, float& q) {
 template <int FN>
 struct LnTab { f32x4 lo[FN], hi[FN]; };       // lo = (S0, b0, S1, b1), hi = (S2, b2, S3, b3)
 __device__ __forceinline__ void ln_tab_load(const GemmArgs& p, int n, f32x4& lo, f32x4& hi) {
-    const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.ln_tab), 0, p.N * 8, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rt = buf_rsrc(p.ln_tab, p.N * 8);
     lo = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rt, (unsigned)n * 8u, 0, 0));
     hi = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rt, (unsigned)n * 8u + 16u, 0, 0));
 }
@@ -221,7 +235,7 @@ __device__ __forceinline__ void epilogue_lean_ln(const GemmArgs& p, f32x4 (&acc)
                                                  const float (&mean)[FM], const float (&rstd)[FM]) {
     const int fr = lane & 15, fq = lane >> 4;
     const int mrow = m0 + wm * WM + fr, ncol = n0 + wn * WN + fq * 4;
-    const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)(((int64_t)(p.M - 1) * p.ldc + p.N) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_c = buf_rsrc(p.C, (int)(((int64_t)(p.M - 1) * p.ldc + p.N) * 2));
 #pragma unroll
     for (int j = 0; j < FM; ++j) {
         const int m = mrow + j * 16;
@@ -255,8 +269,8 @@ __device__ __forceinline__ void epilogue_geglu_lean(const GemmArgs& p, f32x4 (&a
     static_assert(FM % 4 == 0, "left-over fragment columns are transposed over four row fragments");
     const int fr = lane & 15, fq = lane >> 4;
     const int mrow = m0 + wm * WM + fr, nbase = n0 + wn * WN;
-    const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)(((int64_t)(p.M - 1) * p.ldc + (p.N >> 1)) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(p.bias), 0, p.bias ? p.N * 2 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_c = buf_rsrc(p.C, (int)(((int64_t)(p.M - 1) * p.ldc + (p.N >> 1)) * 2));
+    const __amdgpu_buffer_rsrc_t rs_b = buf_rsrc(p.bias, p.bias ? p.N * 2 : 0);
     auto bias4 = [&](int i) { return __builtin_amdgcn_raw_buffer_load_b64(rs_b, (unsigned)(nbase + i * 16 + fq * 4) * 2u, 0, 0); };   // no bias: zero-size descriptor, reads zero
     auto pair = [&](const f32x4& a, u32x2 bb) {
         f16x4 b;
@@ -358,10 +372,9 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, f32x4 (&acc)[FN][FM]
         const int m = mrow + j * fld;
         if (m >= p.M) return kRowOut;
         if (!p.oscat) return (unsigned)m * (unsigned)p.ldc * 2u;
-        const int hw = p.OH * p.OW, b = m / hw, rem = m - b * hw, oh = rem / p.OW, ow = rem - oh * p.OW;
-        return (unsigned)((b * 2 * p.OH + 2 * oh + p.opy) * (2 * p.OW) + 2 * ow + p.opx) * (unsigned)p.ldc * 2u;
+        const OutPixel o = out_pixel(p.OH, p.OW, m);
+        return (unsigned)((o.b * 2 * p.OH + 2 * o.oh + p.opy) * (2 * p.OW) + 2 * o.ow + p.opx) * (unsigned)p.ldc * 2u;
     };
-    auto rsrc = [&](const void* ptr, int64_t bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, (int)bytes, 0x00020000); };
     auto as_h4 = [](u32x2 v) { f16x4 h; __builtin_memcpy(&h, &v, 8); return h; };
 
     if (p.w_scale) {
@@ -419,7 +432,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, f32x4 (&acc)[FN][FM]
     else if (p.act == FIE_ACT_QUICK_GELU) sweep([](float x) { return fie_qgelu(x); });
     else if (p.scale != 1.f) sweep([](float x) { return x; });
     if (p.res) {                                            // never with GEGLU (check_epilogue); may alias C: read before this tile's stores
-        const __amdgpu_buffer_rsrc_t rs = rsrc(p.res, BUF ? ((int64_t)(p.M - 1) * p.ldr + p.N) * 2 : 0);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(p.res, BUF ? ((int64_t)(p.M - 1) * p.ldr + p.N) * 2 : 0);
 #pragma unroll
         for (int j = 0; j < FM; ++j) {
             f16x4 b[FN];
@@ -497,7 +510,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, f32x4 (&acc)[FN][FM]
     }
     if constexpr (BUF) {
         if (p.out_f8) {                                     // e4m3 bytes for an fp8-activation consumer: 4 (GEGLU: 2) bytes per lane and fragment
-            const __amdgpu_buffer_rsrc_t rs8 = rsrc(p.C, (int64_t)(p.M - 1) * p.ldc + (geglu ? p.N >> 1 : p.N));
+            const __amdgpu_buffer_rsrc_t rs8 = buf_rsrc(p.C, (int64_t)(p.M - 1) * p.ldc + (geglu ? p.N >> 1 : p.N));
             const float inv = p.out_inv_scale;
             auto q = [&](float x) { return fie_sat448(x * inv); };
 #pragma unroll
@@ -521,7 +534,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, f32x4 (&acc)[FN][FM]
         }
     }
     // ---- stores: lane holds C[m = .. + fr][n = .. + fq*4 + (0..3)]
-    const __amdgpu_buffer_rsrc_t rs_c = rsrc(p.C, BUF ? ((int64_t)(p.oscat ? 4 * (int64_t)p.M : p.M) - 1) * p.ldc * 2 + (geglu ? p.N >> 1 : p.N) * 2 : 0);
+    const __amdgpu_buffer_rsrc_t rs_c = buf_rsrc(p.C, BUF ? ((int64_t)(p.oscat ? 4 * (int64_t)p.M : p.M) - 1) * p.ldc * 2 + (geglu ? p.N >> 1 : p.N) * 2 : 0);
 #pragma unroll
     for (int j = 0; j < FM; ++j) {
         const int m = mrow + j * fld;
@@ -588,7 +601,7 @@ __device__ __forceinline__ bool splitk_reduce(const GemmArgs& p, f32x4 (&acc)[FN
     const int S = p.splitk;
     float* base = p.sk_slabs + (size_t)tile * S * kTile;
     {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base + (size_t)slice * kTile, 0, kTile * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(base + (size_t)slice * kTile, kTile * 4);
 #pragma unroll
         for (int i = 0; i < FN; ++i)
 #pragma unroll
@@ -618,7 +631,7 @@ __device__ __forceinline__ bool splitk_reduce(const GemmArgs& p, f32x4 (&acc)[FN
 #pragma unroll
         for (int j = 0; j < FM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < S; ++s) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base + (size_t)s * kTile, 0, kTile * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(base + (size_t)s * kTile, kTile * 4);
         u32x4 v[FN][FM];
 #pragma unroll
         for (int i = 0; i < FN; ++i)

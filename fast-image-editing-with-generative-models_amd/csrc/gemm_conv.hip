@@ -11,6 +11,9 @@
 //                                    256x256 tile.
 //   gemm8_kernel<MODE> (gemm8.hip)   256x256, four phases per K-tile, two wave groups one barrier apart.
 //
+// The im2col and split-K address arithmetic of all three (and of gemm_w8.hip, gemm_x8.hip, f32.hip) is stated in gemm_addr.h; a kernel keeps its loops,
+// its per-piece offset arrays and its issue lambdas, and says in a comment where it takes less than the others (no slice, no 2x2 taps) and why.
+//
 // Unselected experiments of round 1 (zero-page global_load_lds ring, ping-pong, four-phase, producer waves, halo-reuse conv,
 // 160-wide tiles, column split): measured no better, removed (git history has them; the numbers are in profiles/r01_microbench.md).
 #include <algorithm>
@@ -38,30 +41,24 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     const int wm = wave & 1, wn = wave >> 1;
 
     const int bid = xcd_remap(blockIdx.x, gridDim.x);     // consecutive ids on one XCD share the activation rows (n fastest)
-    const int m0 = (p.order ? bid % p.nbm : bid / p.nbn) * BM;
-    const int n0 = (p.order ? bid / p.nbm : bid % p.nbn) * BN;
+    const int m0 = tile_m0<BM>(p.order, p.nbm, p.nbn, bid), n0 = tile_n0<BN>(p.order, p.nbm, p.nbn, bid);
 
     const int c8 = tid & 7;          // chunk column inside the K-step
     const int r0 = tid >> 3;         // 0..31
 
     // ---- per-thread A-row descriptors
-    int64_t a_base[RA];
-    int a_ih[RA], a_iw[RA];
-    bool a_ok[RA];
+    const ConvGeom g = conv_geom(p, 0);      // 3x3 taps only: the launcher refuses the 2x2 parity convs on this kernel (run_code)
+    int64_t a_base[RA];              // conv: first element of the row's image; GEMM: the row
+    ConvRow a_row[RA];
 #pragma unroll
     for (int i = 0; i < RA; ++i) {
         const int m = m0 + r0 + 32 * i;
-        a_ok[i] = m < p.M;
         if (MODE == 1) {
-            const int hw = p.OH * p.OW;
-            const int b = m / hw, rem = m - b * hw;
-            const int oh = rem / p.OW, ow = rem - oh * p.OW;
-            a_ih[i] = oh * p.stride - p.pt;
-            a_iw[i] = ow * p.stride - p.pl;
-            a_base[i] = (int64_t)b * p.H * p.W * p.Cin;
+            a_row[i] = conv_row(g, m);
+            a_base[i] = (int64_t)a_row[i].b * p.H * p.W * p.Cin;
         } else {
+            a_row[i] = ConvRow{0, 0, 0, m < p.M};
             a_base[i] = (int64_t)m;
-            a_ih[i] = a_iw[i] = 0;
         }
     }
     int tap = 0, ci = c8 * 8;        // conv: position of this thread's chunk in (tap, channel) space
@@ -75,12 +72,15 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     auto load_tiles = [&](int kt) {
         const int k = kt * BK + c8 * 8;
         if (MODE == 1) {
-            const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;
+            const TapYX t = tap_yx(g, tap);
+            // conv_inside and conv_index of gemm_addr.h with `tap < 9` in the test's second place, written out: through the helpers (the extra term in
+            // front, or folded into the row) the three conv views gain or lose up to 50 instructions (profiles/gemm_addr_shared.md).
+            // tap < 9: K is rounded up to whole K-steps and Cin % 64 != 0 here, so the chunks of the last K-step walk past the ninth tap
             const int hlim = p.H << p.ups, wlim = p.W << p.ups;
 #pragma unroll
             for (int i = 0; i < RA; ++i) {
-                const int ih = a_ih[i] + ky, iw = a_iw[i] + kx;
-                const bool ok = a_ok[i] && tap < 9 && ih >= 0 && ih < hlim && iw >= 0 && iw < wlim;
+                const int ih = a_row[i].ih0 + t.ky, iw = a_row[i].iw0 + t.kx;
+                const bool ok = a_row[i].ok && tap < 9 && ih >= 0 && ih < hlim && iw >= 0 && iw < wlim;
                 const int64_t off = a_base[i] + ((int64_t)((ih >> p.ups) * p.W + (iw >> p.ups))) * p.Cin + ci;
                 ra[i] = ok ? *reinterpret_cast<const f16x8*>(p.A1 + off) : zero8;
             }
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
             const int kk = k1 ? k : k - p.K1;
 #pragma unroll
             for (int i = 0; i < RA; ++i) {
-                const bool ok = a_ok[i] && k < p.K;
+                const bool ok = a_row[i].ok && k < p.K;
                 ra[i] = ok ? *reinterpret_cast<const f16x8*>(src + a_base[i] * ld + kk) : zero8;
             }
         }
@@ -201,41 +201,38 @@ __global__ __launch_bounds__(NW * 64) void gemm3_kernel(GemmArgs p) {
     const int nsplit = p.splitk > 1 ? p.splitk : 1;
     const int tile_all = bid_all / nsplit, slice = bid_all - tile_all * nsplit;
     const int bid = take_parity(p, tile_all);
+    // tile_m0 / tile_n0 of gemm_addr.h, spelled out: through the functions one GEMM-view instance (256x320, ALT, LayerNorm fold) orders two
+    // instructions differently, and the GEMM views keep their text (two faults here followed the schedule, not the arithmetic)
     const int m0 = (p.order ? bid % p.nbm : bid / p.nbn) * BM;
     const int n0 = (p.order ? bid / p.nbm : bid % p.nbn) * BN;
     const int lr = lane >> 3;
     const int c8 = (lane & 7) ^ lr;
 
     const int live = p.probe == 1 ? 0 : 1;                 // timing probes, see GemmArgs::probe
-    const __amdgpu_buffer_rsrc_t rs_a1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A1, 0, (int)p.a1_bytes * live, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A2, 0, (int)p.a2_bytes * live, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wt, 0, (int)p.w_bytes * live, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_a3 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A3, 0, (int)p.a3_bytes * live, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a1 = buf_rsrc(p.A1, (int)p.a1_bytes * live);
+    const __amdgpu_buffer_rsrc_t rs_a2 = buf_rsrc(p.A2, (int)p.a2_bytes * live);
+    const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.Wt, (int)p.w_bytes * live);
+    const __amdgpu_buffer_rsrc_t rs_a3 = buf_rsrc(p.A3, (int)p.a3_bytes * live);
     const int lm0 = p.probe == 2 ? 0 : m0, ln0 = p.probe == 2 ? 0 : n0;
 
     // per-lane byte offsets
     unsigned a_off1[RA], a_off2[RA];       // GEMM: row offsets into A1 / A2;  conv: a_off1 = offset for the current tap, a_off2 = row m of the side input A2
     unsigned a_off3[RA];                   // conv: row m of the second side input A3
-    int a_ih[RA], a_iw[RA];
+    const ConvGeom g = conv_geom(p, p.taps2);      // behind take_parity, which sets this block's pt / pl
+    ConvRow a_row[RA];
     unsigned a_img[RA];
-    bool a_ok[RA];
 #pragma unroll
     for (int i = 0; i < RA; ++i) {
         const int m = lm0 + (wave + NW * i) * 8 + lr;
-        a_ok[i] = m < p.M;
         if (MODE == 2) {
-            const int hw = p.OH * p.OW;
-            const int b = m / hw, rem = m - b * hw;
-            const int oh = rem / p.OW, ow = rem - oh * p.OW;
-            a_ih[i] = oh * p.stride - p.pt;
-            a_iw[i] = ow * p.stride - p.pl;
-            a_img[i] = (unsigned)b * (unsigned)(p.H * p.W) * (unsigned)p.Cin * 2u;
+            a_row[i] = conv_row(g, m);
+            a_img[i] = (unsigned)a_row[i].b * (unsigned)(p.H * p.W) * (unsigned)p.Cin * 2u;
             a_off1[i] = kOob;
-            a_off2[i] = a_ok[i] ? (unsigned)m * (unsigned)p.lda2 * 2u + c8 * 16u : kOob;
-            a_off3[i] = a_ok[i] ? (unsigned)m * (unsigned)p.lda3 * 2u + c8 * 16u : kOob;
+            a_off2[i] = a_row[i].ok ? (unsigned)m * (unsigned)p.lda2 * 2u + c8 * 16u : kOob;
+            a_off3[i] = a_row[i].ok ? (unsigned)m * (unsigned)p.lda3 * 2u + c8 * 16u : kOob;
         } else {
             a_off1[i] = a_off2[i] = a_off3[i] = a_img[i] = 0;          // GEMM: a_base1 / a_base2 below
-            a_ih[i] = a_iw[i] = 0;
+            a_row[i] = ConvRow{};
         }
     }
     // GEMM view: a lane's row groups are NW * 8 rows apart, so ONE per-lane offset (+ a uniform stride per group) serves all of them.
@@ -250,13 +247,13 @@ __global__ __launch_bounds__(NW * 64) void gemm3_kernel(GemmArgs p) {
     const int csteps = MODE == 2 ? p.Cin / BK : 1;
     const int k1_steps = p.K1 / BK;            // GEMM: K-steps served by A1 (K1 % 64 == 0 unless K1 == K)
     const int nk_all = (p.K + BK - 1) / BK;
-    const int kbeg = (int)((int64_t)nk_all * slice / nsplit);          // this block's K-steps: [kbeg, kbeg + nk); all of them without split-K
-    const int nk = (int)((int64_t)nk_all * (slice + 1) / nsplit) - kbeg;
+    const KSlice ks(nk_all, slice, nsplit, csteps);                    // this block's K-steps: [kbeg, kbeg + nk); all of them without split-K
+    const int kbeg = ks.kbeg, nk = ks.nk;
     const bool ktail = (p.K % BK) != 0;
-    int ftap = kbeg / csteps, cs = kbeg - ftap * csteps;              // conv: tap and channel step of the next K-step to issue
+    int ftap = ks.ftap, cs = ks.cs;                                   // conv: tap and channel step of the next K-step to issue
     bool tap_fresh = true;                                            // a slice may start in the middle of a tap
 
-    const int ntaps = p.taps2 ? 4 : 9;
+    const int ntaps = conv_taps(g);
     auto issue = [&](int kt, int stage) {
         half_t* sa = smem + stage * STAGE;
         if (MODE == 2 && ftap >= ntaps) {                   // past the taps: the 1x1 side inputs, row m itself
@@ -271,14 +268,10 @@ __global__ __launch_bounds__(NW * 64) void gemm3_kernel(GemmArgs p) {
         } else if (MODE == 2) {
             if (cs == 0 || tap_fresh) {
                 tap_fresh = false;
-                const int ky = p.taps2 ? ftap >> 1 : (ftap * 11) >> 5, kx = p.taps2 ? ftap & 1 : ftap - 3 * ky;
-                const int hlim = p.H << p.ups, wlim = p.W << p.ups;
+                const TapYX t = tap_yx(g, ftap);
 #pragma unroll
-                for (int i = 0; i < RA; ++i) {
-                    const int ih = a_ih[i] + ky, iw = a_iw[i] + kx;
-                    const bool ok = a_ok[i] && ih >= 0 && ih < hlim && iw >= 0 && iw < wlim;
-                    a_off1[i] = ok ? a_img[i] + (unsigned)((ih >> p.ups) * p.W + (iw >> p.ups)) * (unsigned)p.Cin * 2u + c8 * 16u : kOob;
-                }
+                for (int i = 0; i < RA; ++i)
+                    a_off1[i] = conv_inside(g, a_row[i], t.ky, t.kx) ? a_img[i] + (unsigned)conv_index(g, a_row[i], t.ky, t.kx) * (unsigned)p.Cin * 2u + c8 * 16u : kOob;
             }
             const unsigned so = (unsigned)cs * (BK * 2);
 #pragma unroll

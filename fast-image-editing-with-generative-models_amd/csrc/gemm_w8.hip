@@ -12,7 +12,7 @@
 //
 // Kernel = the LDS-DMA ring kernel of gemm_conv.hip (ST stages, counted vmcnt, one raw barrier per K-step, swapped operands) with a
 // 64-byte-per-row weight image: a DMA piece is 16 rows x 64 B, 16-byte chunks XOR-swizzled by (row >> 2) & 3 (rows r and r + 4 would
-// otherwise share banks for the ds_read_b64 fragment reads), applied on the SOURCE chunk and on the read.
+// otherwise share banks for the ds_read_b64 fragment reads), applied on the SOURCE chunk and on the read.  Activation addressing: gemm_addr.h, as there.
 #include "gemm_common.h"
 #include "gemm_tiles.h"
 
@@ -55,38 +55,33 @@ __global__ __launch_bounds__(NW * 64) void gemm3w8_kernel(GemmArgs p) {
     const int wm = wave & 1, wn = wave >> 1;
 
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (p.order ? bid % p.nbm : bid / p.nbn) * BM;
-    const int n0 = (p.order ? bid / p.nbm : bid % p.nbn) * BN;
+    const int m0 = tile_m0<BM>(p.order, p.nbm, p.nbn, bid), n0 = tile_n0<BN>(p.order, p.nbm, p.nbn, bid);
     const int lr = lane >> 3;
     const int c8 = (lane & 7) ^ lr;
     const int lr16 = lane >> 2;                                     // weight piece: 16 rows x 4 chunks of 16 B
     const int c4 = (lane & 3) ^ ((lr16 >> 2) & 3);
 
-    const __amdgpu_buffer_rsrc_t rs_a1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A1, 0, (int)p.a1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.A2, 0, (int)p.a2_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wt, 0, (int)p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a1 = buf_rsrc(p.A1, (int)p.a1_bytes);
+    const __amdgpu_buffer_rsrc_t rs_a2 = buf_rsrc(p.A2, (int)p.a2_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.Wt, (int)p.w_bytes);
 
+    const ConvGeom g = conv_geom(p, 0);                             // 3x3 taps only: the launcher refuses the 2x2 parity convs with fp8 weights (gemm_conv.hip, run_code)
     unsigned a_off1[RA], a_off2[RA];
-    int a_ih[RA], a_iw[RA];
+    ConvRow a_row[RA];
     unsigned a_img[RA];
-    bool a_ok[RA];
 #pragma unroll
     for (int i = 0; i < RA; ++i) {
         const int m = m0 + (wave + NW * i) * 8 + lr;
-        a_ok[i] = m < p.M;
         if (MODE == 2) {
-            const int hw = p.OH * p.OW;
-            const int b = m / hw, rem = m - b * hw;
-            const int oh = rem / p.OW, ow = rem - oh * p.OW;
-            a_ih[i] = oh * p.stride - p.pt;
-            a_iw[i] = ow * p.stride - p.pl;
-            a_img[i] = (unsigned)b * (unsigned)(p.H * p.W) * (unsigned)p.Cin * 2u;
+            a_row[i] = conv_row(g, m);
+            a_img[i] = (unsigned)a_row[i].b * (unsigned)(p.H * p.W) * (unsigned)p.Cin * 2u;
             a_off1[i] = kOob;
             a_off2[i] = 0;
         } else {
-            a_off1[i] = a_ok[i] ? (unsigned)m * (unsigned)p.lda1 * 2u + c8 * 16u : kOob;
-            a_off2[i] = a_ok[i] ? (unsigned)m * (unsigned)p.lda2 * 2u + c8 * 16u : kOob;
-            a_ih[i] = a_iw[i] = 0;
+            const bool ok = m < p.M;
+            a_off1[i] = ok ? (unsigned)m * (unsigned)p.lda1 * 2u + c8 * 16u : kOob;
+            a_off2[i] = ok ? (unsigned)m * (unsigned)p.lda2 * 2u + c8 * 16u : kOob;
+            a_row[i] = ConvRow{};
             a_img[i] = 0;
         }
     }
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(NW * 64) void gemm3w8_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < RW; ++i) w_off[i] = (unsigned)(n0 + (wave + NW * i) * 16 + lr16) * (unsigned)p.ldw + c4 * 16u;
 
-    int cs = 0, ftap = 0;
+    int cs = 0, ftap = 0;                                           // no k_slice, no tap_fresh: fp8-weight launches never split K (gemm_conv.hip, splitk_fit), so every block starts at tap 0
     const int csteps = MODE == 2 ? p.Cin / BK : 1;
     const int k1_steps = p.K1 / BK;
     const int nk = (p.K + BK - 1) / BK;
@@ -104,13 +99,10 @@ __global__ __launch_bounds__(NW * 64) void gemm3w8_kernel(GemmArgs p) {
         half_t* sa = reinterpret_cast<half_t*>(smem8 + stage * STAGE_B);
         if (MODE == 2) {
             if (cs == 0) {
-                const int ky = (ftap * 11) >> 5, kx = ftap - 3 * ky;
-                const int hlim = p.H << p.ups, wlim = p.W << p.ups;
+                const TapYX t = tap_yx(g, ftap);
 #pragma unroll
                 for (int i = 0; i < RA; ++i) {
-                    const int ih = a_ih[i] + ky, iw = a_iw[i] + kx;
-                    const bool ok = a_ok[i] && ih >= 0 && ih < hlim && iw >= 0 && iw < wlim;
-                    a_off1[i] = ok ? a_img[i] + (unsigned)((ih >> p.ups) * p.W + (iw >> p.ups)) * (unsigned)p.Cin * 2u + c8 * 16u : kOob;
+                    a_off1[i] = conv_inside(g, a_row[i], t.ky, t.kx) ? a_img[i] + (unsigned)conv_index(g, a_row[i], t.ky, t.kx) * (unsigned)p.Cin * 2u + c8 * 16u : kOob;
                 }
             }
             const unsigned so = (unsigned)cs * (BK * 2);

@@ -9,6 +9,7 @@
 // Kernel = the LDS-DMA ring kernel of gemm_conv.hip (GEMM view only) with byte elements: K-step = 128 elements = the same 128-byte rows, the
 // same 16-byte-chunk XOR swizzle by (row & 7), the same DMA pieces and counted vmcnt; a lane's fragment is 32 contiguous k-values of one row
 // (lane = (row 0-15, k-block 0-3): two ds_read_b128), operands swapped (weights first) so a lane owns 4 consecutive output channels.
+// Tile origin, split-K range and the conv view's row / tap / pixel lookup: gemm_addr.h, as there; the byte offsets here count one byte per element.
 // Entry: fie_gemm_x8_f16 (include/fie.h).
 #include "gemm_common.h"
 #include "gemm_tiles.h"
@@ -40,13 +41,12 @@ __global__ __launch_bounds__(NW * 64) void gemm3x8_kernel(GemmArgs p) {
     const int bid_all = xcd_remap(blockIdx.x, gridDim.x);
     const int nsplit = p.splitk > 1 ? p.splitk : 1;
     const int tile_all = bid_all / nsplit, slice = bid_all - tile_all * nsplit;
-    const int m0 = (p.order ? tile_all % p.nbm : tile_all / p.nbn) * BM;
-    const int n0 = (p.order ? tile_all / p.nbm : tile_all % p.nbn) * BN;
+    const int m0 = tile_m0<BM>(p.order, p.nbm, p.nbn, tile_all), n0 = tile_n0<BN>(p.order, p.nbm, p.nbn, tile_all);
     const int lr = lane >> 3;
     const int c8 = (lane & 7) ^ lr;
 
-    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.A1, 0, (int)p.a1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wt, 0, (int)p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = buf_rsrc(p.A1, (int)p.a1_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.Wt, (int)p.w_bytes);
     // one per-lane offset per operand + a uniform stride per 8-row piece group (rows >= M: past the descriptor's extent, read as zeros)
     const unsigned a_base = (unsigned)(m0 + wave * 8 + lr) * (unsigned)p.lda1 + c8 * 16u;
     const unsigned a_step = (unsigned)(NW * 8) * (unsigned)p.lda1;
@@ -54,28 +54,23 @@ __global__ __launch_bounds__(NW * 64) void gemm3x8_kernel(GemmArgs p) {
     const unsigned w_step = (unsigned)(NW * 8) * (unsigned)p.ldw;
 
     const int nk_all = (p.K + KE - 1) / KE;
-    const int kbeg = (int)((int64_t)nk_all * slice / nsplit);
-    const int nk = (int)((int64_t)nk_all * (slice + 1) / nsplit) - kbeg;
+    const int csteps = MODE == 2 ? p.Cin / KE : 1;
+    const KSlice ks(nk_all, slice, nsplit, csteps);
+    const int kbeg = ks.kbeg, nk = ks.nk;
     const bool ktail = (p.K % KE) != 0;
 
     // conv view: per-lane pixel coordinates of this lane's row in each of its RA pieces; a K-step = 128 channels of one tap
-    int a_ih[RA], a_iw[RA];
-    unsigned a_img[RA], a_off[RA];
-    bool a_ok[RA];
-    const int csteps = MODE == 2 ? p.Cin / KE : 1;
-    int ftap = kbeg / csteps, cs = kbeg - ftap * csteps;
+    const ConvGeom g = conv_geom(p, 0);                              // 3x3 taps only: the launcher refuses the 2x2 parity convs with fp8 activations (gemm_conv.hip, run_code)
+    unsigned a_off[RA];                                              // in front of a_row: behind it, two conv views build their kOob constants in another order
+    ConvRow a_row[RA];
+    unsigned a_img[RA];
+    int ftap = ks.ftap, cs = ks.cs;
     bool tap_fresh = true;
     if constexpr (MODE == 2) {
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
-            const int m = m0 + (wave + NW * i) * 8 + lr;
-            a_ok[i] = m < p.M;
-            const int hw = p.OH * p.OW;
-            const int b = m / hw, rem = m - b * hw;
-            const int oh = rem / p.OW, ow = rem - oh * p.OW;
-            a_ih[i] = oh * p.stride - p.pt;
-            a_iw[i] = ow * p.stride - p.pl;
-            a_img[i] = (unsigned)b * (unsigned)(p.H * p.W) * (unsigned)p.Cin;
+            a_row[i] = conv_row(g, m0 + (wave + NW * i) * 8 + lr);
+            a_img[i] = (unsigned)a_row[i].b * (unsigned)(p.H * p.W) * (unsigned)p.Cin;
             a_off[i] = kOob;
         }
     }
@@ -87,14 +82,10 @@ __global__ __launch_bounds__(NW * 64) void gemm3x8_kernel(GemmArgs p) {
         if constexpr (MODE == 2) {
             if (cs == 0 || tap_fresh) {
                 tap_fresh = false;
-                const int ky = (ftap * 11) >> 5, kx = ftap - 3 * ky;
-                const int hlim = p.H << p.ups, wlim = p.W << p.ups;
+                const TapYX t = tap_yx(g, ftap);
 #pragma unroll
-                for (int i = 0; i < RA; ++i) {
-                    const int ih = a_ih[i] + ky, iw = a_iw[i] + kx;
-                    const bool ok = a_ok[i] && ih >= 0 && ih < hlim && iw >= 0 && iw < wlim;
-                    a_off[i] = ok ? a_img[i] + (unsigned)((ih >> p.ups) * p.W + (iw >> p.ups)) * (unsigned)p.Cin + c8 * 16u : kOob;
-                }
+                for (int i = 0; i < RA; ++i)          // one byte per element here
+                    a_off[i] = conv_inside(g, a_row[i], t.ky, t.kx) ? a_img[i] + (unsigned)conv_index(g, a_row[i], t.ky, t.kx) * (unsigned)p.Cin + c8 * 16u : kOob;
             }
             const unsigned soa = (unsigned)cs * KE;
 #pragma unroll
@@ -126,7 +117,7 @@ __global__ __launch_bounds__(NW * 64) void gemm3x8_kernel(GemmArgs p) {
     }
     f32x4 ws[LEAN ? FN : 1];                                     // LEAN: the dequantisation scales of the lane's columns ride along with the bias row
     if constexpr (LEAN) {
-        const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w_scale), 0, p.N * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsw = buf_rsrc(p.w_scale, p.N * 4);
 #pragma unroll
         for (int i = 0; i < FN; ++i) ws[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, (unsigned)(n0 + wn * WN + i * 16 + (lane >> 4) * 4) * 4u, 0, 0));
     }
