@@ -1,4 +1,4 @@
-// The arithmetic the image-side kernels share, stated once (resize, mask, mask_fill, fullres, metrics, clip_score, dino, pointwise .hip).
+// The arithmetic the image-side kernels share, stated once (resize, mask, mask_fill, multiband, fullres, metrics, clip_score, dino, pointwise .hip).
 // Kernels that must agree bit for bit -- the fused full-resolution paste with the resize + mask_prep + composite sequence, the two patchify
 // kernels with each other's K order -- agree because they call the same function here, not because one restates the other.
 #pragma once
@@ -87,6 +87,57 @@ __device__ __forceinline__ float feather_vsum(const float* __restrict__ hrow, co
 __device__ __forceinline__ uint8_t blend_u8(float m, float d, uint8_t s) {
     const float sf = (float)s;
     return m <= 0.f ? s : (uint8_t)rintf(m >= 1.f ? d : m * d + (1.f - m) * sf);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the multi-band blend
+// One-sided Laplacian-pyramid paste-back (tests/multiband_oracle.py restates it).  Signed 32-bit integers throughout:
+// a cell is an int4 {D_r, D_g, D_b, G} (difference edit - source in 1/16 levels, mask in 1/256) or {C_r, C_g, C_b, -} (the collapsed bands).
+// |D| <= 4080 and 0 <= G <= 256, so a level is stored as short4; |Lap| <= 8160, every product and sum stays under 2^23.  >> floors.
+constexpr int kBandMaxLevels = 6;
+
+// level 0, never stored: D_0 = 16 (A - S), G_0 = 256 m
+__device__ __forceinline__ int4 band_level0(const uint8_t* a, const uint8_t* s, uint8_t mask_l) {
+    return make_int4(16 * ((int)a[0] - (int)s[0]), 16 * ((int)a[1] - (int)s[1]), 16 * ((int)a[2] - (int)s[2]), mask_l >= 128 ? 256 : 0);
+}
+
+// reduce: one axis of the 1-4-6-4-1 binomial over p[0], p[stride], .. p[4 stride]; the 2-D sum (two such passes) is rounded once
+__device__ __forceinline__ int4 band_reduce5(const int4* p, int stride) {
+    const int4 a = p[0], b = p[stride], c = p[2 * stride], d = p[3 * stride], e = p[4 * stride];
+    return make_int4(a.x + 4 * b.x + 6 * c.x + 4 * d.x + e.x, a.y + 4 * b.y + 6 * c.y + 4 * d.y + e.y, a.z + 4 * b.z + 6 * c.z + 4 * d.z + e.z,
+                     a.w + 4 * b.w + 6 * c.w + 4 * d.w + e.w);
+}
+__device__ __forceinline__ int band_reduce_round(int sum) { return (sum + 128) >> 8; }
+
+// expand: the weights of one axis for output index i over the parents (i >> 1) - 1, i >> 1, (i >> 1) + 1 -- 1 6 1 at even i, 4 4 at odd
+__device__ __forceinline__ void band_expand_weights(int i, int (&wt)[3]) {
+    wt[0] = (i & 1) ? 0 : 1;
+    wt[1] = (i & 1) ? 4 : 6;
+    wt[2] = (i & 1) ? 4 : 1;
+}
+// the expanded value's three channels; `centre`: the parent cell (y >> 1, x >> 1) in a staged tile of `pitch` cells a row whose halo
+// holds the clamped neighbours
+__device__ __forceinline__ void band_expand3(const int4* centre, int pitch, const int (&wy)[3], const int (&wx)[3], int (&e)[3]) {
+    int s[3] = {0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const int4 v = centre[(a - 1) * pitch + (b - 1)];
+            const int wt = wy[a] * wx[b];
+            s[0] += wt * v.x; s[1] += wt * v.y; s[2] += wt * v.z;
+        }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) e[c] = (s[c] + 32) >> 6;
+}
+
+// the one-sided ramp W = max(0, 2 G - 256) and a band weighted by it
+__device__ __forceinline__ int band_weight(int g) { return max(0, 2 * g - 256); }
+__device__ __forceinline__ int band_mix(int wt, int v) { return (wt * v + 128) >> 8; }
+
+// one byte of the result: B = clamp(S + ((C_0 + 8) >> 4), 0, 255), or with the feathered mask m the paste-back of B
+__device__ __forceinline__ uint8_t band_out(uint8_t s, int c0, const float* m) {
+    const int b = min(max((int)s + ((c0 + 8) >> 4), 0), 255);
+    return m ? blend_u8(*m, (float)b, s) : (uint8_t)b;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- patchify

@@ -854,6 +854,37 @@ class Context:
         _chk(lib().fie_mask_fill_rgb_u8(self.h, _p(src_u8), _p(mask_l), h, w, _p(ws), _p(out), _p(ctl_u8), _p(cleared)))
         return out, cleared
 
+    def multiband_workspace(self, h, w, levels):
+        """The pyramid workspace of multiband_blend for an h x w image: a fresh int32 allocation of the caller's stream (a capture keeps it)."""
+        nbytes = lib().fie_multiband_workspace_bytes(h, w, int(levels))
+        if nbytes < 0:
+            raise FieError(f"multiband_blend: {h} x {w} with {levels} levels is outside 1 .. 2^24 pixels, 1 .. 6 levels")
+        return self._alloc((nbytes // 8, 2), torch.int32)
+
+    def multiband_blend(self, edit_u8, source_u8, mask_l, alpha=None, levels=4, out=None, workspace=None):
+        """The one-sided multi-band paste-back (fie_multiband_blend_rgb_u8; DESIGN.md section 15).  edit_u8: u8 [H, W, 3], the decoded image;
+        source_u8: u8 [H, W, 3], the resized source; mask_l: u8 [H, W] (edited = L >= 128).  -> u8 [H, W, 3]: the full blended image B, or with
+        `alpha` (f32 [H, W], mask_prep's mask_px) its paste-back against the source.  `out`: a contiguous u8 [H, W, 3] tensor to write (no
+        operand); `workspace`: multiband_workspace()'s, for a caller that keeps one.  No synchronisation, 2 * levels launches."""
+        self.sync_stream()
+        h, w = mask_l.shape
+        u8img = lambda t: tuple(t.shape) == (h, w, 3) and t.dtype == torch.uint8 and t.is_contiguous()
+        if mask_l.dtype != torch.uint8 or not mask_l.is_contiguous() or not u8img(edit_u8) or not u8img(source_u8):
+            raise ValueError(f"multiband_blend: contiguous u8 [H, W, 3] images and a u8 [H, W] mask, got {tuple(edit_u8.shape)} {edit_u8.dtype}, "
+                             f"{tuple(source_u8.shape)} {source_u8.dtype} and {tuple(mask_l.shape)} {mask_l.dtype}")
+        if alpha is not None and (tuple(alpha.shape) != (h, w) or alpha.dtype != torch.float32 or not alpha.is_contiguous()):
+            raise ValueError(f"multiband_blend: alpha must be contiguous f32 {(h, w)}, got {tuple(alpha.shape)} {alpha.dtype}")
+        if out is None:
+            out = self._alloc((h, w, 3), torch.uint8)
+        elif not u8img(out) or any(out.data_ptr() == t.data_ptr() for t in (edit_u8, source_u8)):
+            raise ValueError(f"multiband_blend: out must be a contiguous u8 {(h, w, 3)} tensor of its own")
+        ws = workspace if workspace is not None else self.multiband_workspace(h, w, levels)
+        need = lib().fie_multiband_workspace_bytes(h, w, int(levels))
+        if need < 0 or ws.numel() * ws.element_size() < need:
+            raise ValueError(f"multiband_blend: {h} x {w} with {levels} levels needs a workspace of {need} bytes")
+        _chk(lib().fie_multiband_blend_rgb_u8(self.h, _p(edit_u8), _p(source_u8), _p(mask_l), _p(alpha), h, w, int(levels), _p(ws), _p(out)))
+        return out
+
     def pixels_out_composite(self, x_nhwc, source_u8, mask_px):
         """pixels_out() with the paste-back: the source bytes where mask_px == 0, the decoded ones where it is 1, the rounded blend between."""
         self.sync_stream()

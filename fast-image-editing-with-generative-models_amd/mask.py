@@ -14,6 +14,8 @@ from . import header
 CONTENT_CODES = {n[len("CONTENT_"):].lower(): v for n, v in header.DEFINES.items() if n.startswith("CONTENT_")}
 CONTENT_MODES = tuple(sorted(CONTENT_CODES, key=CONTENT_CODES.get))
 MAX_BLUR = 21          # radius ceil(3 r) <= 64: the LDS bound of fie_mask_prep
+BLEND_MODES = ("alpha", "multiband")      # blend: the paste-back as ever, or the one-sided multi-band blend
+MAX_BLEND_LEVELS = 6                      # fie_multiband_blend_rgb_u8's bound
 
 
 def to_l_array(mask, size=None):
@@ -58,6 +60,19 @@ def check_content(masked_content, have_mask=True):
     if masked_content != "original" and not have_mask:
         raise ValueError(f"masked_content={masked_content!r} needs a mask")
     return masked_content
+
+
+def check_blend(blend, blend_levels=4, have_mask=True, paste_back=True):
+    """The argument rules of `blend` / `blend_levels` (how the paste-back meets the source); returns (name, levels)."""
+    if not isinstance(blend, str) or blend not in BLEND_MODES:
+        raise ValueError(f"blend={blend!r}: one of {', '.join(repr(m) for m in BLEND_MODES)}")
+    if isinstance(blend_levels, bool) or not isinstance(blend_levels, (int, np.integer)) or not 1 <= blend_levels <= MAX_BLEND_LEVELS:
+        raise ValueError(f"blend_levels={blend_levels!r}: an integer in 1..{MAX_BLEND_LEVELS}")
+    if blend != "alpha" and not have_mask:
+        raise ValueError(f"blend={blend!r} needs a mask")
+    if blend != "alpha" and not paste_back:
+        raise ValueError(f"blend={blend!r} is a paste-back: it needs paste_back=True")
+    return blend, int(blend_levels)
 
 
 def blur_radius(r):

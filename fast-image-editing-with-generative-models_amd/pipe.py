@@ -138,15 +138,20 @@ class HipImg2ImgPipeline:
 
     def prepare(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                 num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
-                mask_image=None, mask_blur=0, paste_back=True, *, masked_content="original"):
+                mask_image=None, mask_blur=0, paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False):
         """`image` / `control_image`: PIL images, or u8 [H, W, 3] tensors already on the device (FastEditor.edit keeps the
         resized source and its device-side Canny map in HBM instead of bouncing them through PIL).  `mask_image` (additive, diffusers'
         name): restricts the edit to its white region -- a PIL image, a uint8 / bool [H, W] array, or a u8 [H, W]
         device tensor, at the image's size; `mask_blur` feathers and `paste_back` (default) enables the paste-back of the source.
         `masked_content` (additive; needs a mask): what the model starts from inside the mask -- "original" the source, "fill" a smooth
-        continuation of the surroundings, "latent_noise" pure noise, "latent_nothing" the zero latent plus noise."""
+        continuation of the surroundings, "latent_noise" pure noise, "latent_nothing" the zero latent plus noise.
+        `blend` (additive; needs a mask and the paste-back): "alpha" the paste-back as ever, "multiband" the one-sided multi-band blend over
+        `blend_levels` (1..6) pyramid levels -- the decoded image's low-frequency difference to the source fades out towards the seam, outside the
+        mask the output stays the source's bytes.  `paste_later`: the caller composites the result itself behind the job
+        (FastEditor's source-size back end): a "multiband" job with paste_back=False then returns the blended image B uncomposited."""
         return self._prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content)
+                             controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content,
+                             hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later))
 
     def _mask_job(self, mask_image, mask_blur, paste_back, h, w):
         """Mask tensors of one image: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back, the edit-size L mask
@@ -167,7 +172,8 @@ class HipImg2ImgPipeline:
         return m_lat[None], (m_px[None] if paste_back else None), lm[None]
 
     def _prepare(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                 controlnet_conditioning_scale, generator, mask_image=None, mask_blur=0, paste_back=True, masked_content="original"):
+                 controlnet_conditioning_scale, generator, mask_image=None, mask_blur=0, paste_back=True, masked_content="original",
+                 blend=("alpha", 4)):
         """Host side of one call: argument checks, tokenisation, RNG draws (in upstream order: posterior sample, init
         noise, one per non-final step) and the H2D copies.  Returns the device-resident job for run_device()."""
         ctx = self.ctx
@@ -217,7 +223,14 @@ class HipImg2ImgPipeline:
             time_ids=const[0], t_dev=const[1],
             noises=[self._randn((1, 4, lh, lw), generator) for _ in range(n_noise)],
             mask_lat=mask_lat, mask_px=mask_px, mask_cfg=None if mask_lat is None else (float(mask_blur), bool(paste_back)),
-            **self._content_job(content, mask_l, mask_lat))
+            **self._content_job(content, mask_l, mask_lat), **self._blend_job(blend, mask_l))
+
+    @staticmethod
+    def _blend_job(blend, blend_l):
+        """The job entries of blend="multiband" (DESIGN.md section 15); none with "alpha", whose job is what it was.  `blend_l`: the edit-size L
+        mask u8 [1, h, w] that the blend reads inside the device job -- the image's own mask, or all 255 for an image of a batch that has none
+        (everything is inside: the blend returns the decoded bytes)."""
+        return {} if blend[0] == "alpha" else dict(blend=(blend[0], int(blend[1])), blend_l=blend_l)
 
     @staticmethod
     def _content_job(content, mask_l, content_lat):
@@ -233,12 +246,13 @@ class HipImg2ImgPipeline:
 
     def prepare_batch(self, prompts, negative_prompts, images, control_images, strength=0.8, num_inference_steps=4,
                       guidance_scale=1.5, controlnet_conditioning_scale=0.5, generators=None, mask_image=None, mask_blur=0,
-                      paste_back=True, *, masked_content="original"):
+                      paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False):
         """[additive] n independent edits as ONE device job (BASELINE config "batch=8"): the UNet / ControlNet / CLIP run
         at batch n * nb, the VAE per image.  Rows are image-major ([img0 uncond, img0 cond, img1 uncond, ...]); each
         image keeps its own generator, so image i of a batch draws exactly the noise a single call with that generator
         draws (upstream: a list of generators, one per prompt).  `mask_image`: None, or one mask per image (None in the
-        list = edit everywhere).  `masked_content`: one mode for the call (prepare()); an image without a mask is edited as ever."""
+        list = edit everywhere).  `masked_content`: one mode for the call (prepare()); an image without a mask is edited as ever.  `blend` / `blend_levels` /
+        `paste_later`: prepare()'s, one value for the call; an image without a mask comes out as without the keyword."""
         n = len(prompts)
         if not (n == len(images) == len(control_images)) or n == 0:
             raise ValueError("prompts, images and control_images must be non-empty lists of one length")
@@ -248,12 +262,14 @@ class HipImg2ImgPipeline:
         masked = any(m is not None for m in masks)
         hmask.check_args(mask_blur, paste_back, masked)
         content = hmask.check_content(masked_content, masked)
+        blend = hmask.check_blend(blend, blend_levels, masked, paste_back or paste_later)
         negative_prompts = negative_prompts or [""] * n
         generators = generators or [None] * n
         jobs = [self._prepare(prompts[i], negative_prompts[i], images[i], control_images[i], strength, num_inference_steps,
                               guidance_scale, controlnet_conditioning_scale, generators[i], masks[i],
                               mask_blur if masks[i] is not None else 0, paste_back,
-                              content if masks[i] is not None else "original") for i in range(n)]
+                              content if masks[i] is not None else "original",
+                              blend if masks[i] is not None else ("alpha", 4)) for i in range(n)]
         if any(j["hw"] != jobs[0]["hw"] for j in jobs):
             raise ValueError("all images of a batch must have one size")
         if masked:                                        # an image without a mask edits everywhere: an all-ones mask
@@ -266,6 +282,7 @@ class HipImg2ImgPipeline:
                     # no mask of its own: an empty hole -- nothing filled, no edge cleared, no latent replaced
                     j.update(self._content_job(content, torch.zeros((1, h, w), device=self.ctx.device, dtype=torch.uint8),
                                                torch.zeros((1, (h // 8) * (w // 8)), device=self.ctx.device, dtype=torch.uint8)))
+                    j.update(self._blend_job(blend, torch.full((1, h, w), 255, device=self.ctx.device, dtype=torch.uint8)))
         if n == 1:
             return jobs[0]                                # the single-image job (and its graph)
         nb, t77 = jobs[0]["nb"], jobs[0]["ids_g"].shape[1]
@@ -401,7 +418,10 @@ class HipImg2ImgPipeline:
             self._mark("lcm_step")
         # 8-9. decode + postprocess
         dec = (lambda z: cabi.vae_decode(self.vae, z)) if self.cpp_walks else self.vae.decode
-        if mask_px is None:
+        if job.get("blend"):                              # the one-sided multi-band paste-back: B takes the decoded image's place
+            outs = [ctx.multiband_blend(ctx.pixels_out(dec(decode_in[i:i + 1])), imgs[i], job["blend_l"][i],
+                                        None if mask_px is None else mask_px[i], job["blend"][1]) for i in range(n)]
+        elif mask_px is None:
             outs = [ctx.pixels_out(dec(decode_in[i:i + 1])) for i in range(n)]
         else:                                             # paste-back of the source outside the (feathered) mask
             outs = [ctx.pixels_out_composite(dec(decode_in[i:i + 1]), imgs[i], mask_px[i]) for i in range(n)]
@@ -488,7 +508,8 @@ class HipImg2ImgPipeline:
     MAX_FORKED_GRAPHS = 6
 
     _TENSOR_KEYS = ("ids_l", "ids_g", "eos_rows", "img_u8", "ctl_u8", "time_ids")
-    _MASK_KEYS = ("mask_lat", "mask_px", "mask_l", "content_lat")      # the last two: a masked-content mode's
+    # mask_l, content_lat: a masked-content mode's; blend_l: the multi-band blend's (section 15)
+    _MASK_KEYS = ("mask_lat", "mask_px", "mask_l", "content_lat", "blend_l")
 
     def run_device_graphed(self, job, slot=0):
         """run_device() replayed from a hipGraph: the ~2 500 launches of one edit are captured once per
@@ -498,7 +519,8 @@ class HipImg2ImgPipeline:
         flight on different streams of one GPU."""
         base = (job["hw"], job["nb"], tuple(st["t"] for st in job["steps"]), job["guidance"], job["cn_scale"], slot, job.get("n", 1))
         if job.get("mask_lat") is not None:              # masked: (masked, mask_blur, paste_back); an unmasked key is what it was
-            base = base + ((True,) + job["mask_cfg"] + ((job["content"],) if job.get("content") else ()),)      # + the masked-content mode, unless "original"
+            # + the masked-content mode, unless "original"; + ("multiband", levels), unless the blend is "alpha"
+            base = base + ((True,) + job["mask_cfg"] + ((job["content"],) if job.get("content") else ()) + ((job["blend"],) if job.get("blend") else ()),)
         # A forked graph owns extra runtime streams; past ~8 such graphs in one process new ones start sharing hardware queues
         # with their own launch stream and replay 50 % slower (measured: 82 -> 125 ms, tools/edit_ab.py).  Beyond the budget a
         # new key is captured on one stream instead (87 ms): slower than a healthy forked graph, never pathological.
@@ -629,7 +651,7 @@ class HipImg2ImgPipeline:
     def __call__(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                  num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
                  output_type="pil", slot=0, post_check=None, mask_image=None, mask_blur=0, paste_back=True, after_device=None, *,
-                 masked_content="original", **unused):
+                 masked_content="original", blend="alpha", blend_levels=4, paste_later=False, **unused):
         """`slot` (additive): independent hipGraph instance + stream, so that several calls may be in flight from different
         host threads on one GPU (graph mode only).  `post_check` (additive): a callable run after the result has reached the host
         (the stream is idle then); when it returns True the device-resident inputs have changed meanwhile and the device job is run
@@ -637,7 +659,7 @@ class HipImg2ImgPipeline:
         number of hysteresis rounds in front of the edit, and whether they had reached the fixed point is only looked at here --
         no host wait in front of the edit, a repeated job in the rare case that they had not.  `mask_image` / `mask_blur` / `paste_back`
         (additive): a mask-restricted edit (prepare(); a list of masks for a batch call); `masked_content`: what it starts from inside the mask
-        (prepare()).  `after_device` (additive): a callable given the u8 result
+        (prepare()); `blend` / `blend_levels` / `paste_later`: how the paste-back meets the source (prepare()).  `after_device` (additive): a callable given the u8 result
         while it is still on the device, on the slot's stream behind the device job and outside its graph; it may queue more work there (FastEditor
         scores the edit) and whatever it returns comes back as `.extra`, complete once the image has reached the host.  A hook that returns a
         `DeviceOutput` replaces the image: its tensor(s) take the final device-to-host copy (FastEditor's full-resolution back end)."""
@@ -648,7 +670,7 @@ class HipImg2ImgPipeline:
         with torch.cuda.stream(st):
             out = self._call(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                              controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back), after_device,
-                             masked_content)
+                             masked_content, dict(blend=blend, blend_levels=blend_levels, paste_later=paste_later))
         caller.wait_stream(st)
         return out
 
@@ -682,7 +704,9 @@ class HipImg2ImgPipeline:
 
     def _call(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
               controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_args=(None, 0, True), after_device=None,
-              masked_content="original"):
+              masked_content="original", blend_kw=None):
+        blend_kw = blend_kw or {}
+
         def run(job):
             """One device job, the caller's after_device hook behind it, then the result on the host: -> (u8 array, hook's return)."""
             out_u8 = self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
@@ -695,7 +719,7 @@ class HipImg2ImgPipeline:
             job = self.prepare_batch(list(prompt), negative_prompt if isinstance(negative_prompt, (list, tuple)) else None,
                                      list(image), list(control_image), strength, num_inference_steps, guidance_scale,
                                      controlnet_conditioning_scale, generator if isinstance(generator, (list, tuple)) else None, *mask_args,
-                                     masked_content=masked_content)
+                                     masked_content=masked_content, **blend_kw)
             arr, extra = run(job)
             if post_check is not None and post_check():
                 arr, extra = run(job)
@@ -705,7 +729,7 @@ class HipImg2ImgPipeline:
                 return types.SimpleNamespace(images=list(arr), extra=extra)
             return types.SimpleNamespace(images=[Image.fromarray(a) for a in arr], extra=extra)
         job = self.prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps,
-                           guidance_scale, controlnet_conditioning_scale, generator, *mask_args, masked_content=masked_content)
+                           guidance_scale, controlnet_conditioning_scale, generator, *mask_args, masked_content=masked_content, **blend_kw)
         if output_type == "latent":
             self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
             res = job["_result"]

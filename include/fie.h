@@ -582,6 +582,24 @@ int fie_latent_prep_src_content_f32(fie_ctx* ctx, const void* moments, const flo
                                     float scaling_factor, float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in,
                                     int copies, float* z0_out, const uint8_t* mask_lat, int mode);
 
+/* ---- One-sided multi-band paste-back of a mask-restricted edit: the seam of a masked edit without a wide alpha ramp.
+ *   fie_multiband_blend_rgb_u8   edit u8 [H, W, 3] (A: what fie_pixels_out_* wrote), source u8 [H, W, 3] (S: the resized source), mask_l u8 [H, W]
+ *      (m = L >= 128), any H, W >= 1 with H * W <= 2^24, levels L in 1 .. 6.  out u8 [H, W, 3] (aliases no operand).
+ *      Signed 32-bit integers, >> floors; level k has sides h_k+1 = (h_k + 1) >> 1.  D_0 = 16 (A - S), G_0 = 256 m; D_k+1 = reduce(D_k),
+ *      G_k+1 = reduce(G_k), reduce = the 5x5 binomial [1 4 6 4 1]^2 at (2Y, 2X), indices clamped, (sum + 128) >> 8.  expand(g) at index i per
+ *      axis: parents (i >> 1) - 1, i >> 1, (i >> 1) + 1 (clamped) weighted 1 6 1 for even i, 0 4 4 for odd; the 2-D sum (+ 32) >> 6.
+ *      W_k = max(0, 2 G_k - 256).  C_L = (W_L D_L + 128) >> 8; C_k = ((W_k (D_k - expand(D_k+1)) + 128) >> 8) + expand(C_k+1);
+ *      B = clamp(S + ((C_0 + 8) >> 4), 0, 255).  Exact to the bit (tests/multiband_oracle.py restates it in numpy).
+ *      alpha == NULL: out = B.  Otherwise alpha is f32 [H, W] (fie_mask_prep's mask_px) and out = source where alpha <= 0, B where alpha >= 1,
+ *      rint(alpha B + (1 - alpha) source) between, in f32 without fused multiply-adds.
+ *      workspace: fie_multiband_workspace_bytes(H, W, levels) bytes (-1 for what the op refuses), 16-byte aligned: levels 1 .. L of D, G and C;
+ *      level 0 is recomputed from the images.  Every byte the op reads from it, it has written before.
+ *      Launches: 2 L (8 at L = 4) -- one reduce per level (three difference channels and the mask in one pass), one collapse per level from the
+ *      top down, the last over the image.  Asynchronous on the ctx stream; no block waits for another, no atomics. */
+int64_t fie_multiband_workspace_bytes(int H, int W, int levels);
+int fie_multiband_blend_rgb_u8(fie_ctx* ctx, const uint8_t* edit, const uint8_t* source, const uint8_t* mask_l, const float* alpha, int H,
+                               int W, int levels, void* workspace, uint8_t* out);
+
 /* ---- Full-resolution back end of an edit: the edit-size result at the source's size, composited against the
  * source's own bytes.  res: u8 [h, w, 3], the edit-size result.  The output is H x W: up = Pillow's 8-bit LANCZOS resize of res to
  * (W, H), bit-exact (kx / bx / ksx, ky / by / ksy: the tables of fie_resize_rgb_u8 for w -> W and h -> H; a table is NULL on an axis

@@ -86,6 +86,17 @@ def add_mask_args(p):
     return p
 
 
+def add_blend_args(p):
+    """[additive] the one-sided multi-band paste-back.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--blend", type=str, default="alpha", choices=["alpha", "multiband"],
+                   help="[additive] with --use_mask: how the edited region meets the source -- 'alpha' the paste-back as ever, 'multiband' a one-sided "
+                        "multi-band blend: the edit keeps its detail, its brightness / colour difference to the source fades out towards the seam, "
+                        "and outside the mask the output stays the source's bytes")
+    p.add_argument("--blend_levels", type=int, default=4, choices=range(1, 7), metavar="N",
+                   help="[additive] with --blend multiband: pyramid levels, 1..6; the difference fades over about 2^N pixels")
+    return p
+
+
 def add_resolution_args(p):
     """[additive] aspect-ratio edits.  Kept apart from build_parser() for the same reason as add_mask_args."""
     p.add_argument("--resolution", type=str, default="square",
@@ -240,6 +251,11 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
         if not use_mask:
             raise ValueError("--masked_content needs --use_mask")
         extra = dict(extra, masked_content=masked_content)
+    blend = getattr(args, "blend", "alpha")
+    if blend != "alpha":
+        if not use_mask:
+            raise ValueError("--blend multiband needs --use_mask")
+        extra = dict(extra, blend=blend, blend_levels=getattr(args, "blend_levels", 4))
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
     def flush():
@@ -345,12 +361,14 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    parser = add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_mask_args(build_parser()))))))
+    parser = add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_blend_args(add_mask_args(build_parser())))))))
     args = parser.parse_args(argv)
     if args.region == "mask" and not args.use_mask:
         parser.error("--region mask needs --use_mask")
     if args.masked_content != "original" and not args.use_mask:
         parser.error("--masked_content needs --use_mask")
+    if args.blend != "alpha" and not args.use_mask:
+        parser.error("--blend multiband needs --use_mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets

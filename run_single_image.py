@@ -49,6 +49,12 @@ def build_parser():
       help="[additive] with --mask: what the model starts from inside the mask -- 'original' the source, 'fill' a smooth continuation of the "
            "surroundings (object removal), 'latent_noise' pure noise, 'latent_nothing' the zero latent plus noise; the three new modes also clear "
            "the edge map inside the mask")
+    a("--blend", type=str, default="alpha", choices=["alpha", "multiband"],
+      help="[additive] with --mask: how the edited region meets the source -- 'alpha' the paste-back as ever (one ramp, --mask_blur), 'multiband' a "
+           "one-sided multi-band blend: the edit keeps its detail, its brightness / colour difference to the source fades out towards the seam, "
+           "and outside the mask the output stays the source's bytes")
+    a("--blend_levels", type=int, default=4, choices=range(1, 7), metavar="N",
+      help="[additive] with --blend multiband: pyramid levels, 1..6; the difference fades over about 2^N pixels")
     a("--resolution", type=str, default="square",
       help="[additive] output size: 'square' (1024x1024, the reference's), 'auto' (the SDXL aspect-ratio bucket nearest the source's) or WxH "
            "(multiples of 64, 512..2048, at most 1024^2 pixels)")
@@ -92,6 +98,8 @@ def main(argv=None):
         parser.error("--region mask needs --mask")
     if args.masked_content != "original" and args.mask is None:
         parser.error("--masked_content needs --mask")
+    if args.blend != "alpha" and (args.mask is None or args.no_paste_back):
+        parser.error("--blend multiband needs --mask and the paste-back")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets
@@ -133,6 +141,9 @@ def main(argv=None):
         if args.masked_content != "original":
             extra.update(masked_content=args.masked_content)
             print(f"      Masked content: {args.masked_content}")
+        if args.blend != "alpha":
+            extra.update(blend=args.blend, blend_levels=args.blend_levels)
+            print(f"      Blend: {args.blend}, {args.blend_levels} levels")
     if args.resolution != "square":
         extra.update(resolution=args.resolution)
     if args.region == "mask":

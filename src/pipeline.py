@@ -162,7 +162,8 @@ class FastEditor:
 
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
-             paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original"):
+             paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
+             blend="alpha", blend_levels=4):
         """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
         [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
         latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
@@ -193,16 +194,24 @@ class FastEditor:
         the source with the hole replaced by a smooth continuation of its surroundings before the encode (object removal); "latent_noise" pure
         noise; "latent_nothing" the zero latent plus noise.  The three new modes also clear the ControlNet's edge map inside the mask, so the old
         outline is not redrawn.  They act on the edit-size source inside the device job; paste-back, the source-size composite and the metrics
-        still use the original source."""
+        still use the original source.
+        [additive] `blend` (needs a mask and `paste_back`): how the edited region meets the source.  "alpha" (default) the paste-back as ever: one
+        ramp (`mask_blur`) for all frequencies.  "multiband" a one-sided multi-band blend over `blend_levels` (1..6, default 4) pyramid levels, run at
+        the edit size inside the device job: inside the mask the edit keeps all of its detail while its low-frequency difference to the source
+        (brightness, white balance, a slow gradient) fades to nothing towards the seam, over about 2^blend_levels pixels; outside the mask the
+        output stays the source's bytes, and `mask_blur`, the source-size composite, regions and the metrics take the blended image in place of
+        the decoded one.  A region smaller than about 2^(blend_levels + 2) pixels keeps less of its own low frequencies."""
         full = hregion.check_output(output_size, region)
         hmask.check_args(mask_blur, paste_back, mask is not None)
         hmask.check_content(masked_content, mask is not None)
+        hmask.check_blend(blend, blend_levels, mask is not None, paste_back)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
         if region is not None:
             box = hregion.resolve(region, image.size, mask_l, region_padding, resolution)
             res = self.edit(image.crop(box), prompt, negative_prompt, strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
                             canny_low_threshold, canny_high_threshold, seed, None if mask_l is None else mask_l[box[1]:box[3], box[0]:box[2]],
-                            mask_blur, paste_back, resolution=resolution, metrics=metrics, output_size="source", masked_content=masked_content)
+                            mask_blur, paste_back, resolution=resolution, metrics=metrics, output_size="source", masked_content=masked_content,
+                            blend=blend, blend_levels=blend_levels)
             if metrics:
                 return hregion.paste(image, res[0], box), res[1]
             return hregion.paste(image, res, box)
@@ -230,7 +239,8 @@ class FastEditor:
                         control_image=control_dev, strength=strength, num_inference_steps=num_inference_steps,
                         guidance_scale=guidance_scale, controlnet_conditioning_scale=controlnet_conditioning_scale,
                         generator=generator, post_check=finish, mask_image=mask_dev, mask_blur=0 if full else mask_blur,
-                        paste_back=paste_back and not full, after_device=hook, masked_content=masked_content)
+                        paste_back=paste_back and not full, after_device=hook, masked_content=masked_content, blend=blend,
+                        blend_levels=blend_levels, paste_later=full)
         if not metrics:
             return res.images[0]
         return res.images[0], self._scores(res.extra, [mask_l is not None])[0]
@@ -352,7 +362,8 @@ class FastEditor:
 
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
-                   paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original"):
+                   paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
+                   blend="alpha", blend_levels=4):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
         edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
@@ -363,12 +374,14 @@ class FastEditor:
         `output_size` / `region` / `region_padding`: as edit()'s; every image comes back at its own source's size, the back end queued per image
         behind the job.  `region` may also be a LIST with one entry per image (None, "mask" or a box): each image gets its own box, images are
         grouped by the target size of their crops, and an image whose entry is None is edited whole and returned at its source's size.
-        `masked_content`: as edit()'s, one value for the whole call; an image whose mask is None is edited as without it."""
+        `masked_content`: as edit()'s, one value for the whole call; an image whose mask is None is edited as without it.
+        `blend` / `blend_levels`: as edit()'s, one value for the whole call; an image whose mask is None comes out as without them."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
             raise ValueError(f"{len(masks)} masks for {len(images)} images: one mask (or None) per image")
         hmask.check_content(masked_content, masks is not None and any(m is not None for m in masks))
+        hmask.check_blend(blend, blend_levels, masks is not None and any(m is not None for m in masks), paste_back)
         regions = list(region) if isinstance(region, list) else [region] * len(images)
         if len(regions) != len(images):
             raise ValueError(f"{len(regions)} regions for {len(images)} images: one region (or None) per image")
@@ -382,7 +395,8 @@ class FastEditor:
             res = self.edit_batch([im if b is None else im.crop(b) for im, b in zip(images, boxes)], prompts, negative_prompts, strength,
                                   num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold,
                                   seed, None if masks is None else [cut(m, b) for m, b in zip(mls, boxes)], mask_blur, paste_back,
-                                  resolution=resolution, metrics=metrics, output_size="source", masked_content=masked_content)
+                                  resolution=resolution, metrics=metrics, output_size="source", masked_content=masked_content,
+                                  blend=blend, blend_levels=blend_levels)
             outs = [o if b is None else hregion.paste(im, o, b) for im, o, b in zip(images, res[0] if metrics else res, boxes)]
             return (outs, res[1]) if metrics else outs
         sizes = [buckets.target_size(resolution, im.size) for im in images]
@@ -398,7 +412,9 @@ class FastEditor:
                                       controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
                                       canny_high_threshold=canny_high_threshold, seed=seed, masks=pick(masks, idx), mask_blur=mask_blur,
                                       paste_back=paste_back, resolution=sz, metrics=metrics, output_size=output_size,
-                                      masked_content=masked_content if masks is not None and any(masks[i] is not None for i in idx) else "original")
+                                      masked_content=masked_content if masks is not None and any(masks[i] is not None for i in idx) else "original",
+                                      blend=blend if masks is not None and any(masks[i] is not None for i in idx) else "alpha",
+                                      blend_levels=blend_levels)
                 res, ms = res if metrics else (res, [None] * len(idx))
                 for i, r, m in zip(idx, res, ms):
                     out[i], mets[i] = r, m
@@ -430,7 +446,7 @@ class FastEditor:
                         strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                         controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens, mask_image=mask_devs,
                         mask_blur=0 if full else mask_blur, paste_back=paste_back and not full, after_device=hook,
-                        masked_content=masked_content)
+                        masked_content=masked_content, blend=blend, blend_levels=blend_levels, paste_later=full)
         if not metrics:
             return res.images
         return res.images, self._scores(res.extra, [m is not None for m in omasks])
