@@ -654,7 +654,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }  // namespace fie_gemm
 
 // gemm8.hip: the 256x256 phased kernel.  conv != 0: im2col view with Cin % 64 == 0.  Shapes must satisfy the LDS-DMA
-// eligibility rule of gemm_conv.hip (operands < 2 GiB, K1 == K or K1 % 64 == 0).
+// eligibility rule of gemm_conv.hip (operands < 2 GiB, K1 == K or K1 % 64 == 0 and K % 64 == 0).
 int fie_launch_gemm8(fie_ctx* ctx, const fie_gemm::GemmArgs& a, int conv, int split);
 int fie_gemm8_init(void);          // per-device function attributes (dynamic LDS size); called from fie_ctx_create
 int fie_gemm_init(void);           // same for the kernels of gemm_conv.hip

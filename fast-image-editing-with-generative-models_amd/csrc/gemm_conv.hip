@@ -245,7 +245,7 @@ __global__ __launch_bounds__(NW * 64) void gemm3_kernel(GemmArgs p) {
     const unsigned w_step = (unsigned)(NW * 8) * (unsigned)p.ldw * 2u;
 
     const int csteps = MODE == 2 ? p.Cin / BK : 1;
-    const int k1_steps = p.K1 / BK;            // GEMM: K-steps served by A1 (K1 % 64 == 0 unless K1 == K)
+    const int k1_steps = p.K1 / BK;            // GEMM: K-steps served by A1 (K1 % 64 == 0 and K % 64 == 0 unless K1 == K: launch<0>)
     const int nk_all = (p.K + BK - 1) / BK;
     const KSlice ks(nk_all, slice, nsplit, csteps);                    // this block's K-steps: [kbeg, kbeg + nk); all of them without split-K
     const int kbeg = ks.kbeg, nk = ks.nk;
@@ -834,7 +834,7 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
     const Tile* t = find_tile(code);
     FIE_REQUIRE(t != nullptr, "unknown tile code %d", code);
     const Family fam = t->family;
-    FIE_REQUIRE(fam == kGeneric || fam == kThin || dma_ok, "tile code %d: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0 or K1 %% 64 != 0)", code);
+    FIE_REQUIRE(fam == kGeneric || fam == kThin || dma_ok, "tile code %d: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0, or A = [A1 | A2] with K1 %% 64 != 0 or K %% 64 != 0)", code);
     FIE_REQUIRE(!(a.taps2 && (fam == kGeneric || a.w_scale)), "tile code %d: the 2x2 parity convs run on the f16 LDS-DMA kernels only", code);
     FIE_REQUIRE(!(MODE == 1 && a.A2 && (fam == kGeneric || fam == kPhased || a.w_scale)), "tile code %d: conv + 1x1 side inputs run on the f16 ring kernels and the halo-resident kernel (72) only", code);
     FIE_REQUIRE(!(fam == kHalo && (MODE != 1 || !dma_ok || !fie_conv_halo_ok(a))), "tile code %d (halo-resident conv): stride-1 same-size 3x3 conv with H, W %% 16 == 0, Cin %% 64 == 0, f16 weights only", code);
@@ -862,7 +862,7 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
         t = find_tile(t->x8);
         if (MODE == 1 && (t->flags & kGemmOnly)) t = find_tile(62);      // the 320-wide tile has no conv view: 256x128 stands in
     } else if (a.w_scale) {          // fp8 weights: the W8 ring tiles (gemm_w8.hip)
-        FIE_REQUIRE(dma_ok, "fp8 weights: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0 or K1 %% 64 != 0)");
+        FIE_REQUIRE(dma_ok, "fp8 weights: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0, or A = [A1 | A2] with K1 %% 64 != 0 or K %% 64 != 0)");
         t = find_tile(t->w8);
     }
     code = t->code;
@@ -1024,10 +1024,11 @@ int autotune(fie_ctx* ctx, GemmArgs& a, int guess, bool dma_ok) {
 template <int MODE>
 int launch(fie_ctx* ctx, GemmArgs& a) {
     // LDS-DMA kernels (codes >= 40): 32-bit buffer offsets (operands < 2 GiB) and K-steps that never straddle a 3x3 tap / the A1|A2 seam
+    // (A = [A1 | A2]: K1 AND K multiples of 64 -- the last, partial K-step of these kernels is issued from A1's descriptor, which is A2's tail there)
     // ... and an epilogue on 32-bit buffer offsets (gemm_common.h): output / residual spans of at most 1 GiB
     const int64_t c_span = ((int64_t)((a.oscat ? 4 * (int64_t)a.M : a.M) - 1) * a.ldc + a.N) * 2, r_span = a.res ? ((int64_t)(a.M - 1) * a.ldr + a.N) * 2 : 0;
     const bool dma_ok = a.a1_bytes < (1ll << 31) && a.a2_bytes < (1ll << 31) && a.w_bytes < (1ll << 31) && c_span <= (1ll << 30) && r_span <= (1ll << 30) &&
-                        (MODE == 1 ? a.Cin % (a.a_scale != 0.f ? 2 * BK : BK) == 0 : (a.K1 == a.K || a.K1 % BK == 0));
+                        (MODE == 1 ? a.Cin % (a.a_scale != 0.f ? 2 * BK : BK) == 0 : (a.K1 == a.K || (a.K1 % BK == 0 && a.K % BK == 0)));
     FIE_REQUIRE(!(MODE == 1 && a.A2 && !dma_ok), "conv + 1x1 side inputs: tensors too large for the LDS-DMA kernels");
     if (MODE == 1 && a.gna_tab) {                          // the input's GroupNorm applied on the resident halo: one kernel family, no choice to make
         FIE_REQUIRE(dma_ok && fie_conv_halo_gna_ok(a), "fie_conv3x3_gn_nhwc_f16: shape / epilogue not built for the fused form (ask fie_conv3x3_gn_ok first)");

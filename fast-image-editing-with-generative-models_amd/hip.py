@@ -536,13 +536,14 @@ class Context:
         out._gn_tag = None
         return out
 
-    def conv3x3_plus(self, x, wp, cout, x2, x3=None, bias=None, rowbias=None, scale=1.0, act=ACT_NONE, gn_groups=None):
+    def conv3x3_plus(self, x, wp, cout, x2, x3=None, bias=None, rowbias=None, scale=1.0, act=ACT_NONE, gn_groups=None, out=None):
         """conv3x3(x) + [x2 | x3] @ W1x1^T in one GEMM (include/fie.h: fie_conv3x3_plus_nhwc_f16); x2 / x3: [B*H*W, C] views, last dim contiguous."""
         self.sync_stream()
         self._bind_splitk()
         b, h, w, cin = x.shape
         assert x.is_contiguous() and not self.f32 and x2.stride(1) == 1 and (x3 is None or x3.stride(1) == 1)
-        out = self._alloc((b, h, w, cout))
+        if out is None:
+            out = self._alloc((b, h, w, cout))
         tag = self._gn_stats_arm(b * h * w, cout, h * w, gn_groups) if gn_groups else None
         _chk(lib().fie_conv3x3_plus_nhwc_f16(self.h, _p(x), b, h, w, cin, _p(wp), wp.stride(0), _p(out), out.stride(2), cout, _p(bias), _p(rowbias),
                                              rowbias.stride(0) if rowbias is not None else 0, float(scale), act, _p(x2), x2.stride(0), x2.shape[1],
@@ -562,13 +563,14 @@ class Context:
                 mats.append(self.pack_linear(torch.stack(taps, 1).reshape(w.shape[0], -1).to(torch.float16), quant=False))
         return torch.stack(mats).contiguous()
 
-    def conv_up2x(self, x, wp4, cout, bias=None, rowbias=None, scale=1.0, act=ACT_NONE, gn_groups=None):
+    def conv_up2x(self, x, wp4, cout, bias=None, rowbias=None, scale=1.0, act=ACT_NONE, gn_groups=None, out=None):
         """conv3x3(nearest-2x(x)) from the four parity matrices of pack_conv_up2x: x [B, H, W, Cin] -> [B, 2H, 2W, cout]."""
         self.sync_stream()
         self._bind_splitk()
         b, h, w, cin = x.shape
         assert x.is_contiguous() and not self.f32 and cin % 64 == 0
-        out = self._alloc((b, 2 * h, 2 * w, cout))
+        if out is None:
+            out = self._alloc((b, 2 * h, 2 * w, cout))
         tag = self._gn_stats_arm(b * 4 * h * w, cout, 4 * h * w, gn_groups) if gn_groups else None
         _chk(lib().fie_conv_up2x_nhwc_f16(self.h, _p(x), b, h, w, cin, _p(wp4), wp4.stride(1), wp4.shape[1], _p(out), out.stride(2), cout,
                                           _p(bias), _p(rowbias), rowbias.stride(0) if rowbias is not None else 0, float(scale), act))
@@ -695,13 +697,14 @@ class Context:
         _chk(lib().fie_groupnorm_coef_f16(self.h, c, b, rows, groups, _p(gamma), _p(beta), float(eps), _p(tag[0]), _p(ws), tag[7], _p(coef)))
         return coef
 
-    def conv3x3_gn(self, x, coef, silu, wp, cout, bias=None, residual=None, gn_groups=None):
+    def conv3x3_gn(self, x, coef, silu, wp, cout, bias=None, residual=None, gn_groups=None, out=None):
         """conv3x3(silu(x * sc + sh)) in one launch (fie_conv3x3_gn_nhwc_f16); the output's own GroupNorm sums are armed as for conv3x3."""
         self.sync_stream()
         self._bind_splitk()
         b, h, w, cin = x.shape
         assert x.is_contiguous() and coef.dtype == torch.float32 and coef.shape == (b, cin, 2)
-        out = self._alloc((b, h, w, cout))
+        if out is None:
+            out = self._alloc((b, h, w, cout))
         tag = self._gn_stats_arm(b * h * w, cout, h * w, gn_groups)
         assert tag is not None, "the fused GroupNorm -> conv needs the output's sums armed (conv3x3_gn_ok)"
         _chk(lib().fie_conv3x3_gn_nhwc_f16(self.h, _p(x), b, h, w, cin, _p(coef), int(bool(silu)), _p(wp), wp.stride(0), _p(out), out.stride(2), cout, _p(bias),
@@ -709,11 +712,12 @@ class Context:
         out._gn_tag = tag
         return out
 
-    def quantize_f8(self, x, inv_scale=1.0):
+    def quantize_f8(self, x, inv_scale=1.0, out=None):
         """[rows, C] f16 -> e4m3 bytes (value * inv_scale, saturated): the plain conversion (tests; producers without a fused form)."""
         self.sync_stream()
         rows, c = x.shape
-        out = self._alloc((rows, c), torch.uint8)
+        if out is None:
+            out = self._alloc((rows, c), torch.uint8)
         _chk(lib().fie_quantize_f8(self.h, _p(x), x.stride(0), _p(out), out.stride(0), rows, c, float(inv_scale)))
         return out
 
@@ -748,46 +752,53 @@ class Context:
         """Zero-filled workspace of the fused timestep-embedding kernel (one per model: launches on one stream reuse it)."""
         return torch.zeros(lib().fie_time_embed_workspace_bytes(e), device=self.device, dtype=torch.uint8)
 
-    def time_embed(self, t, w1, b1, w2, b2, ws, add=None):
+    def time_embed(self, t, w1, b1, w2, b2, ws, add=None, out=None):
         """K7 fused: silu(W2 silu(W1 sinusoid(t) + b1) + b2 + add) for the B <= 4 rows of one step; w1 [E, C0], w2 [E, E] plain f16."""
         self.sync_stream()
         b, (e, c0) = t.numel(), w1.shape
-        out = self._alloc((b, e), torch.float16)
+        if out is None:
+            out = self._alloc((b, e), torch.float16)
         _chk(lib().fie_time_embed_f16(self.h, _p(t), b, c0, e, _p(w1), _p(b1), _p(w2), _p(b2), _p(add),
                                       add.stride(0) if add is not None else 0, _p(out), out.stride(0), _p(ws)))
         return out
 
-    def clip_embed(self, ids, tok, pos):
+    def clip_embed(self, ids, tok, pos, out=None):
         self.sync_stream()
         b, t = ids.shape
         c = tok.shape[1]
-        out = self._alloc((b * t, c))
+        if out is None:
+            out = self._alloc((b * t, c))
+        assert out.is_contiguous()
         _chk((lib().fie_clip_embed_f32 if self.f32 else lib().fie_clip_embed_f16)(self.h, _p(ids), b, t, c, _p(tok), _p(pos), _p(out)))
         return out
 
-    def pixels_in(self, u8_hwc, normalize, copies=1):
+    def pixels_in(self, u8_hwc, normalize, copies=1, out=None):
         self.sync_stream()
         h, w, _ = u8_hwc.shape
-        out = self._alloc((copies, h, w, 8))
+        if out is None:
+            out = self._alloc((copies, h, w, 8))
+        assert out.is_contiguous()
         _chk((lib().fie_pixels_in_u8_f32 if self.f32 else lib().fie_pixels_in_u8_f16)(self.h, _p(u8_hwc), h, w, int(normalize), _p(out), copies))
         return out
 
-    def pixels_out(self, x_nhwc):
+    def pixels_out(self, x_nhwc, out=None):
         self.sync_stream()
         _, h, w, ld = x_nhwc.shape
-        out = self._alloc((h, w, 3), torch.uint8)
+        if out is None:
+            out = self._alloc((h, w, 3), torch.uint8)
+        assert out.is_contiguous()
         _chk((lib().fie_pixels_out_f32_u8 if self.f32 else lib().fie_pixels_out_f16_u8)(self.h, _p(x_nhwc), ld, h, w, _p(out)))
         return out
 
-    def resize_lanczos(self, rgb_u8, out_h, out_w):
+    def resize_lanczos(self, rgb_u8, out_h, out_w, out=None):
         """u8 [H, W, 3] device tensor -> u8 [out_h, out_w, 3], bit-exact with PIL's `resize(..., Image.LANCZOS)`.  A u8 [H, W] tensor
         (a mode-L mask) -> u8 [out_h, out_w] through the one-band kernels (fie_resize_l_u8)."""
         self.sync_stream()
         assert rgb_u8.dtype == torch.uint8 and rgb_u8.is_contiguous()
         if rgb_u8.dim() == 2:
-            return self._resize(rgb_u8, rgb_u8.shape[0], rgb_u8.shape[1], out_h, out_w, (), lib().fie_resize_l_u8)
+            return self._resize(rgb_u8, rgb_u8.shape[0], rgb_u8.shape[1], out_h, out_w, (), lib().fie_resize_l_u8, out=out)
         h, w, _ = rgb_u8.shape
-        return self._resize(rgb_u8, h, w, out_h, out_w, (3,), lib().fie_resize_rgb_u8)
+        return self._resize(rgb_u8, h, w, out_h, out_w, (3,), lib().fie_resize_rgb_u8, out=out)
 
     def resize_bicubic(self, rgb_u8, out_h, out_w, out=None):
         """u8 [H, W, 3] device tensor -> u8 [out_h, out_w, 3], bit-exact with PIL's `resize(..., Image.BICUBIC)` (what CLIPImageProcessor resizes
@@ -816,19 +827,23 @@ class Context:
             cache[key] = torch.from_numpy(hmask.gaussian_taps(key)).to(self.device)
         return cache[key]
 
-    def mask_prep(self, mask_l, blur=0.0):
+    def mask_prep(self, mask_l, blur=0.0, out=None):
         """Edit-size u8 [H, W] mask on the device (white = edit) -> (mask_px f32 [H, W], mask_lat u8 [H/8 * W/8]): one launch of
         fie_mask_prep.  mask_px is the binary mask L >= 128, or with blur = r > 0 its Gaussian feather (fie_amd/mask.py: gaussian_taps)."""
         self.sync_stream()
         h, w = mask_l.shape
         assert mask_l.dtype == torch.uint8 and mask_l.is_contiguous()
         taps = self._feather_taps(blur)
-        m_px = torch.empty((h, w), device=self.device, dtype=torch.float32)
-        m_lat = torch.empty(((h // 8) * (w // 8),), device=self.device, dtype=torch.uint8)
+        if out is not None:                         # (mask_px, mask_lat) to write: contiguous tensors of the shapes below
+            m_px, m_lat = out
+            assert m_px.is_contiguous() and m_lat.is_contiguous()
+        else:
+            m_px = torch.empty((h, w), device=self.device, dtype=torch.float32)
+            m_lat = torch.empty(((h // 8) * (w // 8),), device=self.device, dtype=torch.uint8)
         _chk(lib().fie_mask_prep(self.h, _p(mask_l), h, w, _p(taps), (taps.numel() - 1) // 2, _p(m_px), _p(m_lat)))
         return m_px, m_lat
 
-    def mask_fill(self, src_u8, mask_l, ctl_u8=None, fill=True):
+    def mask_fill(self, src_u8, mask_l, ctl_u8=None, fill=True, out=None, cleared=None):
         """The masked-content pre-pass of a masked edit (fie_mask_fill_rgb_u8).  src_u8: u8 [H, W, 3]; mask_l: u8 [H, W]
         (hole = L >= 128); ctl_u8: None or the u8 [H, W, 3] edge map.  -> (filled, cleared): the source with the hole replaced by the push-pull
         continuation of its surroundings (None with fill=False: nothing is computed for it), and the edge map set to 0 inside the hole (None
@@ -843,14 +858,21 @@ class Context:
             raise ValueError(f"mask_fill: the edge map must be contiguous u8 {(h, w, 3)}, got {tuple(ctl_u8.shape)} {ctl_u8.dtype}")
         if not fill and ctl_u8 is None:
             raise ValueError("mask_fill: nothing to do (fill=False and no edge map)")
-        ws = out = None
+        ws = None
+        if not fill:
+            out = None
+        if ctl_u8 is None:
+            cleared = None
         if fill:
             nbytes = lib().fie_mask_fill_workspace_bytes(h, w)
             if nbytes < 0:
                 raise FieError(f"mask_fill: {h} x {w} is outside 1 .. 2^24 pixels")
             ws = self._alloc((nbytes // 16, 4), torch.int32)
-            out = self._alloc((h, w, 3), torch.uint8)
-        cleared = self._alloc((h, w, 3), torch.uint8) if ctl_u8 is not None else None
+            if out is None:
+                out = self._alloc((h, w, 3), torch.uint8)
+        if ctl_u8 is not None and cleared is None:
+            cleared = self._alloc((h, w, 3), torch.uint8)
+        assert (out is None or out.is_contiguous()) and (cleared is None or cleared.is_contiguous())
         _chk(lib().fie_mask_fill_rgb_u8(self.h, _p(src_u8), _p(mask_l), h, w, _p(ws), _p(out), _p(ctl_u8), _p(cleared)))
         return out, cleared
 
@@ -885,12 +907,14 @@ class Context:
         _chk(lib().fie_multiband_blend_rgb_u8(self.h, _p(edit_u8), _p(source_u8), _p(mask_l), _p(alpha), h, w, int(levels), _p(ws), _p(out)))
         return out
 
-    def pixels_out_composite(self, x_nhwc, source_u8, mask_px):
+    def pixels_out_composite(self, x_nhwc, source_u8, mask_px, out=None):
         """pixels_out() with the paste-back: the source bytes where mask_px == 0, the decoded ones where it is 1, the rounded blend between."""
         self.sync_stream()
         _, h, w, ld = x_nhwc.shape
         assert source_u8.shape == (h, w, 3) and mask_px.shape == (h, w) and source_u8.is_contiguous() and mask_px.is_contiguous()
-        out = self._alloc((h, w, 3), torch.uint8)
+        if out is None:
+            out = self._alloc((h, w, 3), torch.uint8)
+        assert out.is_contiguous()
         _chk((lib().fie_pixels_out_composite_f32_u8 if self.f32 else lib().fie_pixels_out_composite_f16_u8)(
             self.h, _p(x_nhwc), ld, h, w, _p(source_u8), _p(mask_px), _p(out)))
         return out
@@ -1067,13 +1091,15 @@ class Context:
         _chk((lib().fie_selfsim_mse_f32 if self.f32 else lib().fie_selfsim_mse_f16)(self.h, _p(keys_a), _p(keys_b), keys_a.stride(0), n, t, c, _p(ws), _p(out)))
         return out
 
-    def canny_device(self, rgb_u8, low=100, high=200):
+    def canny_device(self, rgb_u8, low=100, high=200, out=None):
         """u8 [H, W, 3] device tensor -> u8 [H, W, 3] edge map on the device (integer exact; synchronises the stream)."""
         self.sync_stream()
         h, w, _ = rgb_u8.shape
         assert rgb_u8.is_contiguous() and rgb_u8.dtype == torch.uint8
         ws = torch.empty(lib().fie_canny_workspace_bytes(h, w), device=self.device, dtype=torch.uint8)
-        out = torch.empty((h, w, 3), device=self.device, dtype=torch.uint8)
+        if out is None:
+            out = torch.empty((h, w, 3), device=self.device, dtype=torch.uint8)
+        assert out.is_contiguous()
         it = _I(0)
         _chk(lib().fie_canny_rgb_device_u8(self.h, _p(rgb_u8), h, w, int(low), int(high), _p(ws), _p(out), ctypes.byref(it)))
         self.canny_passes = it.value

@@ -303,7 +303,7 @@ int fie_pack_conv3x3_f16(fie_ctx* ctx, const void* src_oihw, int Cout, int Cin, 
  * in registers (saturating RNE, scale 1) for v_mfma_f32_16x16x32_fp8_fp8; fp32 accumulation;  epi(v) takes v * scale[n].
  *   fie_pack_rows_f8 / fie_pack_conv3x3_f8: as their _f16 twins, dst = [Npad][ldw] BYTES (ldw % 64 == 0), scales = [Npad] fp32 (out).
  *   fie_gemm_w8_f16 / fie_conv3x3_w8_nhwc_f16: as fie_gemm_f16 / fie_conv3x3_nhwc_f16 with (W8packed, ldw in bytes, w_scale).
- *   Shapes must be eligible for the LDS-DMA kernels (operands < 2 GiB, Cin % 64 == 0, K1 == K or K1 % 64 == 0), else FIE_EINVAL. */
+ *   Shapes must be eligible for the LDS-DMA kernels (operands < 2 GiB, Cin % 64 == 0, K1 == K, or K1 % 64 == 0 and K % 64 == 0), else FIE_EINVAL. */
 int fie_pack_rows_f8(fie_ctx* ctx, const void* src, int64_t ld_src, int N, int K, void* dst, int64_t ldw, int Npad, float* scales,
                      int interleave2);
 int fie_pack_conv3x3_f8(fie_ctx* ctx, const void* src_oihw, int Cout, int Cin, int cin_pad, void* dst, int64_t ldw, int Npad,
