@@ -5,6 +5,7 @@ multiply-add of the hot path runs in the hand-written HIP kernels behind these w
 if the library is missing or the device is not gfx950 the first call raises.
 """
 import ctypes
+import numbers
 import os
 import subprocess
 
@@ -842,6 +843,23 @@ class Context:
             m_lat = torch.empty(((h // 8) * (w // 8),), device=self.device, dtype=torch.uint8)
         _chk(lib().fie_mask_prep(self.h, _p(mask_l), h, w, _p(taps), (taps.numel() - 1) // 2, _p(m_px), _p(m_lat)))
         return m_px, m_lat
+
+    def mask_grow(self, mask_l, radius, out=None):
+        """The mask grown (radius > 0) or shrunk (radius < 0) by the exact Euclidean disk of |radius| <= 64 pixels (fie_mask_grow_u8; DESIGN.md
+        section 16).  mask_l: contiguous u8 [H, W] on the device (set = L >= 128), any size below 2^31 pixels.  -> u8 [H, W] of 0 / 255; radius 0
+        the binarised mask.  `out`: a contiguous u8 [H, W] tensor to write (not the operand).  One launch, no synchronisation."""
+        self.sync_stream()
+        if not torch.is_tensor(mask_l) or mask_l.dim() != 2 or mask_l.dtype != torch.uint8 or not mask_l.is_contiguous():
+            raise ValueError(f"mask_grow: a contiguous u8 [H, W] mask, got {tuple(getattr(mask_l, 'shape', ()))} {getattr(mask_l, 'dtype', type(mask_l).__name__)}")
+        if isinstance(radius, bool) or not isinstance(radius, numbers.Integral):
+            raise ValueError(f"mask_grow: radius={radius!r}: an integer")
+        h, w = mask_l.shape
+        if out is None:
+            out = self._alloc((h, w), torch.uint8)
+        elif tuple(out.shape) != (h, w) or out.dtype != torch.uint8 or not out.is_contiguous() or out.data_ptr() == mask_l.data_ptr():
+            raise ValueError(f"mask_grow: out must be a contiguous u8 {(h, w)} tensor of its own")
+        _chk(lib().fie_mask_grow_u8(self.h, _p(mask_l), h, w, int(radius), _p(out)))
+        return out
 
     def mask_fill(self, src_u8, mask_l, ctl_u8=None, fill=True, out=None, cleared=None):
         """The masked-content pre-pass of a masked edit (fie_mask_fill_rgb_u8).  src_u8: u8 [H, W, 3]; mask_l: u8 [H, W]

@@ -16,6 +16,7 @@ CONTENT_MODES = tuple(sorted(CONTENT_CODES, key=CONTENT_CODES.get))
 MAX_BLUR = 21          # radius ceil(3 r) <= 64: the LDS bound of fie_mask_prep
 BLEND_MODES = ("alpha", "multiband")      # blend: the paste-back as ever, or the one-sided multi-band blend
 MAX_BLEND_LEVELS = 6                      # fie_multiband_blend_rgb_u8's bound
+MAX_GROW = 64                             # mask_grow: fie_mask_grow_u8's radius bound, the halo a block stages
 
 
 def to_l_array(mask, size=None):
@@ -73,6 +74,16 @@ def check_blend(blend, blend_levels=4, have_mask=True, paste_back=True):
     if blend != "alpha" and not paste_back:
         raise ValueError(f"blend={blend!r} is a paste-back: it needs paste_back=True")
     return blend, int(blend_levels)
+
+
+def check_grow(mask_grow, have_mask=True):
+    """The argument rules of `mask_grow` (the mask grown, or with a negative value shrunk, by an exact disk of that many pixels of the mask as
+    passed, before anything else reads it); returns it as an int."""
+    if isinstance(mask_grow, bool) or not isinstance(mask_grow, (int, np.integer)) or not -MAX_GROW <= mask_grow <= MAX_GROW:
+        raise ValueError(f"mask_grow={mask_grow!r}: an integer in {-MAX_GROW}..{MAX_GROW}")
+    if mask_grow != 0 and not have_mask:
+        raise ValueError("mask_grow needs a mask")
+    return int(mask_grow)
 
 
 def blur_radius(r):

@@ -138,7 +138,8 @@ class HipImg2ImgPipeline:
 
     def prepare(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                 num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
-                mask_image=None, mask_blur=0, paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False):
+                mask_image=None, mask_blur=0, paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False,
+                mask_grow=0):
         """`image` / `control_image`: PIL images, or u8 [H, W, 3] tensors already on the device (FastEditor.edit keeps the
         resized source and its device-side Canny map in HBM instead of bouncing them through PIL).  `mask_image` (additive, diffusers'
         name): restricts the edit to its white region -- a PIL image, a uint8 / bool [H, W] array, or a u8 [H, W]
@@ -148,14 +149,19 @@ class HipImg2ImgPipeline:
         `blend` (additive; needs a mask and the paste-back): "alpha" the paste-back as ever, "multiband" the one-sided multi-band blend over
         `blend_levels` (1..6) pyramid levels -- the decoded image's low-frequency difference to the source fades out towards the seam, outside the
         mask the output stays the source's bytes.  `paste_later`: the caller composites the result itself behind the job
-        (FastEditor's source-size back end): a "multiband" job with paste_back=False then returns the blended image B uncomposited."""
+        (FastEditor's source-size back end): a "multiband" job with paste_back=False then returns the blended image B uncomposited.
+        `mask_grow` (additive; a non-zero value needs a mask): the mask grown (> 0) or shrunk (< 0) by the exact Euclidean disk of that many of its
+        pixels, -64 .. 64, on the device before anything else reads it: the call equals the one with the grown mask passed in (DESIGN.md section
+        16).  0 launches nothing and passes the mask on as it is."""
         return self._prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                              controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content,
-                             hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later))
+                             hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later),
+                             hmask.check_grow(mask_grow, mask_image is not None))
 
-    def _mask_job(self, mask_image, mask_blur, paste_back, h, w):
+    def _mask_job(self, mask_image, mask_blur, paste_back, h, w, grow=0):
         """Mask tensors of one image: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back, the edit-size L mask
-        u8 [1, h, w]).  The mask is binarised / downsampled / feathered on the device (fie_mask_prep) on the current stream, in front of the job."""
+        u8 [1, h, w]).  The mask is binarised / downsampled / feathered on the device (fie_mask_prep) on the current stream, in front of the job;
+        with `grow` != 0 it is grown or shrunk by that radius first (fie_mask_grow_u8, same place), and the L mask returned is the grown one."""
         r = hmask.check_args(mask_blur, paste_back, mask_image is not None)
         if mask_image is None:
             return None, None, None
@@ -168,12 +174,14 @@ class HipImg2ImgPipeline:
         else:
             lm = torch.from_numpy(hmask.to_l_array(mask_image, (w, h))).to(self.ctx.device)
         with self.eager_lock:                             # the context's stream binding is shared by the threads of in-flight edits
+            if grow:
+                lm = self.ctx.mask_grow(lm, grow)
             m_px, m_lat = self.ctx.mask_prep(lm, r)
         return m_lat[None], (m_px[None] if paste_back else None), lm[None]
 
     def _prepare(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                  controlnet_conditioning_scale, generator, mask_image=None, mask_blur=0, paste_back=True, masked_content="original",
-                 blend=("alpha", 4)):
+                 blend=("alpha", 4), grow=0):
         """Host side of one call: argument checks, tokenisation, RNG draws (in upstream order: posterior sample, init
         noise, one per non-final step) and the H2D copies.  Returns the device-resident job for run_device()."""
         ctx = self.ctx
@@ -188,7 +196,7 @@ class HipImg2ImgPipeline:
         if h % 8 or w % 8:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {h} and {w}.")
         content = hmask.check_content(masked_content, mask_image is not None)
-        mask_lat, mask_px, mask_l = self._mask_job(mask_image, mask_blur, paste_back, h, w)
+        mask_lat, mask_px, mask_l = self._mask_job(mask_image, mask_blur, paste_back, h, w, grow)
         steps = self.scheduler.plan(num_inference_steps, strength)
         if not steps:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of "
@@ -246,13 +254,14 @@ class HipImg2ImgPipeline:
 
     def prepare_batch(self, prompts, negative_prompts, images, control_images, strength=0.8, num_inference_steps=4,
                       guidance_scale=1.5, controlnet_conditioning_scale=0.5, generators=None, mask_image=None, mask_blur=0,
-                      paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False):
+                      paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0):
         """[additive] n independent edits as ONE device job (BASELINE config "batch=8"): the UNet / ControlNet / CLIP run
         at batch n * nb, the VAE per image.  Rows are image-major ([img0 uncond, img0 cond, img1 uncond, ...]); each
         image keeps its own generator, so image i of a batch draws exactly the noise a single call with that generator
         draws (upstream: a list of generators, one per prompt).  `mask_image`: None, or one mask per image (None in the
         list = edit everywhere).  `masked_content`: one mode for the call (prepare()); an image without a mask is edited as ever.  `blend` / `blend_levels` /
-        `paste_later`: prepare()'s, one value for the call; an image without a mask comes out as without the keyword."""
+        `paste_later`: prepare()'s, one value for the call; an image without a mask comes out as without the keyword.  `mask_grow`: prepare()'s, one
+        radius for the call; an image without a mask is untouched."""
         n = len(prompts)
         if not (n == len(images) == len(control_images)) or n == 0:
             raise ValueError("prompts, images and control_images must be non-empty lists of one length")
@@ -263,13 +272,15 @@ class HipImg2ImgPipeline:
         hmask.check_args(mask_blur, paste_back, masked)
         content = hmask.check_content(masked_content, masked)
         blend = hmask.check_blend(blend, blend_levels, masked, paste_back or paste_later)
+        grow = hmask.check_grow(mask_grow, masked)
         negative_prompts = negative_prompts or [""] * n
         generators = generators or [None] * n
         jobs = [self._prepare(prompts[i], negative_prompts[i], images[i], control_images[i], strength, num_inference_steps,
                               guidance_scale, controlnet_conditioning_scale, generators[i], masks[i],
                               mask_blur if masks[i] is not None else 0, paste_back,
                               content if masks[i] is not None else "original",
-                              blend if masks[i] is not None else ("alpha", 4)) for i in range(n)]
+                              blend if masks[i] is not None else ("alpha", 4),
+                              grow if masks[i] is not None else 0) for i in range(n)]
         if any(j["hw"] != jobs[0]["hw"] for j in jobs):
             raise ValueError("all images of a batch must have one size")
         if masked:                                        # an image without a mask edits everywhere: an all-ones mask
@@ -651,7 +662,7 @@ class HipImg2ImgPipeline:
     def __call__(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                  num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
                  output_type="pil", slot=0, post_check=None, mask_image=None, mask_blur=0, paste_back=True, after_device=None, *,
-                 masked_content="original", blend="alpha", blend_levels=4, paste_later=False, **unused):
+                 masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0, **unused):
         """`slot` (additive): independent hipGraph instance + stream, so that several calls may be in flight from different
         host threads on one GPU (graph mode only).  `post_check` (additive): a callable run after the result has reached the host
         (the stream is idle then); when it returns True the device-resident inputs have changed meanwhile and the device job is run
@@ -659,7 +670,8 @@ class HipImg2ImgPipeline:
         number of hysteresis rounds in front of the edit, and whether they had reached the fixed point is only looked at here --
         no host wait in front of the edit, a repeated job in the rare case that they had not.  `mask_image` / `mask_blur` / `paste_back`
         (additive): a mask-restricted edit (prepare(); a list of masks for a batch call); `masked_content`: what it starts from inside the mask
-        (prepare()); `blend` / `blend_levels` / `paste_later`: how the paste-back meets the source (prepare()).  `after_device` (additive): a callable given the u8 result
+        (prepare()); `blend` / `blend_levels` / `paste_later`: how the paste-back meets the source (prepare()); `mask_grow`: the mask grown or
+        shrunk by an exact disk before anything reads it (prepare()).  `after_device` (additive): a callable given the u8 result
         while it is still on the device, on the slot's stream behind the device job and outside its graph; it may queue more work there (FastEditor
         scores the edit) and whatever it returns comes back as `.extra`, complete once the image has reached the host.  A hook that returns a
         `DeviceOutput` replaces the image: its tensor(s) take the final device-to-host copy (FastEditor's full-resolution back end)."""
@@ -670,7 +682,7 @@ class HipImg2ImgPipeline:
         with torch.cuda.stream(st):
             out = self._call(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                              controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back), after_device,
-                             masked_content, dict(blend=blend, blend_levels=blend_levels, paste_later=paste_later))
+                             masked_content, dict(blend=blend, blend_levels=blend_levels, paste_later=paste_later, mask_grow=mask_grow))
         caller.wait_stream(st)
         return out
 

@@ -600,6 +600,20 @@ int64_t fie_multiband_workspace_bytes(int H, int W, int levels);
 int fie_multiband_blend_rgb_u8(fie_ctx* ctx, const uint8_t* edit, const uint8_t* source, const uint8_t* mask_l, const float* alpha, int H,
                                int W, int levels, void* workspace, uint8_t* out);
 
+/* ---- Growing or shrinking an edit mask by an exact Euclidean disk: in front of everything else that reads the mask.
+ *   fie_mask_grow_u8   mask_l u8 [H, W], any H, W >= 1 with H * W < 2^31 (a source-size mask of 12 MP and more; the 2^24 of the fill and the blend
+ *      is an edit-size bound and does not apply), radius in -64 .. 64.  out u8 [H, W], every byte written, 0 or 255; it overlaps no byte of mask_l
+ *      (blocks read each other's halo).  With m(q) = (mask_l(q) >= 128), R = |radius| and p, q pixels of the H x W mask only:
+ *        radius > 0   out(p) = 255 iff some q has m(q) and (px - qx)^2 + (py - qy)^2 <= R^2: nothing grows in from outside the image;
+ *        radius < 0   out(p) = 255 iff m(q) for every q with (px - qx)^2 + (py - qy)^2 <= R^2: the image border does not erode a mask that
+ *                     touches it; grow(m, -k) = ~grow(~m, k);
+ *        radius == 0  out = 255 m, the binarised mask.
+ *      Integer comparisons only, exact (tests/mask_grow_oracle.py restates it in numpy).  FIE_EINVAL for anything else, NULL operands included.
+ *      One launch of one block per 64 x 64 tile: the tile's binary pixels and an R-halo in LDS ((64 + 2R)^2 + R + 1 bytes), a column scan for the
+ *      distance to the nearest set pixel of each column, a row pass against floor(sqrt(R^2 - dx^2)).  Asynchronous on the ctx stream; no
+ *      workspace, no atomics, no block waits for another. */
+int fie_mask_grow_u8(fie_ctx* ctx, const uint8_t* mask_l, int H, int W, int radius, uint8_t* out);
+
 /* ---- Full-resolution back end of an edit: the edit-size result at the source's size, composited against the
  * source's own bytes.  res: u8 [h, w, 3], the edit-size result.  The output is H x W: up = Pillow's 8-bit LANCZOS resize of res to
  * (W, H), bit-exact (kx / bx / ksx, ky / by / ksy: the tables of fie_resize_rgb_u8 for w -> W and h -> H; a table is NULL on an axis

@@ -97,6 +97,15 @@ def add_blend_args(p):
     return p
 
 
+def add_grow_args(p):
+    """[additive] growing / shrinking the mask.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--mask_grow", type=int, default=0, choices=range(-64, 65), metavar="N",
+                   help="[additive] with --use_mask: grow (N > 0) or shrink (N < 0) each mask by an exact disk of N pixels of the mask (the 512x512 "
+                        "benchmark image), -64..64, before anything else reads it.  PIE-Bench's decoder sets the mask's 1-pixel frame, so a grown "
+                        "benchmark mask has an N-pixel frame")
+    return p
+
+
 def add_resolution_args(p):
     """[additive] aspect-ratio edits.  Kept apart from build_parser() for the same reason as add_mask_args."""
     p.add_argument("--resolution", type=str, default="square",
@@ -256,6 +265,11 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
         if not use_mask:
             raise ValueError("--blend multiband needs --use_mask")
         extra = dict(extra, blend=blend, blend_levels=getattr(args, "blend_levels", 4))
+    mask_grow = getattr(args, "mask_grow", 0)
+    if mask_grow:
+        if not use_mask:
+            raise ValueError("--mask_grow needs --use_mask")
+        extra = dict(extra, mask_grow=mask_grow)
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
     def flush():
@@ -361,7 +375,7 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    parser = add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_blend_args(add_mask_args(build_parser())))))))
+    parser = add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_grow_args(add_blend_args(add_mask_args(build_parser()))))))))
     args = parser.parse_args(argv)
     if args.region == "mask" and not args.use_mask:
         parser.error("--region mask needs --use_mask")
@@ -369,6 +383,8 @@ def main(argv=None):
         parser.error("--masked_content needs --use_mask")
     if args.blend != "alpha" and not args.use_mask:
         parser.error("--blend multiband needs --use_mask")
+    if args.mask_grow and not args.use_mask:
+        parser.error("--mask_grow needs --use_mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets

@@ -55,6 +55,9 @@ def build_parser():
            "and outside the mask the output stays the source's bytes")
     a("--blend_levels", type=int, default=4, choices=range(1, 7), metavar="N",
       help="[additive] with --blend multiband: pyramid levels, 1..6; the difference fades over about 2^N pixels")
+    a("--mask_grow", type=int, default=0, choices=range(-64, 65), metavar="N",
+      help="[additive] with --mask: grow (N > 0) or shrink (N < 0) the mask by an exact disk of N pixels of the mask (the input image's pixels), "
+           "-64..64, before anything else reads it")
     a("--resolution", type=str, default="square",
       help="[additive] output size: 'square' (1024x1024, the reference's), 'auto' (the SDXL aspect-ratio bucket nearest the source's) or WxH "
            "(multiples of 64, 512..2048, at most 1024^2 pixels)")
@@ -100,6 +103,8 @@ def main(argv=None):
         parser.error("--masked_content needs --mask")
     if args.blend != "alpha" and (args.mask is None or args.no_paste_back):
         parser.error("--blend multiband needs --mask and the paste-back")
+    if args.mask_grow and args.mask is None:
+        parser.error("--mask_grow needs --mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets
@@ -144,6 +149,9 @@ def main(argv=None):
         if args.blend != "alpha":
             extra.update(blend=args.blend, blend_levels=args.blend_levels)
             print(f"      Blend: {args.blend}, {args.blend_levels} levels")
+        if args.mask_grow:
+            extra.update(mask_grow=args.mask_grow)
+            print(f"      Mask grown by: {args.mask_grow} px")
     if args.resolution != "square":
         extra.update(resolution=args.resolution)
     if args.region == "mask":

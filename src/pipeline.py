@@ -163,7 +163,7 @@ class FastEditor:
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
              paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
-             blend="alpha", blend_levels=4):
+             blend="alpha", blend_levels=4, mask_grow=0):
         """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
         [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
         latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
@@ -200,13 +200,23 @@ class FastEditor:
         the edit size inside the device job: inside the mask the edit keeps all of its detail while its low-frequency difference to the source
         (brightness, white balance, a slow gradient) fades to nothing towards the seam, over about 2^blend_levels pixels; outside the mask the
         output stays the source's bytes, and `mask_blur`, the source-size composite, regions and the metrics take the blended image in place of
-        the decoded one.  A region smaller than about 2^(blend_levels + 2) pixels keeps less of its own low frequencies."""
+        the decoded one.  A region smaller than about 2^(blend_levels + 2) pixels keeps less of its own low frequencies.
+        [additive] `mask_grow` (an integer in -64..64; a non-zero value needs a mask): moves the mask's outline before anything else looks at the
+        mask.  r > 0 grows it by the exact Euclidean disk of r pixels (what a tight segmenter mask needs for object removal: the rim and the
+        shadow fall inside the hole), r < 0 shrinks it by |r|; pixels of the mask as passed, that is of the source image.  Nothing grows in from
+        outside the image and the image border does not erode.  The call returns exactly what it returns for the grown mask passed in: the latent
+        mask, the feather, the fill, the blend, the source-size composite, `bg_*` / `clip_score_edited` and the box of region="mask" all see the
+        grown mask, and a region crops it after it has grown.  One HIP op on the device; a mask shrunk to nothing returns
+        the source; 0 (default) launches nothing."""
         full = hregion.check_output(output_size, region)
         hmask.check_args(mask_blur, paste_back, mask is not None)
         hmask.check_content(masked_content, mask is not None)
         hmask.check_blend(blend, blend_levels, mask is not None, paste_back)
+        grow = hmask.check_grow(mask_grow, mask is not None)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
         if region is not None:
+            if grow:        # grown first, cropped second: the box of "mask" is the grown mask's, and pixels outside an explicit box reach into it
+                mask_l = self._grow_host(mask_l, grow)
             box = hregion.resolve(region, image.size, mask_l, region_padding, resolution)
             res = self.edit(image.crop(box), prompt, negative_prompt, strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
                             canny_low_threshold, canny_high_threshold, seed, None if mask_l is None else mask_l[box[1]:box[3], box[0]:box[2]],
@@ -231,7 +241,7 @@ class FastEditor:
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False,
                                                                  original=origs)
-            mask_dev = self._mask_device(mask_l, size, original=omasks)
+            mask_dev = self._mask_device(mask_l, size, original=omasks, grow=grow)
         hook = self._scorer(slot, origs, omasks, [prompt]) if metrics else None
         if full:        # the edit-size job runs with its own paste-back off: the composite happens at the source's size, behind it
             hook = self._fullres(slot, origs, omasks if paste_back else [None], mask_blur, hook)
@@ -346,14 +356,23 @@ class FastEditor:
                 out[i]["dino_distance"] = float(v)
         return out
 
-    def _mask_device(self, mask_l, size, original=None):
+    def _grow_host(self, mask_l, grow):
+        """uint8 [H, W] mask -> the mask grown by `grow` (fie_mask_grow_u8), back on the host: what a region edit crops.  One upload, one launch
+        and one synchronising copy of H * W bytes on the calling thread's slot stream."""
+        with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(getattr(self._tls, "slot", 0))):
+            return self.pipe.ctx.mask_grow(torch.from_numpy(mask_l).to(self.pipe.ctx.device), grow).cpu().numpy()
+
+    def _mask_device(self, mask_l, size, original=None, grow=0):
         """uint8 [H, W] mode-L mask (or None) -> u8 [size[1], size[0]] on the device: LANCZOS-resized as the source is (fie_resize_l_u8,
-        bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`).  `original`: a list that receives the mask as uploaded (or None)."""
+        bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`).  `original`: a list that receives the mask as uploaded (or None).
+        `grow` != 0: the uploaded mask is grown by that radius first (fie_mask_grow_u8), and it is the grown one that `original` receives."""
         if mask_l is None:
             if original is not None:
                 original.append(None)
             return None
         m = torch.from_numpy(mask_l).to(self.pipe.ctx.device)
+        if grow:
+            m = self.pipe.ctx.mask_grow(m, grow)
         if original is not None:
             original.append(m)
         if (m.shape[1], m.shape[0]) != tuple(size):
@@ -363,7 +382,7 @@ class FastEditor:
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
                    paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
-                   blend="alpha", blend_levels=4):
+                   blend="alpha", blend_levels=4, mask_grow=0):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
         edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
@@ -375,13 +394,15 @@ class FastEditor:
         behind the job.  `region` may also be a LIST with one entry per image (None, "mask" or a box): each image gets its own box, images are
         grouped by the target size of their crops, and an image whose entry is None is edited whole and returned at its source's size.
         `masked_content`: as edit()'s, one value for the whole call; an image whose mask is None is edited as without it.
-        `blend` / `blend_levels`: as edit()'s, one value for the whole call; an image whose mask is None comes out as without them."""
+        `blend` / `blend_levels`: as edit()'s, one value for the whole call; an image whose mask is None comes out as without them.
+        `mask_grow`: as edit()'s, one radius for the whole call; an image whose mask is None is untouched."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
             raise ValueError(f"{len(masks)} masks for {len(images)} images: one mask (or None) per image")
         hmask.check_content(masked_content, masks is not None and any(m is not None for m in masks))
         hmask.check_blend(blend, blend_levels, masks is not None and any(m is not None for m in masks), paste_back)
+        grow = hmask.check_grow(mask_grow, masks is not None and any(m is not None for m in masks))
         regions = list(region) if isinstance(region, list) else [region] * len(images)
         if len(regions) != len(images):
             raise ValueError(f"{len(regions)} regions for {len(images)} images: one region (or None) per image")
@@ -390,6 +411,8 @@ class FastEditor:
         if has_region:
             hmask.check_args(mask_blur, paste_back, masks is not None and any(m is not None for m in masks))
             mls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks or [None] * len(images), images)]
+            if grow:        # grown first, cropped second (edit())
+                mls = [m if m is None else self._grow_host(m, grow) for m in mls]
             boxes = [hregion.resolve(r, im.size, m, region_padding, resolution) for r, im, m in zip(regions, images, mls)]
             cut = lambda a, b: a if a is None or b is None else a[b[1]:b[3], b[0]:b[2]]
             res = self.edit_batch([im if b is None else im.crop(b) for im, b in zip(images, boxes)], prompts, negative_prompts, strength,
@@ -414,7 +437,8 @@ class FastEditor:
                                       paste_back=paste_back, resolution=sz, metrics=metrics, output_size=output_size,
                                       masked_content=masked_content if masks is not None and any(masks[i] is not None for i in idx) else "original",
                                       blend=blend if masks is not None and any(masks[i] is not None for i in idx) else "alpha",
-                                      blend_levels=blend_levels)
+                                      blend_levels=blend_levels,
+                                      mask_grow=grow if masks is not None and any(masks[i] is not None for i in idx) else 0)
                 res, ms = res if metrics else (res, [None] * len(idx))
                 for i, r, m in zip(idx, res, ms):
                     out[i], mets[i] = r, m
@@ -436,7 +460,7 @@ class FastEditor:
                 ctls.append(c_dev)
                 if one is not None:
                     origs.append(one[0])
-            mask_devs = [self._mask_device(m, size, original=omasks) for m in mask_ls] if mask_ls is not None else None
+            mask_devs = [self._mask_device(m, size, original=omasks, grow=grow) for m in mask_ls] if mask_ls is not None else None
         if (metrics or full) and mask_ls is None:
             omasks = [None] * len(images)
         hook = self._scorer(slot, origs, omasks, list(prompts)) if metrics else None
