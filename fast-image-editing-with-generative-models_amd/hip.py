@@ -165,6 +165,7 @@ class Context:
         self._stream = None
         self._gn_ws = {}
         self._gn_stats = {}
+        self._ws_retired = []          # scratch buffers a larger one has replaced (_scratch): a captured hipGraph may still hold their address
         self._gn_gen = 0
         self._sk_ws = {}               # split-K workspaces (fie_splitk_workspace), one per (stream, graph slot)
         self._sk_bound = None
@@ -309,6 +310,19 @@ class Context:
         """Run the program registered under `name` through its C-ABI graph entry (fie_unet_forward, fie_vae_decode, ...)."""
         self.sync_stream()
         _chk(getattr(lib(), "fie_" + name)(self.h))
+
+    def _scratch(self, cache, key, need):
+        """cache[key] when it holds `need` bytes, else a new u8 buffer of that size in its place.  The buffer it replaces is NOT freed: a hipGraph
+        captured on that (stream, graph slot) has its address in its launches, and a later replay would write into whatever torch has put there
+        since -- or, once a capture's empty_cache() has returned the block to the driver, into an unmapped page.  (An edit of three images after
+        an edit of one grows the GroupNorm scratch of the ControlNet's side stream; replaying the first edit's graph afterwards faulted.)  The
+        sizes follow the batch and the map and each replacement is larger than the last, so what is kept stays below the live buffers' size."""
+        buf = cache.get(key)
+        if buf is None or buf.numel() < need:
+            if buf is not None:
+                self._ws_retired.append(buf)
+            buf = cache[key] = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return buf
 
     def _alloc(self, shape, dtype=None, zero=False):
         t = (torch.zeros if zero else torch.empty)(shape, device=self.device, dtype=dtype or self.dtype)
@@ -467,9 +481,7 @@ class Context:
         b = rows_total // rows_per_image
         need = lib().fie_gn_stats_bytes(b, rows_per_image, pgroups)
         key = (self._stream, self.ws_tag)            # one buffer per stream and graph slot: a producer's sums are consumed before the next producer runs
-        buf = self._gn_stats.get(key)
-        if buf is None or buf.numel() < need:
-            buf = self._gn_stats[key] = torch.empty(need, device=self.device, dtype=torch.uint8)
+        buf = self._scratch(self._gn_stats, key, need)
         if self._keep is not None:
             self._keep.append(buf)
         _chk(lib().fie_gn_stats_target(self.h, _p(buf), rows_per_image, pgroups))
@@ -650,9 +662,7 @@ class Context:
             out = self._alloc(x1.shape[:-1] + (c1 + c2,), torch.uint8 if out_f8 else None)
         need = lib().fie_groupnorm_workspace_bytes(b, rows, groups)
         key = (self._stream, self.ws_tag)            # one scratch buffer per stream (and per in-flight graph slot)
-        ws = self._gn_ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._gn_ws[key] = torch.empty(need, device=self.device, dtype=torch.uint8)
+        ws = self._scratch(self._gn_ws, key, need)
         if self._keep is not None:
             self._keep.append(ws)
         tag = getattr(x1, "_gn_tag", None)
@@ -689,9 +699,7 @@ class Context:
         if not (tag is not None and tag[1:5] == (groups, c, rows, b) and tag[5] == self._gn_gen and tag[6] == key):
             return None
         need = lib().fie_groupnorm_workspace_bytes(b, rows, groups)
-        ws = self._gn_ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._gn_ws[key] = torch.empty(need, device=self.device, dtype=torch.uint8)
+        ws = self._scratch(self._gn_ws, key, need)
         if self._keep is not None:
             self._keep.append(ws)
         coef = self._alloc((b, c, 2), torch.float32)
@@ -860,6 +868,43 @@ class Context:
             raise ValueError(f"mask_grow: out must be a contiguous u8 {(h, w)} tensor of its own")
         _chk(lib().fie_mask_grow_u8(self.h, _p(mask_l), h, w, int(radius), _p(out)))
         return out
+
+    def outpaint_canvas(self, src, mask_l, margins, out=None):
+        """The canvas of an outpainting edit and its mask (fie_outpaint_canvas_rgb_u8).  src: contiguous u8 [H, W, 3] on the
+        device; mask_l: None or a contiguous u8 [H, W]; margins: (left, top, right, bottom), integers in 0 .. 4096, not all 0.  -> (canvas u8
+        [Hc, Wc, 3], canvas_mask u8 [Hc, Wc]) with Hc = top + H + bottom, Wc = left + W + right: the source with its edge pixels replicated into
+        the margins, and 255 in the margins over the mask as passed (0 without one).  `out`: a pair of contiguous u8 tensors of those shapes to
+        write (neither an operand, nor each other).  One launch, no synchronisation."""
+        self.sync_stream()
+        if not torch.is_tensor(src) or src.dim() != 3 or src.shape[2] != 3 or src.dtype != torch.uint8 or not src.is_contiguous():
+            raise ValueError(f"outpaint_canvas: a contiguous u8 [H, W, 3] source, got {tuple(getattr(src, 'shape', ()))} {getattr(src, 'dtype', type(src).__name__)}")
+        h, w, _ = src.shape
+        if mask_l is not None and (not torch.is_tensor(mask_l) or tuple(mask_l.shape) != (h, w) or mask_l.dtype != torch.uint8
+                                   or not mask_l.is_contiguous()):
+            raise ValueError(f"outpaint_canvas: mask_l must be None or a contiguous u8 {(h, w)} tensor, got "
+                             f"{tuple(getattr(mask_l, 'shape', ()))} {getattr(mask_l, 'dtype', type(mask_l).__name__)}")
+        try:
+            margins = tuple(margins)
+        except TypeError:
+            margins = ()
+        if len(margins) != 4 or any(isinstance(m, bool) or not isinstance(m, numbers.Integral) for m in margins):
+            raise ValueError(f"outpaint_canvas: margins={margins!r}: four integers (left, top, right, bottom)")
+        left, top, right, bottom = margins = tuple(int(m) for m in margins)
+        if min(margins) < 0 or max(margins) > 4096 or not any(margins):
+            raise ValueError(f"outpaint_canvas: margins={margins!r}: each in 0..4096 and at least one > 0")
+        hc, wc = top + h + bottom, left + w + right
+        if hc * wc >= 1 << 31:
+            raise ValueError(f"outpaint_canvas: a canvas of {hc} x {wc} has 2^31 pixels or more")
+        if out is None:
+            out = self._alloc((hc, wc, 3), torch.uint8), self._alloc((hc, wc), torch.uint8)
+        else:
+            ops = [t.data_ptr() for t in (src, mask_l) if t is not None]
+            ok = isinstance(out, (tuple, list)) and len(out) == 2 and all(torch.is_tensor(o) and o.dtype == torch.uint8 and o.is_contiguous() for o in out)
+            if not ok or tuple(out[0].shape) != (hc, wc, 3) or tuple(out[1].shape) != (hc, wc) or out[0].data_ptr() in ops \
+                    or out[1].data_ptr() in ops or out[0].data_ptr() == out[1].data_ptr():
+                raise ValueError(f"outpaint_canvas: out must be a pair of contiguous u8 tensors {(hc, wc, 3)} and {(hc, wc)} of their own")
+        _chk(lib().fie_outpaint_canvas_rgb_u8(self.h, _p(src), _p(mask_l), h, w, left, top, right, bottom, _p(out[0]), _p(out[1])))
+        return out[0], out[1]
 
     def mask_fill(self, src_u8, mask_l, ctl_u8=None, fill=True, out=None, cleared=None):
         """The masked-content pre-pass of a masked edit (fie_mask_fill_rgb_u8).  src_u8: u8 [H, W, 3]; mask_l: u8 [H, W]

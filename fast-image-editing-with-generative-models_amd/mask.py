@@ -17,6 +17,7 @@ MAX_BLUR = 21          # radius ceil(3 r) <= 64: the LDS bound of fie_mask_prep
 BLEND_MODES = ("alpha", "multiband")      # blend: the paste-back as ever, or the one-sided multi-band blend
 MAX_BLEND_LEVELS = 6                      # fie_multiband_blend_rgb_u8's bound
 MAX_GROW = 64                             # mask_grow: fie_mask_grow_u8's radius bound, the halo a block stages
+MAX_OUTPAINT = 4096                       # outpaint: fie_outpaint_canvas_rgb_u8's bound on each of the four margins
 
 
 def to_l_array(mask, size=None):
@@ -84,6 +85,38 @@ def check_grow(mask_grow, have_mask=True):
     if mask_grow != 0 and not have_mask:
         raise ValueError("mask_grow needs a mask")
     return int(mask_grow)
+
+
+def check_outpaint(outpaint):
+    """The argument rules of `outpaint` (the canvas grown by four margins of new border, which becomes the mask): None, or a
+    sequence (left, top, right, bottom) of integers in 0..4096 with at least one > 0.  Returns a tuple of ints, or None.  A mask is not needed:
+    the border is the mask."""
+    if outpaint is None:
+        return None
+    ok = isinstance(outpaint, (tuple, list, np.ndarray)) and len(outpaint) == 4 and all(
+        not isinstance(m, (bool, np.bool_)) and isinstance(m, (int, np.integer)) and 0 <= m <= MAX_OUTPAINT for m in outpaint)
+    if not ok or not any(outpaint):
+        raise ValueError(f"outpaint={outpaint!r}: None or (left, top, right, bottom), integers in 0..{MAX_OUTPAINT}, at least one > 0")
+    return tuple(int(m) for m in outpaint)
+
+
+def parse_outpaint(text):
+    """The command lines' `--outpaint L,T,R,B` -> check_outpaint()'s tuple; anything but four comma-separated integers in range is a ValueError."""
+    parts = str(text).split(",")
+    try:
+        margins = tuple(int(p) for p in parts)
+    except ValueError:
+        raise ValueError(f"--outpaint {text!r}: four comma-separated integers LEFT,TOP,RIGHT,BOTTOM") from None
+    if len(margins) != 4:
+        raise ValueError(f"--outpaint {text!r}: four comma-separated integers LEFT,TOP,RIGHT,BOTTOM")
+    return check_outpaint(margins)
+
+
+def canvas_size(size, outpaint):
+    """(width, height) of the canvas of a `size` = (width, height) image under check_outpaint()'s margins (None: the image's own)."""
+    if outpaint is None:
+        return tuple(size)
+    return size[0] + outpaint[0] + outpaint[2], size[1] + outpaint[1] + outpaint[3]
 
 
 def blur_radius(r):

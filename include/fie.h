@@ -614,6 +614,22 @@ int fie_multiband_blend_rgb_u8(fie_ctx* ctx, const uint8_t* edit, const uint8_t*
  *      workspace, no atomics, no block waits for another. */
 int fie_mask_grow_u8(fie_ctx* ctx, const uint8_t* mask_l, int H, int W, int radius, uint8_t* out);
 
+/* ---- The canvas of an outpainting edit: the source made larger by four margins, and the mask that selects what is new.
+ *   fie_outpaint_canvas_rgb_u8   src u8 [H, W, 3], mask_l u8 [H, W] or NULL, H, W >= 1; left, top, right, bottom in 0 .. 4096, not all 0.  With
+ *      Hc = top + H + bottom, Wc = left + W + right and Hc * Wc < 2^31:
+ *        canvas      u8 [Hc, Wc, 3]   canvas(y, x) = src(clamp(y - top, 0, H - 1), clamp(x - left, 0, W - 1)): the source's bytes inside the source
+ *                                     rectangle, its nearest edge pixel outside (a replicate, not zeros: the VAE encoder's receptive field mixes the
+ *                                     border into the latents next to the seam);
+ *        canvas_mask u8 [Hc, Wc]      255 outside the source rectangle; inside it mask_l(y - top, x - left) as passed, greys included, or 0 when
+ *                                     mask_l is NULL.
+ *      Every byte of both outputs is written; no output overlaps an operand or the other output.  FIE_EINVAL for anything else, NULL src / canvas /
+ *      canvas_mask included.  Exact (tests/outpaint_oracle.py restates it in numpy).  One launch at any size: both outputs are stored as aligned
+ *      dwords with the 0 .. 3 bytes in front of and behind them in each row stored as bytes (rows of 3 Wc and Wc bytes start at any address); over the
+ *      source rectangle the operands are read as aligned dwords too, by bytes elsewhere; no access is misaligned, none leaves its tensor; 64-bit
+ *      indexing.  Asynchronous on the ctx stream; no workspace, no atomics, no block waits for another. */
+int fie_outpaint_canvas_rgb_u8(fie_ctx* ctx, const uint8_t* src, const uint8_t* mask_l, int H, int W, int left, int top, int right, int bottom,
+                               uint8_t* canvas, uint8_t* canvas_mask);
+
 /* ---- Full-resolution back end of an edit: the edit-size result at the source's size, composited against the
  * source's own bytes.  res: u8 [h, w, 3], the edit-size result.  The output is H x W: up = Pillow's 8-bit LANCZOS resize of res to
  * (W, H), bit-exact (kx / bx / ksx, ky / by / ksy: the tables of fie_resize_rgb_u8 for w -> W and h -> H; a table is NULL on an axis

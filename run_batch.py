@@ -106,6 +106,26 @@ def add_grow_args(p):
     return p
 
 
+def outpaint_arg(text):
+    """argparse type of --outpaint: 'L,T,R,B' -> (left, top, right, bottom) (fie_amd/mask.py: parse_outpaint)."""
+    import fie_amd  # noqa: F401
+    from fie_amd import mask as hmask
+    try:
+        return hmask.parse_outpaint(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def add_outpaint_args(p):
+    """[additive] outpainting.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--outpaint", type=outpaint_arg, default=None, metavar="L,T,R,B",
+                   help="[additive] outpainting, for every image: make it larger by L, T, R, B pixels (left, top, right, bottom; each 0..4096, not "
+                        "all 0) and let the model invent the new border.  The border is the mask: with --use_mask the item's mask is carried into "
+                        "it, without it the border alone is edited, and --mask_grow, --masked_content, --blend and --region mask work without "
+                        "--use_mask")
+    return p
+
+
 def add_resolution_args(p):
     """[additive] aspect-ratio edits.  Kept apart from build_parser() for the same reason as add_mask_args."""
     p.add_argument("--resolution", type=str, default="square",
@@ -254,20 +274,24 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     with_metrics = getattr(args, "metrics", False)
     if with_metrics:
         extra = dict(extra, metrics=True)
-    extra = dict(extra, **region_kwargs(args, use_mask))
+    outpaint = getattr(args, "outpaint", None)
+    masked = use_mask or outpaint is not None      # --outpaint: the new border is a mask
+    if outpaint is not None:
+        extra = dict(extra, outpaint=tuple(outpaint))
+    extra = dict(extra, **region_kwargs(args, masked))
     masked_content = getattr(args, "masked_content", "original")
     if masked_content != "original":
-        if not use_mask:
+        if not masked:
             raise ValueError("--masked_content needs --use_mask")
         extra = dict(extra, masked_content=masked_content)
     blend = getattr(args, "blend", "alpha")
     if blend != "alpha":
-        if not use_mask:
+        if not masked:
             raise ValueError("--blend multiband needs --use_mask")
         extra = dict(extra, blend=blend, blend_levels=getattr(args, "blend_levels", 4))
     mask_grow = getattr(args, "mask_grow", 0)
     if mask_grow:
-        if not use_mask:
+        if not masked:
             raise ValueError("--mask_grow needs --use_mask")
         extra = dict(extra, mask_grow=mask_grow)
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
@@ -375,15 +399,17 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    parser = add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_grow_args(add_blend_args(add_mask_args(build_parser()))))))))
+    parser = add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_outpaint_args(add_grow_args(add_blend_args(
+        add_mask_args(build_parser())))))))))
     args = parser.parse_args(argv)
-    if args.region == "mask" and not args.use_mask:
+    masked = args.use_mask or args.outpaint is not None                # --outpaint: the new border is a mask
+    if args.region == "mask" and not masked:
         parser.error("--region mask needs --use_mask")
-    if args.masked_content != "original" and not args.use_mask:
+    if args.masked_content != "original" and not masked:
         parser.error("--masked_content needs --use_mask")
-    if args.blend != "alpha" and not args.use_mask:
+    if args.blend != "alpha" and not masked:
         parser.error("--blend multiband needs --use_mask")
-    if args.mask_grow and not args.use_mask:
+    if args.mask_grow and not masked:
         parser.error("--mask_grow needs --use_mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401

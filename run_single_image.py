@@ -19,6 +19,16 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
+def outpaint_arg(text):
+    """argparse type of --outpaint: 'L,T,R,B' -> (left, top, right, bottom) (fie_amd/mask.py: parse_outpaint)."""
+    import fie_amd  # noqa: F401
+    from fie_amd import mask as hmask
+    try:
+        return hmask.parse_outpaint(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Fast image editing on a single image")
     a = p.add_argument
@@ -58,6 +68,10 @@ def build_parser():
     a("--mask_grow", type=int, default=0, choices=range(-64, 65), metavar="N",
       help="[additive] with --mask: grow (N > 0) or shrink (N < 0) the mask by an exact disk of N pixels of the mask (the input image's pixels), "
            "-64..64, before anything else reads it")
+    a("--outpaint", type=outpaint_arg, default=None, metavar="L,T,R,B",
+      help="[additive] outpainting: make the picture larger by L, T, R, B pixels (left, top, right, bottom; each 0..4096, not all 0) and let the "
+           "model invent the new border.  The border is the mask (a --mask is carried into it), so --mask_grow, --mask_blur, --masked_content, "
+           "--blend and --region mask work without --mask; recommended: --masked_content fill --mask_grow 16 --blend multiband --output_size source")
     a("--resolution", type=str, default="square",
       help="[additive] output size: 'square' (1024x1024, the reference's), 'auto' (the SDXL aspect-ratio bucket nearest the source's) or WxH "
            "(multiples of 64, 512..2048, at most 1024^2 pixels)")
@@ -97,13 +111,14 @@ def save_plot(path, source_img, edited_img, model, prompt):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.region == "mask" and args.mask is None:
+    masked = args.mask is not None or args.outpaint is not None        # --outpaint: the new border is a mask
+    if args.region == "mask" and not masked:
         parser.error("--region mask needs --mask")
-    if args.masked_content != "original" and args.mask is None:
+    if args.masked_content != "original" and not masked:
         parser.error("--masked_content needs --mask")
-    if args.blend != "alpha" and (args.mask is None or args.no_paste_back):
+    if args.blend != "alpha" and (not masked or args.no_paste_back):
         parser.error("--blend multiband needs --mask and the paste-back")
-    if args.mask_grow and args.mask is None:
+    if args.mask_grow and not masked:
         parser.error("--mask_grow needs --mask")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
@@ -137,12 +152,17 @@ def main(argv=None):
     print(f"      Prompt: {args.prompt}")
     print(f"      Steps: {args.steps}, Guidance: {args.guidance}, Control Scale: {args.control_scale}")
     extra = {} if args.strength is None else {"strength": args.strength}
-    if args.mask is not None:
-        if not os.path.exists(args.mask):
-            print(f"Error: Mask not found at {args.mask}")
-            return
-        extra.update(mask=Image.open(args.mask), mask_blur=args.mask_blur, paste_back=not args.no_paste_back)
-        print(f"      Mask: {args.mask} (blur {args.mask_blur}, paste-back {'off' if args.no_paste_back else 'on'})")
+    if args.mask is not None and not os.path.exists(args.mask):
+        print(f"Error: Mask not found at {args.mask}")
+        return
+    if args.outpaint is not None:
+        extra.update(outpaint=args.outpaint)
+        print("      Outpaint: left %d, top %d, right %d, bottom %d px" % args.outpaint)
+    if masked:
+        if args.mask is not None:
+            extra.update(mask=Image.open(args.mask))
+        extra.update(mask_blur=args.mask_blur, paste_back=not args.no_paste_back)
+        print(f"      Mask: {args.mask or 'the new border'} (blur {args.mask_blur}, paste-back {'off' if args.no_paste_back else 'on'})")
         if args.masked_content != "original":
             extra.update(masked_content=args.masked_content)
             print(f"      Masked content: {args.masked_content}")

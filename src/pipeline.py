@@ -132,15 +132,19 @@ class FastEditor:
         wait=False: returns (source, edge map, finish) with the kernels still in flight (NMS + CANNY_ROUNDS hysteresis rounds); finish()
         -- called once the stream has drained -- returns True when those rounds had NOT reached the fixed point: it has then run the
         remaining ones and rewritten the edge map, and whatever was computed from the map must be computed again.
-        `original`: a list that receives the source as uploaded, before the resize (what an inline metric scores against)."""
-        if size is not None and image.size != tuple(size) and image.mode != "RGB":
-            if original is not None:                    # the one case in which the upload below is not the original: score what evaluate.py would
-                original.append(torch.from_numpy(np.array(image.convert("RGB"))).to(self.pipe.ctx.device))
-            image = image.resize(size, Image.LANCZOS)
-        arr = np.array(image)
-        if arr.ndim == 2:
-            arr = np.stack([arr] * 3, axis=2)
-        src = torch.from_numpy(np.ascontiguousarray(arr[..., :3])).to(self.pipe.ctx.device)
+        `original`: a list that receives the source as uploaded, before the resize (what an inline metric scores against).
+        `image` may also be a u8 [H, W, 3] tensor already on the device (an outpainting canvas): it is taken as the upload."""
+        if torch.is_tensor(image):
+            src = image
+        else:
+            if size is not None and image.size != tuple(size) and image.mode != "RGB":
+                if original is not None:                # the one case in which the upload below is not the original: score what evaluate.py would
+                    original.append(torch.from_numpy(np.array(image.convert("RGB"))).to(self.pipe.ctx.device))
+                image = image.resize(size, Image.LANCZOS)
+            arr = np.array(image)
+            if arr.ndim == 2:
+                arr = np.stack([arr] * 3, axis=2)
+            src = torch.from_numpy(np.ascontiguousarray(arr[..., :3])).to(self.pipe.ctx.device)
         if original is not None and not original:
             original.append(src)
         if size is not None and (src.shape[1], src.shape[0]) != tuple(size):
@@ -163,7 +167,7 @@ class FastEditor:
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
              paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
-             blend="alpha", blend_levels=4, mask_grow=0):
+             blend="alpha", blend_levels=4, mask_grow=0, outpaint=None):
         """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
         [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
         latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
@@ -207,13 +211,31 @@ class FastEditor:
         outside the image and the image border does not erode.  The call returns exactly what it returns for the grown mask passed in: the latent
         mask, the feather, the fill, the blend, the source-size composite, `bg_*` / `clip_score_edited` and the box of region="mask" all see the
         grown mask, and a region crops it after it has grown.  One HIP op on the device; a mask shrunk to nothing returns
-        the source; 0 (default) launches nothing."""
+        the source; 0 (default) launches nothing.
+        [additive] `outpaint` (None, or (left, top, right, bottom): integers in 0..4096, at least one > 0): outpainting.  The picture is made larger
+        by that many pixels on each side and the model invents what lies in the new border.  The call returns exactly what
+        `edit(C, prompt, mask=M, ...)` returns with the same other arguments, where C is the canvas -- `image` (converted to RGB) with its edge
+        pixels replicated into the margins -- and M the canvas mask: 255 in the margins, `mask` as passed (or 0) over the source
+        (`outpaint_canvas()` returns the pair).  So the keyword counts as a mask for `mask_grow` (r > 0 grows the border r pixels into the source:
+        the seam is regenerated), `mask_blur`, `masked_content`, `blend` and region="mask"; `resolution="auto"` picks the bucket of the canvas;
+        output_size="source" returns the canvas's size with the caller's bytes wherever the mask is 0; an explicit `region` box is in canvas
+        coordinates.  With masked_content="original" the model starts from the replicated streaks and the edge map keeps their edges: "fill" or
+        "latent_noise" with mask_grow=8..32 is the usual recipe.  Source and mask are uploaded at their own size and the canvas is built by one
+        HIP op on the device in front of the job; None (default) launches nothing."""
         full = hregion.check_output(output_size, region)
-        hmask.check_args(mask_blur, paste_back, mask is not None)
-        hmask.check_content(masked_content, mask is not None)
-        hmask.check_blend(blend, blend_levels, mask is not None, paste_back)
-        grow = hmask.check_grow(mask_grow, mask is not None)
+        margins = hmask.check_outpaint(outpaint)
+        masked = mask is not None or margins is not None          # the new border is a mask of its own
+        hmask.check_args(mask_blur, paste_back, masked)
+        hmask.check_content(masked_content, masked)
+        hmask.check_blend(blend, blend_levels, masked, paste_back)
+        grow = hmask.check_grow(mask_grow, masked)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
+        if region is not None and margins is not None:            # a region crops on the host: the canvas comes back once, the rest is the call on it
+            canvas, canvas_mask = self._outpaint_host(image, mask_l, margins)
+            return self.edit(Image.fromarray(canvas), prompt, negative_prompt, strength, num_inference_steps, guidance_scale,
+                             controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold, seed, canvas_mask, mask_blur, paste_back,
+                             resolution=resolution, metrics=metrics, output_size=output_size, region=region, region_padding=region_padding,
+                             masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow)
         if region is not None:
             if grow:        # grown first, cropped second: the box of "mask" is the grown mask's, and pixels outside an explicit box reach into it
                 mask_l = self._grow_host(mask_l, grow)
@@ -225,7 +247,7 @@ class FastEditor:
             if metrics:
                 return hregion.paste(image, res[0], box), res[1]
             return hregion.paste(image, res, box)
-        size = buckets.target_size(resolution, image.size)
+        size = buckets.target_size(resolution, hmask.canvas_size(image.size, margins))
         generator = None
         if seed is not None:
             generator = torch.Generator(device=self.device).manual_seed(seed)
@@ -239,6 +261,8 @@ class FastEditor:
         # run and the device job is repeated on the final edge map -- same result as preprocess_image() + the pipeline call, always
         origs, omasks = ([], []) if metrics or full else (None, None)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
+            if margins is not None:         # from here on the canvas and its mask stand where the image and the mask stood, already on the device
+                image, mask_l = self._outpaint_device(image, mask_l, margins)
             source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False,
                                                                  original=origs)
             mask_dev = self._mask_device(mask_l, size, original=omasks, grow=grow)
@@ -253,7 +277,7 @@ class FastEditor:
                         blend_levels=blend_levels, paste_later=full)
         if not metrics:
             return res.images[0]
-        return res.images[0], self._scores(res.extra, [mask_l is not None])[0]
+        return res.images[0], self._scores(res.extra, [masked])[0]
 
     def _fullres(self, slot, origs, omasks, blur, then=None):
         """The `after_device` hook of an edit with output_size="source": queues, on the edit's stream behind its result and outside its graph, the
@@ -362,15 +386,40 @@ class FastEditor:
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(getattr(self._tls, "slot", 0))):
             return self.pipe.ctx.mask_grow(torch.from_numpy(mask_l).to(self.pipe.ctx.device), grow).cpu().numpy()
 
+    def _outpaint_device(self, image, mask_l, margins):
+        """PIL image, uint8 [H, W] mask or None, check_outpaint()'s margins -> (canvas u8 [Hc, Wc, 3], canvas mask u8 [Hc, Wc]) on the device:
+        source and mask are uploaded at their own size, the canvas is one launch (fie_outpaint_canvas_rgb_u8) on the current stream.  An image of
+        another mode than RGB goes through `.convert("RGB")`."""
+        dev = self.pipe.ctx.device
+        src = torch.from_numpy(np.array(image if image.mode == "RGB" else image.convert("RGB"))).to(dev)
+        return self.pipe.ctx.outpaint_canvas(src, None if mask_l is None else torch.from_numpy(mask_l).to(dev), margins)
+
+    def _outpaint_host(self, image, mask_l, margins):
+        """_outpaint_device(), back on the host as two numpy arrays: what a region edit crops.  One synchronising copy of the canvas and its mask
+        on the calling thread's slot stream."""
+        with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(getattr(self._tls, "slot", 0))):
+            canvas, canvas_mask = self._outpaint_device(image, mask_l, margins)
+            return canvas.cpu().numpy(), canvas_mask.cpu().numpy()
+
+    def outpaint_canvas(self, image, outpaint, mask=None):
+        """[additive] What `edit(image, ..., mask=mask, outpaint=outpaint)` runs on: (canvas, canvas mask) as PIL images of modes RGB and L, built
+        by the device op.  edit(canvas, ..., mask=canvas mask) is that call."""
+        margins = hmask.check_outpaint(outpaint)
+        if margins is None:
+            raise ValueError("outpaint_canvas: outpaint=None: (left, top, right, bottom)")
+        canvas, canvas_mask = self._outpaint_host(image, hmask.to_l_array(mask, image.size) if mask is not None else None, margins)
+        return Image.fromarray(canvas), Image.fromarray(canvas_mask)
+
     def _mask_device(self, mask_l, size, original=None, grow=0):
         """uint8 [H, W] mode-L mask (or None) -> u8 [size[1], size[0]] on the device: LANCZOS-resized as the source is (fie_resize_l_u8,
         bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`).  `original`: a list that receives the mask as uploaded (or None).
-        `grow` != 0: the uploaded mask is grown by that radius first (fie_mask_grow_u8), and it is the grown one that `original` receives."""
+        `grow` != 0: the uploaded mask is grown by that radius first (fie_mask_grow_u8), and it is the grown one that `original` receives.
+        `mask_l` may also be a u8 [H, W] tensor already on the device (an outpainting canvas's mask): it is taken as the upload."""
         if mask_l is None:
             if original is not None:
                 original.append(None)
             return None
-        m = torch.from_numpy(mask_l).to(self.pipe.ctx.device)
+        m = mask_l if torch.is_tensor(mask_l) else torch.from_numpy(mask_l).to(self.pipe.ctx.device)
         if grow:
             m = self.pipe.ctx.mask_grow(m, grow)
         if original is not None:
@@ -382,7 +431,7 @@ class FastEditor:
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
                    paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
-                   blend="alpha", blend_levels=4, mask_grow=0):
+                   blend="alpha", blend_levels=4, mask_grow=0, outpaint=None):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
         edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
@@ -395,19 +444,38 @@ class FastEditor:
         grouped by the target size of their crops, and an image whose entry is None is edited whole and returned at its source's size.
         `masked_content`: as edit()'s, one value for the whole call; an image whose mask is None is edited as without it.
         `blend` / `blend_levels`: as edit()'s, one value for the whole call; an image whose mask is None comes out as without them.
-        `mask_grow`: as edit()'s, one radius for the whole call; an image whose mask is None is untouched."""
+        `mask_grow`: as edit()'s, one radius for the whole call; an image whose mask is None is untouched.
+        `outpaint`: as edit()'s -- one (left, top, right, bottom) tuple for the whole call, or a LIST with one entry (a tuple or None) per image; an
+        image whose entry is None is treated as without the keyword, one with margins counts as masked.  Images group by the target size of their
+        canvases."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
             raise ValueError(f"{len(masks)} masks for {len(images)} images: one mask (or None) per image")
-        hmask.check_content(masked_content, masks is not None and any(m is not None for m in masks))
-        hmask.check_blend(blend, blend_levels, masks is not None and any(m is not None for m in masks), paste_back)
-        grow = hmask.check_grow(mask_grow, masks is not None and any(m is not None for m in masks))
+        if isinstance(outpaint, list) and len(outpaint) != len(images):
+            raise ValueError(f"{len(outpaint)} outpaint entries for {len(images)} images: one (left, top, right, bottom) or None per image")
+        margins = [hmask.check_outpaint(o) for o in outpaint] if isinstance(outpaint, list) else [hmask.check_outpaint(outpaint)] * len(images)
+        outpainted = any(o is not None for o in margins)
+        has_mask = [(masks is not None and masks[i] is not None) or o is not None for i, o in enumerate(margins)]
+        hmask.check_content(masked_content, any(has_mask))
+        hmask.check_blend(blend, blend_levels, any(has_mask), paste_back)
+        grow = hmask.check_grow(mask_grow, any(has_mask))
         regions = list(region) if isinstance(region, list) else [region] * len(images)
         if len(regions) != len(images):
             raise ValueError(f"{len(regions)} regions for {len(images)} images: one region (or None) per image")
         has_region = any(r is not None for r in regions)
         full = hregion.check_output(output_size, "mask" if has_region else None)
+        if has_region and outpainted:       # regions crop on the host: the canvases come back once (edit()), the rest is the call on them
+            hmask.check_args(mask_blur, paste_back, True)
+            canvases, cmasks = list(images), list(masks) if masks is not None else [None] * len(images)
+            for i, o in enumerate(margins):
+                if o is not None:
+                    c, m = self._outpaint_host(images[i], hmask.to_l_array(cmasks[i], images[i].size) if cmasks[i] is not None else None, o)
+                    canvases[i], cmasks[i] = Image.fromarray(c), m
+            return self.edit_batch(canvases, prompts, negative_prompts, strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
+                                   canny_low_threshold, canny_high_threshold, seed, cmasks, mask_blur, paste_back, resolution=resolution,
+                                   metrics=metrics, output_size=output_size, region=region, region_padding=region_padding,
+                                   masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow)
         if has_region:
             hmask.check_args(mask_blur, paste_back, masks is not None and any(m is not None for m in masks))
             mls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks or [None] * len(images), images)]
@@ -422,7 +490,7 @@ class FastEditor:
                                   blend=blend, blend_levels=blend_levels)
             outs = [o if b is None else hregion.paste(im, o, b) for im, o, b in zip(images, res[0] if metrics else res, boxes)]
             return (outs, res[1]) if metrics else outs
-        sizes = [buckets.target_size(resolution, im.size) for im in images]
+        sizes = [buckets.target_size(resolution, hmask.canvas_size(im.size, o)) for im, o in zip(images, margins)]
         groups = {}
         for i, sz in enumerate(sizes):
             groups.setdefault(sz, []).append(i)
@@ -435,17 +503,20 @@ class FastEditor:
                                       controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
                                       canny_high_threshold=canny_high_threshold, seed=seed, masks=pick(masks, idx), mask_blur=mask_blur,
                                       paste_back=paste_back, resolution=sz, metrics=metrics, output_size=output_size,
-                                      masked_content=masked_content if masks is not None and any(masks[i] is not None for i in idx) else "original",
-                                      blend=blend if masks is not None and any(masks[i] is not None for i in idx) else "alpha",
+                                      masked_content=masked_content if any(has_mask[i] for i in idx) else "original",
+                                      blend=blend if any(has_mask[i] for i in idx) else "alpha",
                                       blend_levels=blend_levels,
-                                      mask_grow=grow if masks is not None and any(masks[i] is not None for i in idx) else 0)
+                                      mask_grow=grow if any(has_mask[i] for i in idx) else 0,
+                                      outpaint=[margins[i] for i in idx] if outpainted else None)
                 res, ms = res if metrics else (res, [None] * len(idx))
                 for i, r, m in zip(idx, res, ms):
                     out[i], mets[i] = r, m
             return (out, mets) if metrics else out
         size = sizes[0]
-        hmask.check_args(mask_blur, paste_back, masks is not None and any(m is not None for m in masks))
+        hmask.check_args(mask_blur, paste_back, any(has_mask))
         mask_ls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks, images)] if masks is not None else None
+        if outpainted and mask_ls is None:
+            mask_ls = [None] * len(images)
         gens = None
         if seed is not None:
             gens = [torch.Generator(device=self.device).manual_seed(seed) for _ in images]
@@ -453,6 +524,11 @@ class FastEditor:
         srcs, ctls = [], []
         origs, omasks = ([], []) if metrics or full else (None, None)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
+            if outpainted:                  # the canvases and their masks stand where the images and the masks stood, already on the device
+                images = list(images)
+                for i, o in enumerate(margins):
+                    if o is not None:
+                        images[i], mask_ls[i] = self._outpaint_device(images[i], mask_ls[i], o)
             for im in images:
                 one = [] if metrics or full else None
                 s_dev, c_dev = self._canny_device(im, canny_low_threshold, canny_high_threshold, size=size, original=one)
