@@ -1,4 +1,4 @@
-// The arithmetic the image-side kernels share, stated once (resize, mask, mask_fill, multiband, fullres, metrics, clip_score, dino, pointwise .hip).
+// The arithmetic the image-side kernels share, stated once (resize, mask, mask_fill, multiband, fullres, outpaint, tile_blend, metrics, clip_score, dino, pointwise .hip).
 // Kernels that must agree bit for bit -- the fused full-resolution paste with the resize + mask_prep + composite sequence, the two patchify
 // kernels with each other's K order -- agree because they call the same function here, not because one restates the other.
 #pragma once
@@ -80,6 +80,30 @@ __device__ __forceinline__ float feather_vsum(const float* __restrict__ hrow, co
     float s = 0.f;
     for (int k = 0; k <= 2 * R; ++k) s += taps[k] * hrow[(ty + k) * TW + tx];
     return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- byte rows at any address
+// Rows of u8 pixels start wherever the rows before them end (outpaint, tile_blend .hip): a row is stored as a head of 0 .. 3 bytes up to the next
+// dword boundary of its ADDRESS, a body of whole aligned dwords and a tail of 0 .. 3 bytes, and read through aligned dwords likewise.
+
+// where a row of `len` bytes at address `row` splits: `head` bytes in front of the first aligned dword, `body` whole dwords behind them
+__device__ __forceinline__ void row_split(const uint8_t* row, int64_t len, int& head, int64_t& body) {
+    const int64_t h = (int64_t)((0 - (uintptr_t)row) & 3);
+    head = (int)(h < len ? h : len);
+    body = (len - head) >> 2;
+}
+
+// the four bytes at `a` (any alignment) of an operand that spans [lo, hi), as one little-endian dword: from the aligned dwords that cover them
+// when those lie inside the operand, else by bytes
+__device__ __forceinline__ uint32_t load4(const uint8_t* a, const uint8_t* lo, const uint8_t* hi) {
+    const unsigned sh = (unsigned)((uintptr_t)a & 3);
+    const uint8_t* al = a - sh;
+    if (sh == 0) return *reinterpret_cast<const uint32_t*>(a);
+    if (al >= lo && al + 8 <= hi) {
+        const uint32_t* d = reinterpret_cast<const uint32_t*>(al);
+        return __builtin_amdgcn_alignbyte(d[1], d[0], sh);
+    }
+    return (uint32_t)a[0] | (uint32_t)a[1] << 8 | (uint32_t)a[2] << 16 | (uint32_t)a[3] << 24;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the u8 blend

@@ -14,6 +14,9 @@
 
 namespace {
 
+using fie_img::load4;
+using fie_img::row_split;
+
 constexpr int kOutpaintMaxMargin = 4096;
 
 constexpr int kOutpaintRows = 4;           // canvas rows a thread takes, one after the other: enough work per wave to pay for its launch
@@ -22,26 +25,6 @@ struct OutpaintGeom {
     int H, W, left, top, Hc, Wc;
     unsigned canvas_slots;                 // 3 Wc / 4 + 1: the most dwords a canvas row can hold, and the slot of its head and tail
 };
-
-// where a row of `len` bytes at address `row` splits: `head` bytes in front of the first aligned dword, `body` whole dwords behind them
-__device__ __forceinline__ void row_split(const uint8_t* row, int64_t len, int& head, int64_t& body) {
-    const int64_t h = (int64_t)((0 - (uintptr_t)row) & 3);
-    head = (int)(h < len ? h : len);
-    body = (len - head) >> 2;
-}
-
-// the four bytes at `a` (any alignment) of an operand that spans [lo, hi), as one little-endian dword: from the aligned dwords that cover them
-// when those lie inside the operand, else by bytes
-__device__ __forceinline__ uint32_t load4(const uint8_t* a, const uint8_t* lo, const uint8_t* hi) {
-    const unsigned sh = (unsigned)((uintptr_t)a & 3);
-    const uint8_t* al = a - sh;
-    if (sh == 0) return *reinterpret_cast<const uint32_t*>(a);
-    if (al >= lo && al + 8 <= hi) {
-        const uint32_t* d = reinterpret_cast<const uint32_t*>(al);
-        return __builtin_amdgcn_alignbyte(d[1], d[0], sh);
-    }
-    return (uint32_t)a[0] | (uint32_t)a[1] << 8 | (uint32_t)a[2] << 16 | (uint32_t)a[3] << 24;
-}
 
 __device__ __forceinline__ uint8_t canvas_byte(const uint8_t* __restrict__ srow, const OutpaintGeom& g, int x, int c) {
     return srow[(int64_t)min(max(x - g.left, 0), g.W - 1) * 3 + c];

@@ -906,6 +906,36 @@ class Context:
         _chk(lib().fie_outpaint_canvas_rgb_u8(self.h, _p(src), _p(mask_l), h, w, left, top, right, bottom, _p(out[0]), _p(out[1])))
         return out[0], out[1]
 
+    def tile_blend(self, tiles, xs, ys, H, W, out=None):
+        """The back end of a tiled edit (fie_tile_blend_rgb_u8).  tiles: contiguous u8 [ny * nx, th, tw, 3] on the device, tile
+        j = iy * nx + ix at (xs[ix], ys[iy]); xs, ys: host lists of 1 .. 32 integers that start at 0, increase strictly, leave no gap and end at
+        W - tw / H - th (anything else is a ValueError).  -> u8 [H, W, 3]: every pixel the weighted mean of the tiles that cover it, a tile's weight
+        the distance to its nearest interior edge -- exactly fie_amd/tiles.py: blend_numpy.  `out`: a u8 [H, W, 3] tensor with contiguous
+        memory at any address, not the tiles'.  One launch, no synchronisation."""
+        from . import tiles as htiles
+        self.sync_stream()
+        if not torch.is_tensor(tiles) or tiles.dim() != 4 or tiles.shape[3] != 3 or tiles.dtype != torch.uint8 or not tiles.is_contiguous() \
+                or tiles.numel() == 0:
+            raise ValueError(f"tile_blend: contiguous u8 [n, th, tw, 3] tiles, got {tuple(getattr(tiles, 'shape', ()))} "
+                             f"{getattr(tiles, 'dtype', type(tiles).__name__)}")
+        n, th, tw, _ = tiles.shape
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in (H, W)) or H * W >= 1 << 31:
+            raise ValueError(f"tile_blend: H={H!r}, W={W!r}: integers >= 1 with fewer than 2^31 pixels")
+        H, W = int(H), int(W)
+        xs, ys = htiles.check_positions(xs, tw, W, "xs"), htiles.check_positions(ys, th, H, "ys")
+        if n != len(xs) * len(ys):
+            raise ValueError(f"tile_blend: {n} tiles for a grid of {len(xs)} x {len(ys)}")
+        if out is None:
+            out = self._alloc((H, W, 3), torch.uint8)
+        else:
+            lo, hi = tiles.data_ptr(), tiles.data_ptr() + tiles.numel()
+            if not torch.is_tensor(out) or tuple(out.shape) != (H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() \
+                    or (out.data_ptr() < hi and lo < out.data_ptr() + out.numel()):
+                raise ValueError(f"tile_blend: out must be a contiguous u8 {(H, W, 3)} tensor of its own")
+        cx, cy = (ctypes.c_int * len(xs))(*xs), (ctypes.c_int * len(ys))(*ys)
+        _chk(lib().fie_tile_blend_rgb_u8(self.h, _p(tiles), len(xs), len(ys), cx, cy, th, tw, H, W, _p(out)))
+        return out
+
     def mask_fill(self, src_u8, mask_l, ctl_u8=None, fill=True, out=None, cleared=None):
         """The masked-content pre-pass of a masked edit (fie_mask_fill_rgb_u8).  src_u8: u8 [H, W, 3]; mask_l: u8 [H, W]
         (hole = L >= 128); ctl_u8: None or the u8 [H, W, 3] edge map.  -> (filled, cleared): the source with the hole replaced by the push-pull

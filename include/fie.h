@@ -630,6 +630,21 @@ int fie_mask_grow_u8(fie_ctx* ctx, const uint8_t* mask_l, int H, int W, int radi
 int fie_outpaint_canvas_rgb_u8(fie_ctx* ctx, const uint8_t* src, const uint8_t* mask_l, int H, int W, int left, int top, int right, int bottom,
                                uint8_t* canvas, uint8_t* canvas_mask);
 
+/* ---- Tiled edits: ny x nx overlapping tiles of one size blended into one H x W image.
+ *   tiles u8 [ny * nx, th, tw, 3]: tile j = iy * nx + ix (row-major) lies at (xs[ix], ys[iy]).  xs [nx], ys [ny]: HOST arrays (they travel as kernel
+ *   arguments); nx, ny in 1 .. 32.  th, tw, H, W: any values >= 1, H * W < 2^31.  Per axis the positions start at 0, increase strictly, leave no gap
+ *   (p[i + 1] <= p[i] + t) and end at S - t.  out u8 [H, W, 3], at any address, overlapping nothing of tiles.
+ *   With w(u) = min(t if the tile is the first of its axis else u + 1, t if it is the last else t - u) -- the distance to the tile's nearest INTERIOR
+ *   edge: the image border fades nothing --, W_j = wy(y - ys[iy]) * wx(x - xs[ix]) and S = sum_j W_j over the tiles that cover (y, x):
+ *       out(y, x, c) = (sum_j W_j * tile_j(y - ys[iy], x - xs[ix], c) + (S >> 1)) / S
+ *   a linear crossfade over each overlap, exact in integers (fie_amd/tiles.py: blend_numpy restates it): where one tile covers a pixel the output is
+ *   that tile's byte, the blend of a source's own crops is the source, the output lies between the covering tiles' minimum and maximum.
+ *   FIE_EINVAL for anything else, NULL pointers included.  One launch at any size: a gather, no atomics, no f32, no workspace; 32-bit accumulators where
+ *   the geometry bounds the numerator below 2^32 (every plan of fie_amd/tiles.py), 64-bit ones otherwise; the output is stored as aligned dwords with
+ *   the 0 .. 3 bytes in front of and behind them in each row stored as bytes, the tiles are read as aligned dwords wherever those lie inside them; no
+ *   access is misaligned, none leaves its tensor.  Asynchronous on the ctx stream. */
+int fie_tile_blend_rgb_u8(fie_ctx* ctx, const uint8_t* tiles, int nx, int ny, const int* xs, const int* ys, int th, int tw, int H, int W, uint8_t* out);
+
 /* ---- Full-resolution back end of an edit: the edit-size result at the source's size, composited against the
  * source's own bytes.  res: u8 [h, w, 3], the edit-size result.  The output is H x W: up = Pillow's 8-bit LANCZOS resize of res to
  * (W, H), bit-exact (kx / bx / ksx, ky / by / ksy: the tables of fie_resize_rgb_u8 for w -> W and h -> H; a table is NULL on an axis

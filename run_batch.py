@@ -126,6 +126,40 @@ def add_outpaint_args(p):
     return p
 
 
+def tiles_arg(text):
+    """argparse type of --tiles: 'auto' or 'WxH' -> "auto" or (tw, th) (fie_amd/tiles.py: parse)."""
+    import fie_amd  # noqa: F401
+    from fie_amd import tiles as htiles
+    try:
+        return htiles.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def add_tile_args(p):
+    """[additive] tiled edits.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--tiles", type=tiles_arg, default=None, metavar="{auto,WxH}",
+                   help="[additive] tiled edits, for images above 1024^2 pixels: cover each image with overlapping tiles of one edit size ('auto': "
+                        "per axis the smallest legal size that still overlaps by --tile_overlap; WxH: multiples of 64, 512..2048, at most 1024^2 "
+                        "pixels), edit every tile at its native size and crossfade the results on the device into one image of the source's size.  "
+                        "Not with --resolution, --region mask, --outpaint")
+    p.add_argument("--tile_overlap", type=int, default=128, choices=range(0, 257), metavar="N",
+                   help="[additive] with --tiles: pixels neighbouring tiles share at least, 0..256")
+    p.add_argument("--tile_batch", type=int, default=4, choices=range(1, 17), metavar="N",
+                   help="[additive] with --tiles: tiles per device job, 1..16")
+    return p
+
+
+def tile_kwargs(args):
+    """The --tiles / --tile_overlap / --tile_batch flags (absent on a parser without add_tile_args) -> edit()'s keyword arguments."""
+    if getattr(args, "tiles", None) is None:
+        return {}
+    for flag, off in (("resolution", "square"), ("region", "none"), ("outpaint", None)):
+        if getattr(args, flag, off) != off:
+            raise ValueError(f"--tiles with --{flag}: the tile size is the edit size and the output is the source's size")
+    return dict(tiles=args.tiles, tile_overlap=getattr(args, "tile_overlap", 128), tile_batch=getattr(args, "tile_batch", 4))
+
+
 def add_resolution_args(p):
     """[additive] aspect-ratio edits.  Kept apart from build_parser() for the same reason as add_mask_args."""
     p.add_argument("--resolution", type=str, default="square",
@@ -278,7 +312,7 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     masked = use_mask or outpaint is not None      # --outpaint: the new border is a mask
     if outpaint is not None:
         extra = dict(extra, outpaint=tuple(outpaint))
-    extra = dict(extra, **region_kwargs(args, masked))
+    extra = dict(extra, **region_kwargs(args, masked), **tile_kwargs(args))
     masked_content = getattr(args, "masked_content", "original")
     if masked_content != "original":
         if not masked:
@@ -399,9 +433,13 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    parser = add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_outpaint_args(add_grow_args(add_blend_args(
-        add_mask_args(build_parser())))))))))
+    parser = add_tile_args(add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_outpaint_args(add_grow_args(
+        add_blend_args(add_mask_args(build_parser()))))))))))
     args = parser.parse_args(argv)
+    try:
+        tile_kwargs(args)
+    except ValueError as e:
+        parser.error(str(e))
     masked = args.use_mask or args.outpaint is not None                # --outpaint: the new border is a mask
     if args.region == "mask" and not masked:
         parser.error("--region mask needs --use_mask")

@@ -91,6 +91,30 @@ def build_parser():
     return p
 
 
+def tiles_arg(text):
+    """argparse type of --tiles: 'auto' or 'WxH' -> "auto" or (tw, th) (fie_amd/tiles.py: parse)."""
+    import fie_amd  # noqa: F401
+    from fie_amd import tiles as htiles
+    try:
+        return htiles.parse(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def add_tile_args(p):
+    """[additive] tiled edits, kept apart from build_parser() like run_batch.py's additive groups."""
+    p.add_argument("--tiles", type=tiles_arg, default=None, metavar="{auto,WxH}",
+                   help="[additive] tiled edit, for an image above 1024^2 pixels: cover it with overlapping tiles of one edit size ('auto': per axis "
+                        "the smallest legal size that still overlaps by --tile_overlap; WxH: multiples of 64, 512..2048, at most 1024^2 pixels), edit "
+                        "every tile at its native size and crossfade the results on the device into one image of the input's size.  Not with "
+                        "--resolution, --region mask, --outpaint")
+    p.add_argument("--tile_overlap", type=int, default=128, choices=range(0, 257), metavar="N",
+                   help="[additive] with --tiles: pixels neighbouring tiles share at least, 0..256")
+    p.add_argument("--tile_batch", type=int, default=4, choices=range(1, 17), metavar="N",
+                   help="[additive] with --tiles: tiles per device job, 1..16")
+    return p
+
+
 def save_plot(path, source_img, edited_img, model, prompt):
     import matplotlib
     matplotlib.use("Agg")
@@ -109,9 +133,12 @@ def save_plot(path, source_img, edited_img, model, prompt):
 
 
 def main(argv=None):
-    parser = build_parser()
+    parser = add_tile_args(build_parser())
     args = parser.parse_args(argv)
     masked = args.mask is not None or args.outpaint is not None        # --outpaint: the new border is a mask
+    if args.tiles is not None and (args.resolution != "square" or args.region != "none" or args.outpaint is not None):
+        parser.error("--tiles does not go with --resolution, --region mask or --outpaint: the tile size is the edit size and the output has the "
+                     "input's size")
     if args.region == "mask" and not masked:
         parser.error("--region mask needs --mask")
     if args.masked_content != "original" and not masked:
@@ -179,6 +206,10 @@ def main(argv=None):
         print(f"      Region: the mask's box + {args.region_padding} px, output at the source's size")
     elif args.output_size == "source":
         extra.update(output_size="source")
+    if args.tiles is not None:
+        extra.update(tiles=args.tiles, tile_overlap=args.tile_overlap, tile_batch=args.tile_batch)
+        extra.pop("output_size", None)
+        print(f"      Tiles: {args.tiles if args.tiles == 'auto' else '%dx%d' % args.tiles}, overlap {args.tile_overlap} px, {args.tile_batch} per device job")
     t0 = time.time()
     edited_img = editor.edit(image=source_img, prompt=args.prompt, negative_prompt=args.negative_prompt,
                              num_inference_steps=args.steps, guidance_scale=args.guidance,

@@ -20,6 +20,7 @@ from fie_amd import buckets, hip, stack
 from fie_amd import mask as hmask
 from fie_amd import metrics as hmetrics
 from fie_amd import region as hregion
+from fie_amd import tiles as htiles
 from fie_amd.pipe import DeviceOutput, HipImg2ImgPipeline
 
 
@@ -103,6 +104,7 @@ class FastEditor:
         self.controlnet = self.pipe.controlnet
         self._tls = threading.local()          # .slot: graph slot of the calling worker thread (set_in_flight)
         self._fullres_out = {}                 # (slot, image) -> flat u8 buffer on the device, grown to the largest source: the full-resolution back end's output (output_size="source")
+        self._tile_bufs = {}                   # (slot, tiles, th, tw) -> u8 [tiles, th, tw, 3] on the device: where the tile results of a tiled edit meet (tiles=...)
         self._metric_rows = {}                 # (slot, images) -> pinned int64 [images, 4]: where an edit's metric rows land (metrics=True)
         self.clip_scorer = None                # fie_amd.clip_score.ClipScorer: only from a directory, never a made-up number
         self._clip_rows = {}                   # (slot, rows) -> pinned f32 [rows, 2]: where an edit's CLIP score rows land
@@ -167,7 +169,7 @@ class FastEditor:
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
              paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
-             blend="alpha", blend_levels=4, mask_grow=0, outpaint=None):
+             blend="alpha", blend_levels=4, mask_grow=0, outpaint=None, tiles=None, tile_overlap=128, tile_batch=4):
         """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
         [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
         latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
@@ -221,7 +223,32 @@ class FastEditor:
         output_size="source" returns the canvas's size with the caller's bytes wherever the mask is 0; an explicit `region` box is in canvas
         coordinates.  With masked_content="original" the model starts from the replicated streaks and the edge map keeps their edges: "fill" or
         "latent_noise" with mask_grow=8..32 is the usual recipe.  Source and mask are uploaded at their own size and the canvas is built by one
-        HIP op on the device in front of the job; None (default) launches nothing."""
+        HIP op on the device in front of the job; None (default) launches nothing.
+        [additive] `tiles` (None, "auto", (tw, th) or "WxH"), `tile_overlap` (0..256, default 128), `tile_batch` (1..16, default 4): a tiled edit, for
+        images above 1024^2 pixels.  The image is covered by overlapping tiles of one legal edit size (fie_amd/tiles.py: plan -- "auto" picks per
+        axis the smallest size that still overlaps by `tile_overlap`), every tile is edited at its native size, `tile_batch` tiles per device job,
+        and the results are crossfaded across their overlaps into one image of the source's size.  Exactly: with (tw, th, xs, ys) the plan and the
+        tiles' crops of `image.convert("RGB")` in tile order, the call returns `tiles.blend_numpy(R, xs, ys, H, W)` where R is the concatenation,
+        over `tiles.chunks(n, tile_batch)`, of `edit_batch(crops, [prompt] * len(crops), resolution=(tw, th), masks=the mask's crops, ...)`; every
+        tile carries `seed`.  The mask keywords apply per tile through the mask's crop (`mask_grow` grows the mask first and crops it second); with
+        a mask and `paste_back` every byte outside the mask is the source's.  `metrics=True` scores (source, output).  Source and mask are
+        uploaded once, the tiles are device slices, the blend is one HIP op behind the last job (csrc/tile_blend.hip) and the only image that
+        crosses to the host is the result.  `resolution`, `region`, `outpaint` and output_size="edit" with tiles are a
+        ValueError; None (default) changes nothing."""
+        tiles, tile_overlap, tile_batch = htiles.check(tiles, tile_overlap, tile_batch)
+        if tiles is not None:
+            self._check_tiled(resolution, region, outpaint, output_size)
+            masked = mask is not None
+            hmask.check_args(mask_blur, paste_back, masked)
+            hmask.check_content(masked_content, masked)
+            hmask.check_blend(blend, blend_levels, masked, paste_back)
+            grow = hmask.check_grow(mask_grow, masked)
+            return self._edit_tiled(image, prompt, negative_prompt, htiles.plan(image.size, tiles, tile_overlap), tile_batch,
+                                    hmask.to_l_array(mask, image.size) if masked else None, grow, metrics,
+                                    dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                         controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
+                                         canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
+                                         masked_content=masked_content, blend=blend, blend_levels=blend_levels))
         full = hregion.check_output(output_size, region)
         margins = hmask.check_outpaint(outpaint)
         masked = mask is not None or margins is not None          # the new border is a mask of its own
@@ -431,7 +458,7 @@ class FastEditor:
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
                    paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
-                   blend="alpha", blend_levels=4, mask_grow=0, outpaint=None):
+                   blend="alpha", blend_levels=4, mask_grow=0, outpaint=None, tiles=None, tile_overlap=128, tile_batch=4):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
         edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
@@ -447,11 +474,31 @@ class FastEditor:
         `mask_grow`: as edit()'s, one radius for the whole call; an image whose mask is None is untouched.
         `outpaint`: as edit()'s -- one (left, top, right, bottom) tuple for the whole call, or a LIST with one entry (a tuple or None) per image; an
         image whose entry is None is treated as without the keyword, one with margins counts as masked.  Images group by the target size of their
-        canvases."""
+        canvases.
+        `tiles` / `tile_overlap` / `tile_batch`: as edit()'s; every image is tiled on its own (its tiles alone fill its device jobs) and the results
+        come back in input order."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
             raise ValueError(f"{len(masks)} masks for {len(images)} images: one mask (or None) per image")
+        if htiles.check(tiles, tile_overlap, tile_batch)[0] is not None:
+            self._check_tiled(resolution, region, outpaint, output_size)
+            has_mask = [masks is not None and m is not None for m in (masks or [None] * len(images))]
+            hmask.check_args(mask_blur, paste_back, any(has_mask))
+            hmask.check_content(masked_content, any(has_mask))
+            hmask.check_blend(blend, blend_levels, any(has_mask), paste_back)
+            hmask.check_grow(mask_grow, any(has_mask))
+            negs = list(negative_prompts) if isinstance(negative_prompts, (list, tuple)) else [negative_prompts or ""] * len(images)
+            if len(negs) != len(images):
+                raise ValueError(f"{len(negs)} negative prompts for {len(images)} images")
+            res = []
+            for i, (im, p) in enumerate(zip(images, prompts)):         # an image whose mask is None is edited as without the mask keywords
+                mk = dict(mask=masks[i], mask_blur=mask_blur, masked_content=masked_content, blend=blend, blend_levels=blend_levels,
+                          mask_grow=mask_grow) if has_mask[i] else {}
+                res.append(self.edit(im, p, negs[i], strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
+                                     canny_low_threshold, canny_high_threshold, seed, paste_back=paste_back, metrics=metrics, output_size=output_size,
+                                     tiles=tiles, tile_overlap=tile_overlap, tile_batch=tile_batch, **mk))
+            return ([r[0] for r in res], [r[1] for r in res]) if metrics else res
         if isinstance(outpaint, list) and len(outpaint) != len(images):
             raise ValueError(f"{len(outpaint)} outpaint entries for {len(images)} images: one (left, top, right, bottom) or None per image")
         margins = [hmask.check_outpaint(o) for o in outpaint] if isinstance(outpaint, list) else [hmask.check_outpaint(outpaint)] * len(images)
@@ -512,26 +559,40 @@ class FastEditor:
                 for i, r, m in zip(idx, res, ms):
                     out[i], mets[i] = r, m
             return (out, mets) if metrics else out
-        size = sizes[0]
         hmask.check_args(mask_blur, paste_back, any(has_mask))
         mask_ls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks, images)] if masks is not None else None
         if outpainted and mask_ls is None:
             mask_ls = [None] * len(images)
+        res, omasks = self._batch_job(images, prompts, negative_prompts, sizes[0], mask_ls, margins if outpainted else None, grow, metrics, full,
+                                      dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                           controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
+                                           canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
+                                           masked_content=masked_content, blend=blend, blend_levels=blend_levels))
+        if not metrics:
+            return res.images
+        return res.images, self._scores(res.extra, [m is not None for m in omasks])
+
+    def _batch_job(self, images, prompts, negative_prompts, size, mask_ls, margins, grow, metrics, full, kw, after=None):
+        """The single-size tail of edit_batch(): ONE device job for images that share the target `size`.  images: PIL images, or u8 [H, W, 3] tensors
+        already on the device (the tiles of a tiled edit: slices of one upload); mask_ls: None, or one uint8 [H, W] array / device tensor / None per
+        image; margins: None, or check_outpaint()'s tuple / None per image; kw: the scalar keywords of edit().  `after`: an `after_device` hook that
+        stands in place of the scorer and the full-resolution back end (metrics and full are then False).  -> (the pipeline's result, the masks as
+        uploaded)."""
         gens = None
-        if seed is not None:
-            gens = [torch.Generator(device=self.device).manual_seed(seed) for _ in images]
+        if kw["seed"] is not None:
+            gens = [torch.Generator(device=self.device).manual_seed(kw["seed"]) for _ in images]
         slot = getattr(self._tls, "slot", 0)
         srcs, ctls = [], []
         origs, omasks = ([], []) if metrics or full else (None, None)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
-            if outpainted:                  # the canvases and their masks stand where the images and the masks stood, already on the device
+            if margins is not None:         # the canvases and their masks stand where the images and the masks stood, already on the device
                 images = list(images)
                 for i, o in enumerate(margins):
                     if o is not None:
                         images[i], mask_ls[i] = self._outpaint_device(images[i], mask_ls[i], o)
             for im in images:
                 one = [] if metrics or full else None
-                s_dev, c_dev = self._canny_device(im, canny_low_threshold, canny_high_threshold, size=size, original=one)
+                s_dev, c_dev = self._canny_device(im, kw["canny_low_threshold"], kw["canny_high_threshold"], size=size, original=one)
                 srcs.append(s_dev)
                 ctls.append(c_dev)
                 if one is not None:
@@ -539,17 +600,77 @@ class FastEditor:
             mask_devs = [self._mask_device(m, size, original=omasks, grow=grow) for m in mask_ls] if mask_ls is not None else None
         if (metrics or full) and mask_ls is None:
             omasks = [None] * len(images)
-        hook = self._scorer(slot, origs, omasks, list(prompts)) if metrics else None
+        hook = after
+        if metrics:
+            hook = self._scorer(slot, origs, omasks, list(prompts))
         if full:
-            hook = self._fullres(slot, origs, omasks if paste_back else [None] * len(images), mask_blur, hook)
+            hook = self._fullres(slot, origs, omasks if kw["paste_back"] else [None] * len(images), kw["mask_blur"], hook)
         res = self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls,
-                        strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                        controlnet_conditioning_scale=controlnet_conditioning_scale, generator=gens, mask_image=mask_devs,
-                        mask_blur=0 if full else mask_blur, paste_back=paste_back and not full, after_device=hook,
-                        masked_content=masked_content, blend=blend, blend_levels=blend_levels, paste_later=full)
+                        strength=kw["strength"], num_inference_steps=kw["num_inference_steps"], guidance_scale=kw["guidance_scale"],
+                        controlnet_conditioning_scale=kw["controlnet_conditioning_scale"], generator=gens, mask_image=mask_devs,
+                        mask_blur=0 if full else kw["mask_blur"], paste_back=kw["paste_back"] and not full, after_device=hook,
+                        masked_content=kw["masked_content"], blend=kw["blend"], blend_levels=kw["blend_levels"], paste_later=full)
+        return res, omasks
+
+    def _check_tiled(self, resolution, region, outpaint, output_size):
+        """What a tiled edit cannot be combined with: the tiles ARE the edit size and the output IS the source's size."""
+        if resolution is not None:
+            raise ValueError(f"tiles with resolution={resolution!r}: the tile size is the edit size (tiles=(tw, th))")
+        if region is not None:
+            raise ValueError("tiles with a region: a region edit runs on one crop")
+        if outpaint is not None:
+            raise ValueError("tiles with outpaint: build the canvas first (outpaint_canvas()) and tile that")
+        hregion.check_output(output_size, None)
+        if output_size == "edit":
+            raise ValueError("tiles with output_size='edit': a tiled edit returns the source-size image (output_size='source')")
+
+    def _edit_tiled(self, image, prompt, negative_prompt, plan, tile_batch, mask_l, grow, metrics, kw):
+        """edit(..., tiles=...) behind its argument checks (the docstring of edit() defines the result).  plan: tiles.plan()'s (tw, th, xs, ys);
+        mask_l: None or the uint8 [H, W] mask; grow: check_grow()'s radius; kw: the scalar keywords of edit().  Source and mask go up once and the
+        mask grows there, whole; the tiles of a device job are contiguous copies of their boxes; each job's `after_device` hook copies its u8
+        results into their rows of the slot's [n, th, tw, 3] buffer and keeps them off the host; the hook of the last job queues the blend (and,
+        with metrics, the scorer behind it) and hands the H x W x 3 image to the pipeline's device-to-host copy."""
+        tw, th, xs, ys = plan
+        W, H = image.size
+        ctx, slot = self.pipe.ctx, getattr(self._tls, "slot", 0)
+        n = len(xs) * len(ys)
+        with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
+            src = torch.from_numpy(np.array(image if image.mode == "RGB" else image.convert("RGB"))).to(ctx.device)
+            mask_dev = None
+            if mask_l is not None:
+                mask_dev = torch.from_numpy(mask_l).to(ctx.device)
+                if grow:
+                    mask_dev = ctx.mask_grow(mask_dev, grow)
+            key = (slot, n, th, tw)
+            if key not in self._tile_bufs:
+                self._tile_bufs = {k: v for k, v in self._tile_bufs.items() if k[0] != slot}          # one plan's buffer per slot
+                self._tile_bufs[key] = torch.empty((n, th, tw, 3), device=ctx.device, dtype=torch.uint8)
+            buf = self._tile_bufs[key]
+            out = self._fullres_out.get((slot, 0))           # the source-size output shares the full-resolution back end's buffer
+            if out is None or out.numel() < src.numel():
+                out = self._fullres_out[(slot, 0)] = torch.empty(src.numel(), device=ctx.device, dtype=torch.uint8)
+            out = out[:src.numel()].view(src.shape)
+        scorer = self._scorer(slot, [src], [mask_dev], [prompt]) if metrics else None
+        jobs = htiles.chunks(n, tile_batch)
+        boxes = htiles.boxes(tw, th, xs, ys)
+        cut = lambda t, b: t[b[1]:b[3], b[0]:b[2]].contiguous()
+        res = None
+        for c in jobs:
+            def collect(out_u8, c=c):
+                with self.pipe.eager_lock:                # the context's stream binding is shared by the threads of in-flight edits
+                    buf[c[0]:c[0] + len(c)].copy_(out_u8 if out_u8.dim() == 4 else out_u8[None])
+                    if c[-1] != n - 1:
+                        return DeviceOutput([])           # nothing of this job crosses to the host
+                    ctx.tile_blend(buf, xs, ys, H, W, out=out)
+                return DeviceOutput([out], scorer(out) if scorer is not None else None)
+            with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
+                crops = [cut(src, boxes[j]) for j in c]
+                mcrops = [cut(mask_dev, boxes[j]) for j in c] if mask_dev is not None else None
+            res, _ = self._batch_job(crops, [prompt] * len(c), [negative_prompt or ""] * len(c), (tw, th), mcrops, None, 0, False, False, kw,
+                                     after=collect)
         if not metrics:
-            return res.images
-        return res.images, self._scores(res.extra, [m is not None for m in omasks])
+            return res.images[0]
+        return res.images[0], self._scores(res.extra, [mask_dev is not None])[0]
 
     def calibrate_fp8(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                       controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=0, margin=2.0):
