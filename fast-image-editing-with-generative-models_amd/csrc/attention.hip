@@ -399,7 +399,9 @@ __global__ __launch_bounds__(NWV * 64) void attn2_kernel(AttnArgs p) {
             if (t == 0 || __any(mx > THR)) {
                 // move the reference: rows whose max grew (or every row on the first tile) are re-based
                 const float delta = t == 0 ? mx : fmaxf(mx, 0.f);
-                const float alpha = __builtin_amdgcn_exp2f(-delta);
+                // first tile: o and l are still zero and keep it -- a row whose scores all lie below -128 (log2 domain) has exp2(-delta) = inf, and
+                // 0 * inf made the whole row NaN
+                const float alpha = t == 0 ? 1.0f : __builtin_amdgcn_exp2f(-delta);
                 mref[a] += delta;
                 negm[a] = (f32x4){-mref[a], -mref[a], -mref[a], -mref[a]};
                 lrun[a] *= alpha;

@@ -4,7 +4,9 @@
 // GroupNorm over NHWC [B, rows, C] with the channel dim optionally split over two source tensors (the UNet up
 // blocks' concat is never materialised before its GroupNorm).  Three launches:
 //   1. partial sums   grid (chunks, B, csplit): each thread owns ONE 8-channel column chunk and walks rows,
-//                     block-reduces to per-group (sum, sumsq) partials -> workspace [B][chunks][G][2] (deterministic)
+//                     block-reduces to per-group (sum, sumsq) partials -> workspace [B][chunks][G][2] (deterministic).
+//                     The sums are taken of x - pivot, the pivot being the group's first value (gn_pivot): with the raw values
+//                     a group whose mean is 64 sigma loses 12 bits of its variance to E[x^2] - mean^2 in the fp32 partials
 //   2. finalize       one thread per (b, g): reduce chunk partials -> (mean, rstd)
 //   3. apply          same thread->column mapping; y = x * a_c + b_c with a, b folded from gamma/beta/mean/rstd, SiLU
 #include "fie_internal.h"
@@ -29,6 +31,7 @@ struct GnArgsT {
     float* partial;          // [B][nchunks][G][2]
     float* stats;            // [B][G][2] mean, rstd
     float o8_inv;            // > 0: Y is e4m3 bytes (value * o8_inv, saturated to +-448): the consumer is an fp8-activation conv (gemm_x8.hip)
+    int shifted;             // the partial sums are of x - gn_pivot (gn_partial_kernel); 0: of x (a producer's epilogue wrote them)
     int pg;                  // producer-written partials only (gn_finalize_wide_kernel): slots per granule row; 0 = G.  pg > G: group g is the sum
                              // of the pg / G consecutive slots (4-channel quads) from g * pg / G on -- the 20 / 40-channel groups of the UNet
 };
@@ -47,6 +50,35 @@ __device__ __forceinline__ void gn_load(const GnArgsT<T>& p, int64_t row_global,
     else fie_load8(p.X2 + row_global * p.C2 + (c0 - p.C1), x);
 }
 
+// The value the three-kernel plan shifts group g of image b by before it sums: the group's first element.  Any member of the group keeps
+// |x - pivot| within a few sigma, so the shifted second moment carries the variance at full fp32 precision whatever the group's mean is.
+template <typename T>
+__device__ __forceinline__ float gn_pivot(const GnArgsT<T>& p, int b, int g) {
+    const int c = g * p.cg;
+    const int64_t row = (int64_t)b * p.rows;
+    return c < p.C1 ? (float)p.X1[row * p.C1 + c] : (float)p.X2[row * p.C2 + (c - p.C1)];
+}
+
+// Sums a producer's epilogue left (fie_gn_stats_target) are raw fp32 sums of y and y^2 per 32-row granule: a group whose mean lies many sigma
+// from zero has lost its variance to E[y^2] - mean^2 (12 bits at 64 sigma), while its mean is still good to fp32.  Such a group --
+// mean^2 > GN_REFINE * var, i.e. beyond 8 sigma -- takes its variance from the tensor itself instead: the threads that finalize it sum
+// (y - mean)^2 over the group's rows in fp64 (t of nt threads; the caller reduces).  Every other group pays one compare.
+constexpr double GN_REFINE = 64.0;
+
+template <typename T>
+__device__ __forceinline__ double gn_centred_m2(const GnArgsT<T>& p, int b, int g, double mean, int t, int nt) {
+    const T* src = p.X1 + (int64_t)b * p.rows * p.C + g * p.cg;
+    double m2 = 0.0;
+    for (int64_t r = t; r < p.rows; r += nt) {
+        const T* row = src + r * p.C;
+        for (int c = 0; c < p.cg; ++c) {
+            const double d = (double)(float)row[c] - mean;
+            m2 += d * d;
+        }
+    }
+    return m2;
+}
+
 template <typename T>
 __global__ __launch_bounds__(GN_THREADS) void gn_partial_kernel(GnArgsT<T> p) {
     __shared__ float red[GN_THREADS * 16];
@@ -59,6 +91,14 @@ __global__ __launch_bounds__(GN_THREADS) void gn_partial_kernel(GnArgsT<T> p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] = ss[j] = 0.f;
     if (active) {
+        float pv[8];
+        int gprev = -1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int g = (c0 + j) / p.cg;
+            pv[j] = g == gprev ? pv[j > 0 ? j - 1 : 0] : gn_pivot(p, b, g);
+            gprev = g;
+        }
         const int64_t r_begin = (int64_t)blockIdx.x * p.rows_per_chunk;
         const int64_t r_end = min(r_begin + p.rows_per_chunk, p.rows);
         for (int64_t r = r_begin + rsub; r < r_end; r += p.rpp) {
@@ -66,8 +106,9 @@ __global__ __launch_bounds__(GN_THREADS) void gn_partial_kernel(GnArgsT<T> p) {
             gn_load(p, (int64_t)b * p.rows + r, c0, v);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                s[j] += v[j];
-                ss[j] += v[j] * v[j];
+                const float d = v[j] - pv[j];
+                s[j] += d;
+                ss[j] += d * d;
             }
         }
     }
@@ -116,11 +157,18 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(GnArgsT<T> p, int B) {
         a += __shfl_xor(a, o);
         q += __shfl_xor(q, o);
     }
+    const double n = (double)p.rows * p.cg;
+    double mean = a / n;                                   // (every lane holds the totals)
+    double var = q / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    if (p.shifted) mean += (double)gn_pivot(p, b, g);
+    else if (p.X1 && mean * mean > GN_REFINE * var) {     // gathered producer sums of a group far from zero (wave-uniform): see gn_centred_m2
+        double m2 = gn_centred_m2(p, b, g, mean, lane, 64);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o);
+        var = m2 / n;
+    }
     if (lane == 0) {
-        const double n = (double)p.rows * p.cg;
-        const double mean = a / n;
-        double var = q / n - mean * mean;
-        if (var < 0.0) var = 0.0;
         p.stats[i * 2] = (float)mean;
         p.stats[i * 2 + 1] = (float)(1.0 / sqrt(var + (double)p.eps));
     }
@@ -166,13 +214,22 @@ __global__ __launch_bounds__(256) void gn_finalize_wide_kernel(GnArgsT<T> p, int
     }
     if (lane == 0) { red[wave * 2] = a; red[wave * 2 + 1] = q; }
     __syncthreads();
+    a = (red[0] + red[2]) + (red[4] + red[6]);             // every thread forms the same totals: the decision below is block-uniform
+    q = (red[1] + red[3]) + (red[5] + red[7]);
+    const double n = (double)p.rows * p.cg;
+    const double mean = a / n;
+    double var = q / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    if (p.X1 && mean * mean > GN_REFINE * var) {          // a group far from zero: see gn_centred_m2
+        double m2 = gn_centred_m2(p, b, g, mean, tid, 256);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o);
+        __syncthreads();                                   // red[] has been read by everyone
+        if (lane == 0) red[wave] = m2;
+        __syncthreads();
+        var = ((red[0] + red[1]) + (red[2] + red[3])) / n;
+    }
     if (tid == 0) {
-        a = (red[0] + red[2]) + (red[4] + red[6]);
-        q = (red[1] + red[3]) + (red[5] + red[7]);
-        const double n = (double)p.rows * p.cg;
-        const double mean = a / n;
-        double var = q / n - mean * mean;
-        if (var < 0.0) var = 0.0;
         p.stats[i * 2] = (float)mean;
         p.stats[i * 2 + 1] = (float)(1.0 / sqrt(var + (double)p.eps));
     }
@@ -525,6 +582,7 @@ int groupnorm_t(const char* who, fie_ctx* ctx, const void* X1, int C1, const voi
         return FIE_OK;
     }
     p.partial = (float*)workspace;
+    p.shifted = 1;
     p.stats = p.partial + (int64_t)B * GN_MAX_CHUNKS * groups * 2;
     const dim3 grid((unsigned)p.nchunks, (unsigned)B, (unsigned)csplit);
     FIE_DESC(ctx, "groupnorm partial B=%d rows=%lld C=%d G=%d bytes=%.0f", B, (long long)rows_per_image, C, groups, 1.0 * B * rows_per_image * C * sizeof(T));
@@ -612,16 +670,16 @@ __global__ __launch_bounds__(256) void gn_coef_kernel(GnArgsT<T> p, float* coef)
 
 extern "C" {
 
-int fie_groupnorm_coef_f16(fie_ctx* ctx, int C, int B, int64_t rows_per_image, int groups, const void* gamma, const void* beta, float eps, const void* partial,
-                           void* workspace, int partial_groups, float* coef) {
+int fie_groupnorm_coef_f16(fie_ctx* ctx, const void* X, int C, int B, int64_t rows_per_image, int groups, const void* gamma, const void* beta, float eps,
+                           const void* partial, void* workspace, int partial_groups, float* coef) {
     const char* who = "fie_groupnorm_coef_f16";
-    FIE_REQUIRE(ctx && gamma && beta && partial && workspace && coef, "%s: NULL argument", who);
+    FIE_REQUIRE(ctx && X && gamma && beta && partial && workspace && coef, "%s: NULL argument", who);
     FIE_REQUIRE(C > 0 && C % 8 == 0 && B > 0 && groups > 0 && C % groups == 0 && rows_per_image > 0 && rows_per_image % 32 == 0,
                 "%s: bad shape C=%d G=%d rows=%lld", who, C, groups, (long long)rows_per_image);
     FIE_REQUIRE(partial_groups == 0 || partial_groups == groups || (partial_groups > groups && partial_groups % groups == 0 && partial_groups * 4 == C),
                 "%s: partial_groups=%d must be 0, the group count, or C / 4 quads divisible into the %d groups", who, partial_groups, groups);
     GnArgs p = {};
-    p.C1 = C; p.C = C; p.G = groups; p.cg = C / groups; p.rows = rows_per_image;
+    p.X1 = (const half_t*)X; p.C1 = C; p.C = C; p.G = groups; p.cg = C / groups; p.rows = rows_per_image;
     p.gamma = (const half_t*)gamma; p.beta = (const half_t*)beta; p.eps = eps;
     p.stats = (float*)workspace + (int64_t)B * GN_MAX_CHUNKS * groups * 2;
     const int ngran = (int)(rows_per_image / 32);

@@ -703,7 +703,7 @@ class Context:
         if self._keep is not None:
             self._keep.append(ws)
         coef = self._alloc((b, c, 2), torch.float32)
-        _chk(lib().fie_groupnorm_coef_f16(self.h, c, b, rows, groups, _p(gamma), _p(beta), float(eps), _p(tag[0]), _p(ws), tag[7], _p(coef)))
+        _chk(lib().fie_groupnorm_coef_f16(self.h, _p(x), c, b, rows, groups, _p(gamma), _p(beta), float(eps), _p(tag[0]), _p(ws), tag[7], _p(coef)))
         return coef
 
     def conv3x3_gn(self, x, coef, silu, wp, cout, bias=None, residual=None, gn_groups=None, out=None):

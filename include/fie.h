@@ -442,9 +442,10 @@ int fie_gn_stats_target(fie_ctx* ctx, void* partial, int64_t rows_per_image, int
  * result has the bits of fie_groupnorm_stats_nhwc_f16 followed by fie_conv3x3_nhwc_f16 on tile code 72, without the read + write of the normalised tensor.
  * Built for what fie_conv3x3_gn_ok returns 1 for (one image, H, W % 16 == 0, Cin in whole 64-channel chunks from 128 to 1024, Cout % 128 == 0) WITH a
  * fie_gn_stats_target armed for the OUTPUT at 4 / 8 / 16 channels per group (out_groups) -- every resnet conv of the VAE; elsewhere the caller keeps the two
- * launches.  workspace as for fie_groupnorm_nhwc_f16. */
-int fie_groupnorm_coef_f16(fie_ctx* ctx, int C, int B, int64_t rows_per_image, int groups, const void* gamma, const void* beta, float eps, const void* partial,
-                           void* workspace, int partial_groups, float* coef);
+ * launches.  workspace as for fie_groupnorm_nhwc_f16.  X [B, rows, C] is the tensor the sums were taken of: a group whose mean lies beyond 8 sigma takes its
+ * variance from X itself (the raw fp32 sums of y^2 have lost it), here and in fie_groupnorm_stats_nhwc_f16. */
+int fie_groupnorm_coef_f16(fie_ctx* ctx, const void* X, int C, int B, int64_t rows_per_image, int groups, const void* gamma, const void* beta, float eps,
+                           const void* partial, void* workspace, int partial_groups, float* coef);
 int fie_conv3x3_gn_ok(fie_ctx* ctx, int B, int H, int W, int Cin, int Cout, int out_groups);
 int fie_conv3x3_gn_nhwc_f16(fie_ctx* ctx, const void* X, int B, int H, int W, int Cin, const float* coef, int silu, const void* Wpacked, int64_t ldw, void* Y,
                             int64_t ldc, int Cout, const void* bias, const void* residual, int64_t ldr);
