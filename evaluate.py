@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Evaluation harness -- drop-in for /root/reference/evaluate.py (same flags, same `metrics.csv` columns and
 `summary.json` layout, reference :193-271), on the metrics this build restates (`src/metrics.py`: SSIM, PSNR, MSE).
-LPIPS / CLIP score / DINO distance need checkpoints: without a local model directory (`--clip_score_dir`, `--dino_dir`) their cells are empty in
-the CSV and `null` in the JSON; LPIPS always.
+LPIPS / CLIP score / DINO distance need checkpoints: without a local model directory (`--lpips_dir`, `--clip_score_dir`, `--dino_dir`) their cells
+are empty in the CSV and `null` in the JSON.
 Additive: `--use_mask` appends the background-preservation columns `bg_ssim, bg_psnr, bg_mse` (each item's PIE-Bench `mask`; both images
-zeroed inside the edited region first) to the CSV and to `summary.json`.  Pairs are scored in chunks: on a GPU one launch per chunk.
+zeroed inside the edited region first) to the CSV and to `summary.json`, and `bg_lpips` behind them with an LPIPS directory.
+Pairs are scored in chunks: on a GPU one launch per chunk.
 
 Under `torch.distributed.run` the mapping entries are sharded image-parallel over the ranks (fie_amd.dist) and rank 0
 writes the merged files -- the "gather of metrics" of SURVEY.md 8e.
@@ -27,6 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 METRICS = ("ssim", "lpips", "clip_score", "psnr", "mse", "dino_distance")
 FIELDS = ["image_id", "image_path", "editing_type_id", "editing_prompt", *METRICS]
 BG_METRICS = ("bg_ssim", "bg_psnr", "bg_mse")
+BG_LPIPS_METRICS = ("bg_lpips",)                 # only with --use_mask AND an LPIPS weight directory (--lpips_dir)
 EDITED_METRICS = ("clip_score_edited",)          # only with --use_mask AND a CLIP model directory (--clip_score_dir)
 CHUNK = 16                      # pairs per calculate_pairs() call (one device launch and one synchronisation each)
 KNOWN_SUFFIXES = ("sdxl_fp32", "sdxl_fp16", "ssd-1b_fp32", "ssd-1b_fp16")
@@ -71,6 +73,23 @@ def add_dino_args(p):
     return p
 
 
+def add_lpips_args(p):
+    """[additive] LPIPS.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--lpips_dir", type=str, default=None,
+                   help="[additive] a local directory with the LPIPS SqueezeNet weights (model.safetensors, or torchvision's squeezenet1_1*.pth beside "
+                        "the lpips package's squeeze.pth): fills the lpips column (and, with --use_mask, adds bg_lpips behind bg_mse).  Default: "
+                        "FIE_LPIPS_DIR, else <FIE_WEIGHTS_DIR>/lpips when it exists; without one the column stays empty")
+    return p
+
+
+def extra_columns(args, calc):
+    """The columns behind the reference's: bg_* with --use_mask, bg_lpips / clip_score_edited when the calculator also has that model."""
+    if not getattr(args, "use_mask", False):
+        return ()
+    return (BG_METRICS + (BG_LPIPS_METRICS if getattr(calc, "_lpips", None) is not None else ())
+            + (EDITED_METRICS if getattr(calc, "_clip", None) is not None else ()))
+
+
 def default_paths(args):
     tail = os.path.basename(args.outputs_dir.rstrip("/"))
     sub = f"{tail}/" if args.outputs_dir.rstrip("/").endswith(KNOWN_SUFFIXES) else ""
@@ -105,7 +124,8 @@ def evaluate_entries(entries, args, calc, progress=None):
     rows, skipped = [], 0
     use_mask = getattr(args, "use_mask", False)
     with_edited = use_mask and getattr(calc, "_clip", None) is not None
-    names = METRICS + (BG_METRICS if use_mask else ()) + (EDITED_METRICS if with_edited else ())
+    with_bg_lpips = use_mask and getattr(calc, "_lpips", None) is not None
+    names = METRICS + extra_columns(args, calc)
     if use_mask:
         from fie_amd import mask as hmask
     pending = []                                   # (index, image_id, rel, entry, source, edited, mask) awaiting one calculate_pairs() call
@@ -140,11 +160,21 @@ def evaluate_entries(entries, args, calc, progress=None):
                     dinos[i] = d
             except Exception as e:
                 print(f"\n      Error computing DINO distances: {e}")
-        for (index, image_id, rel, entry, a, b, _), m, cs, dd in zip(pending, ms, clips, dinos):
+        lps = [None] * len(pending)
+        if getattr(calc, "_lpips", None) is not None:     # the chunk's LPIPS (and background LPIPS) in one batched pass
+            try:
+                lps = calc.calculate_lpipses([p[4] for p in pending], [p[5] for p in pending], [p[6] for p in pending] if use_mask else None)
+            except Exception as e:
+                print(f"\n      Error computing LPIPS: {e}")
+        for (index, image_id, rel, entry, a, b, _), m, cs, dd, lp in zip(pending, ms, clips, dinos, lps):
             if m is None:
                 continue
             m = calc.with_unavailable(m, None, None, entry.get("editing_prompt", ""))
             m["dino_distance"] = dd
+            if lp:
+                m.update(lp)
+            if with_bg_lpips:
+                m.setdefault("bg_lpips", None)
             if cs:
                 m.update(cs)
             if with_edited:
@@ -176,7 +206,7 @@ def evaluate_entries(entries, args, calc, progress=None):
 
 
 def main(argv=None):
-    args = add_dino_args(add_clip_args(add_mask_args(build_parser()))).parse_args(argv)
+    args = add_lpips_args(add_dino_args(add_clip_args(add_mask_args(build_parser())))).parse_args(argv)
     import fie_amd  # noqa: F401
     from fie_amd import dist as fdist
     from src.metrics import MetricsCalculator
@@ -190,7 +220,7 @@ def main(argv=None):
     say(f"\n[2/4] Scanning outputs in {args.outputs_dir}")
     say(f"\n[3/4] Initializing metrics on {args.device}...")
     device = args.device if world == 1 or not args.device.startswith("cuda") else f"cuda:{local}"
-    calc = MetricsCalculator(device=device, clip_dir=args.clip_score_dir, dino_dir=args.dino_dir)
+    calc = MetricsCalculator(device=device, clip_dir=args.clip_score_dir, dino_dir=args.dino_dir, lpips_dir=args.lpips_dir)
     mine = fdist.shard([(i, k, e) for i, (k, e) in enumerate(mapping.items())], rank, world)
     progress = None
     if rank == 0:
@@ -211,12 +241,12 @@ def main(argv=None):
         return
     print("\n[4/4] Saving results...")
     with open(args.results_file, "w", newline="") as fh:
-        edited = list(EDITED_METRICS) if args.use_mask and getattr(calc, "_clip", None) is not None else []
-        w = csv.DictWriter(fh, fieldnames=FIELDS + (list(BG_METRICS) if args.use_mask else []) + edited, extrasaction="ignore")
+        extra = extra_columns(args, calc)
+        w = csv.DictWriter(fh, fieldnames=FIELDS + list(extra), extrasaction="ignore")
         w.writeheader()
         w.writerows([{k: ("" if v is None else v) for k, v in r.items()} for r in rows])
     print(f"      Saved detailed metrics to: {args.results_file}")
-    summary = summarize(rows, METRICS + (BG_METRICS if args.use_mask else ()) + tuple(edited))
+    summary = summarize(rows, METRICS + extra)
     with open(args.summary_file, "w") as fh:
         json.dump(summary, fh, indent=2)
     print(f"      Saved summary statistics to: {args.summary_file}")
@@ -227,7 +257,9 @@ def main(argv=None):
               ("clip_score", "CLIP Score:", ".2f"), ("dino_distance", "DINO Dist.:", ".4f"))
     if args.use_mask:
         labels += (("bg_ssim", "Bg SSIM:   ", ".4f"), ("bg_psnr", "Bg PSNR:   ", ".2f"), ("bg_mse", "Bg MSE:    ", ".6f"))
-    if edited:
+    if "bg_lpips" in extra:
+        labels += (("bg_lpips", "Bg LPIPS:  ", ".4f"),)
+    if "clip_score_edited" in extra:
         labels += (("clip_score_edited", "CLIP edited:", ".2f"),)
     for k, label, spec in labels:
         print(f"  {label} {fmt(summary['overall'][k], spec)}")

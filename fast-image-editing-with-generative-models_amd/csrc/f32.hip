@@ -144,6 +144,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(G32 p) {
                 if (p.act == FIE_ACT_SILU) x = x / (1.0f + expf(-x));
                 else if (p.act == FIE_ACT_GELU) x = fie_gelu_exact(x);
                 else if (p.act == FIE_ACT_QUICK_GELU) x = x / (1.0f + expf(-1.702f * x));
+                else if (p.act == FIE_ACT_RELU) x = fmaxf(x, 0.f);
                 x *= p.scale;
                 if (p.res) x += p.res[(int64_t)m * p.ldr + n + r];
                 C[(int64_t)m * p.ldc + n + r] = x;
@@ -190,7 +191,7 @@ int fie_gemm_f32(fie_ctx* ctx, const float* A1, int64_t lda1, int K1, const floa
                  int64_t sC2) {
     FIE_REQUIRE(ctx && A1 && W && C, "fie_gemm_f32: NULL ctx/A1/W/C");
     FIE_REQUIRE(M > 0 && N > 0 && K > 0 && K1 > 0 && K1 <= K && (K1 == K || A2), "fie_gemm_f32: bad shape M=%d N=%d K=%d K1=%d", M, N, K, K1);
-    FIE_REQUIRE(act >= FIE_ACT_NONE && act <= FIE_ACT_GEGLU && !(act == FIE_ACT_GEGLU && (residual || N % 2)), "fie_gemm_f32: bad epilogue");
+    FIE_REQUIRE(act >= FIE_ACT_NONE && act <= FIE_ACT_RELU && !(act == FIE_ACT_GEGLU && (residual || N % 2)), "fie_gemm_f32: bad epilogue");
     FIE_REQUIRE(nb1 >= 1 && nb2 >= 1 && (int64_t)nb1 * nb2 <= 65535, "fie_gemm_f32: bad batch %d x %d", nb1, nb2);
     FIE_REQUIRE(!rowbias || rows_per_batch > 0, "fie_gemm_f32: rowbias needs rows_per_batch");
     G32 a = {};
@@ -206,7 +207,7 @@ int fie_conv3x3_nhwc_f32(fie_ctx* ctx, const float* X, int B, int H, int W, int 
                          const float* rowbias, int64_t ld_rowbias, const float* residual, int64_t ldr, float scale, int act) {
     FIE_REQUIRE(ctx && X && Wkc && Y, "fie_conv3x3_nhwc_f32: NULL ctx/X/W/Y");
     FIE_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (stride == 1 || stride == 2) && (pad_mode == 0 || pad_mode == 1) &&
-                    act != FIE_ACT_GEGLU && ldw >= 9 * Cin, "fie_conv3x3_nhwc_f32: bad argument");
+                    act >= FIE_ACT_NONE && act <= FIE_ACT_RELU && act != FIE_ACT_GEGLU && ldw >= 9 * Cin, "fie_conv3x3_nhwc_f32: bad argument");
     const int ups = upsample2x ? 1 : 0, pads = pad_mode == 0 ? 2 : 1;
     const int OH = ((H << ups) + pads - 3) / stride + 1, OW = ((W << ups) + pads - 3) / stride + 1;
     G32 a = {};

@@ -1,4 +1,4 @@
-// The arithmetic the image-side kernels share, stated once (resize, mask, mask_fill, multiband, fullres, outpaint, tile_blend, metrics, clip_score, dino, pointwise .hip).
+// The arithmetic the image-side kernels share, stated once (resize, mask, mask_fill, multiband, fullres, outpaint, tile_blend, metrics, clip_score, dino, lpips, pointwise .hip).
 // Kernels that must agree bit for bit -- the fused full-resolution paste with the resize + mask_prep + composite sequence, the two patchify
 // kernels with each other's K order -- agree because they call the same function here, not because one restates the other.
 #pragma once

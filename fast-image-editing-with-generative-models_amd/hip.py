@@ -21,6 +21,7 @@ _P, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 # include/fie.h is the one statement of the ABI (fie_amd/header.py reads it): the FIE_ACT_* codes, name -> argtypes of every declared function
 # (out-pointers are c_void_p: byref(), string buffers and ctypes arrays all pass), the return types and the config structs below
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_QUICK_GELU, ACT_GEGLU = (header.DEFINES["ACT_" + n] for n in ("NONE", "SILU", "GELU", "QUICK_GELU", "GEGLU"))
+ACT_RELU = header.DEFINES["ACT_RELU"]                  # the fp32 entries only (gemm_f32 / conv3x3_f32: the LPIPS tower)
 SIGNATURES = {name: args for name, (_, args) in header.FUNCTIONS.items()}
 
 _lib = None
@@ -503,11 +504,7 @@ class Context:
             out = self._alloc((m, nout), torch.uint8 if out_f8 else None)
         assert a.stride(1) == 1 and out.stride(1) == 1
         if self.f32:
-            _chk(lib().fie_gemm_f32(self.h, _p(a), a.stride(0), k1, _p(a2), a2.stride(0) if a2 is not None else 0, _p(wp),
-                                    wp.stride(0), 0, _p(out), out.stride(0), m, n, ktot, _p(bias), _p(rowbias),
-                                    rowbias.stride(0) if rowbias is not None else 0, rows_per_batch, _p(residual),
-                                    residual.stride(0) if residual is not None else 0, float(scale), act, 1, 1, 0, 0, 0, 0, 0, 0))
-            return out
+            return self.gemm_f32(a, wp, n, out, a2=a2, bias=bias, rowbias=rowbias, rows_per_batch=rows_per_batch, residual=residual, scale=scale, act=act)
         if a.dtype == torch.uint8:                      # e4m3 activations (written by a producer with out_f8) x e4m3 weights
             assert isinstance(wp, W8) and a2 is None and wp.stride(0) % 128 == 0, "fp8 activations need fp8 weights packed with Kpad % 128 == 0"
             if out_f8 and out.dtype != torch.uint8:
@@ -528,6 +525,21 @@ class Context:
                                 rowbias.stride(0) if rowbias is not None else 0, rows_per_batch, _p(residual),
                                 residual.stride(0) if residual is not None else 0, float(scale), act))
         out._gn_tag = tag
+        return out
+
+    def gemm_f32(self, a, wp, n, out=None, a2=None, bias=None, rowbias=None, rows_per_batch=0, residual=None, scale=1.0, act=ACT_NONE):
+        """gemm() on fp32 tensors through fie_gemm_f32, from a context of either dtype (the fp32 context's gemm() is this): a [M, K1] (+ a2 [M, K2])
+        f32, wp plain [N, K] f32 weights, out [M, n] f32 (row stride free).  act may be ACT_RELU."""
+        self.sync_stream()
+        m, k1 = a.shape
+        ktot = k1 + (a2.shape[1] if a2 is not None else 0)
+        if out is None:
+            out = self._alloc((m, n // 2 if act == ACT_GEGLU else n), torch.float32)
+        assert a.stride(1) == 1 and out.stride(1) == 1 and a.dtype == torch.float32 and wp.dtype == torch.float32 and out.dtype == torch.float32
+        _chk(lib().fie_gemm_f32(self.h, _p(a), a.stride(0), k1, _p(a2), a2.stride(0) if a2 is not None else 0, _p(wp),
+                                wp.stride(0), 0, _p(out), out.stride(0), m, n, ktot, _p(bias), _p(rowbias),
+                                rowbias.stride(0) if rowbias is not None else 0, rows_per_batch, _p(residual),
+                                residual.stride(0) if residual is not None else 0, float(scale), act, 1, 1, 0, 0, 0, 0, 0, 0))
         return out
 
     def fold_layernorm(self, w, bias, gamma, beta, geglu=False):
@@ -617,13 +629,30 @@ class Context:
                                                rowbias.stride(0) if rowbias is not None else 0, _p(residual),
                                                residual.stride(2) if residual is not None else 0, float(scale), act))
             return out
-        fn = lib().fie_conv3x3_nhwc_f32 if self.f32 else lib().fie_conv3x3_nhwc_f16
+        if self.f32:
+            out = self.conv3x3_f32(x, wp, cout, out, stride=stride, pad_mode=pad_mode, upsample=upsample, bias=bias, rowbias=rowbias, residual=residual,
+                                   scale=scale, act=act)
+            out._gn_tag = None
+            return out
         tag = self._gn_stats_arm(b * oh * ow, cout, oh * ow, gn_groups) if gn_groups and ldc == cout else None
-        _chk(fn(self.h, _p(x), b, h, w, cin, int(upsample), stride, pad_mode, _p(wp),
+        _chk(lib().fie_conv3x3_nhwc_f16(self.h, _p(x), b, h, w, cin, int(upsample), stride, pad_mode, _p(wp),
                                         wp.stride(0), _p(out), out.stride(2), cout, _p(bias), _p(rowbias),
                                         rowbias.stride(0) if rowbias is not None else 0, _p(residual),
                                         residual.stride(2) if residual is not None else 0, float(scale), act))
         out._gn_tag = tag
+        return out
+
+    def conv3x3_f32(self, x, wp, cout, out, stride=1, pad_mode=0, upsample=False, bias=None, rowbias=None, residual=None, scale=1.0, act=ACT_NONE):
+        """conv3x3() on fp32 tensors through fie_conv3x3_nhwc_f32, from a context of either dtype (the fp32 context's conv3x3() is this): x [B, H, W, Cin]
+        f32 contiguous, wp [cout, 9 Cin] f32 in (ky, kx, ci) order, out a [B, OH, OW, >= cout] f32 tensor or channel range of one (its pixel stride
+        is the row stride the op writes with).  act may be ACT_RELU."""
+        self.sync_stream()
+        b, h, w, cin = x.shape
+        assert x.is_contiguous() and x.dtype == torch.float32 and wp.dtype == torch.float32 and out.dtype == torch.float32 and out.stride(3) == 1
+        _chk(lib().fie_conv3x3_nhwc_f32(self.h, _p(x), b, h, w, cin, int(upsample), stride, pad_mode, _p(wp),
+                                        wp.stride(0), _p(out), out.stride(2), cout, _p(bias), _p(rowbias),
+                                        rowbias.stride(0) if rowbias is not None else 0, _p(residual),
+                                        residual.stride(2) if residual is not None else 0, float(scale), act))
         return out
 
     def attention(self, q, k, v, heads, head_dim, tq, tk, batch, out=None, causal=False, scale=None, out_f8=False, out_inv_scale=1.0):
@@ -1182,6 +1211,63 @@ class Context:
         if out is None:
             out = self._alloc((n,), torch.float64)
         _chk((lib().fie_selfsim_mse_f32 if self.f32 else lib().fie_selfsim_mse_f16)(self.h, _p(keys_a), _p(keys_b), keys_a.stride(0), n, t, c, _p(ws), _p(out)))
+        return out
+
+    # ------------------------------------------------------------------ LPIPS (csrc/lpips.hip): fp32 in every context
+    def lpips_stem(self, rgb_u8, lut, w, bias, mask=None, out=None):
+        """u8 [n, H, W, 3] (mask: None or u8 [n, H, W], non-zero = the pixel counts as black) -> f32 [n, OH, OW, 64]: the scaled input through
+        the table `lut` f32 [3, 256], conv 3 -> 64 k3 stride 2 without padding (w f32 [27, 64], bias f32 [64]) and ReLU, one launch
+        (fie_lpips_stem_u8_f32).  `out`: a contiguous f32 tensor of that shape to write (the images of a larger batch)."""
+        self.sync_stream()
+        n, h, wd, c = rgb_u8.shape
+        if c != 3 or rgb_u8.dtype != torch.uint8 or not rgb_u8.is_contiguous() or h < 3 or wd < 3:
+            raise ValueError(f"lpips_stem: a contiguous u8 [n, H, W, 3] tensor of at least 3 x 3, got {tuple(rgb_u8.shape)} {rgb_u8.dtype}")
+        if mask is not None and (tuple(mask.shape) != (n, h, wd) or mask.dtype != torch.uint8 or not mask.is_contiguous()):
+            raise ValueError(f"lpips_stem: mask must be a contiguous u8 {(n, h, wd)} tensor, got {tuple(mask.shape)} {mask.dtype}")
+        f32c = lambda t, shape: t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()
+        if not (f32c(lut, (3, 256)) and f32c(w, (27, 64)) and f32c(bias, (64,))):
+            raise ValueError("lpips_stem: lut f32 [3, 256], w f32 [27, 64] and bias f32 [64], contiguous")
+        shape = (n, (h - 3) // 2 + 1, (wd - 3) // 2 + 1, 64)
+        if out is None:
+            out = self._alloc(shape, torch.float32)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"lpips_stem: out must be a contiguous f32 {shape} tensor, got {tuple(out.shape)} {out.dtype}")
+        _chk(lib().fie_lpips_stem_u8_f32(self.h, _p(rgb_u8), _p(mask), n, h, wd, _p(lut), _p(w), _p(bias), _p(out)))
+        return out
+
+    def maxpool3s2(self, x, out=None):
+        """f32 [n, H, W, C] contiguous, C % 4 == 0 -> f32 [n, OH, OW, C]: MaxPool2d(3, stride 2, ceil_mode=True), bit-equal to torch's
+        (fie_maxpool3s2_nhwc_f32; one launch)."""
+        self.sync_stream()
+        if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[3] % 4 or min(x.shape[1:3]) < 2:
+            raise ValueError(f"maxpool3s2: a contiguous f32 [n, H, W, C] tensor of at least 2 x 2 with C % 4 == 0, got {tuple(x.shape)} {x.dtype}")
+        n, h, w, c = x.shape
+        shape = (n, (h - 2) // 2 + 1, (w - 2) // 2 + 1, c)
+        if out is None:
+            out = self._alloc(shape, torch.float32)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"maxpool3s2: out must be a contiguous f32 {shape} tensor, got {tuple(out.shape)} {out.dtype}")
+        _chk(lib().fie_maxpool3s2_nhwc_f32(self.h, _p(x), n, h, w, c, _p(out)))
+        return out
+
+    def lpips_layer(self, fa, fb, w, out=None):
+        """fa, fb: f32 [P, HW, C] contiguous, the same tap of the two sides of P pairs; w: f32 [C], the tap's `lin` weight -> f64 [P]: the mean
+        over the pixels of sum_c w_c (fa / sqrt(1e-8 + |fa|^2) - fb / sqrt(1e-8 + |fb|^2))^2 (fie_lpips_layer_f32: two launches, no
+        synchronisation).  `out`: a f64 [P] tensor or column of a [P, k] one to write."""
+        self.sync_stream()
+        ok = lambda t: t.dim() == 3 and t.dtype == torch.float32 and t.is_contiguous()
+        if not ok(fa) or not ok(fb) or fa.shape != fb.shape or fa.shape[2] % 64 or fa.shape[2] > 512 or fa.shape[0] < 1 or fa.shape[1] < 1:
+            raise ValueError(f"lpips_layer: two contiguous f32 [P, HW, C] tensors of one shape, C % 64 == 0 and C <= 512, got {tuple(fa.shape)} {fa.dtype} "
+                             f"and {tuple(fb.shape)} {fb.dtype}")
+        p, hw, c = fa.shape
+        if w.dtype != torch.float32 or tuple(w.shape) != (c,) or not w.is_contiguous():
+            raise ValueError(f"lpips_layer: w must be a contiguous f32 {(c,)} tensor, got {tuple(w.shape)} {w.dtype}")
+        if out is None:
+            out = self._alloc((p,), torch.float64)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (p,):
+            raise ValueError(f"lpips_layer: out must be a f64 {(p,)} tensor, got {tuple(out.shape)} {out.dtype}")
+        ws = self._alloc((lib().fie_lpips_layer_workspace_bytes(p, hw) // 8,), torch.int64)
+        _chk(lib().fie_lpips_layer_f32(self.h, _p(fa), _p(fb), p, hw, c, _p(w), _p(ws), _p(out), out.stride(0)))
         return out
 
     def canny_device(self, rgb_u8, low=100, high=200, out=None):

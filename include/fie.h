@@ -41,6 +41,7 @@ extern "C" {
 #define FIE_ACT_GELU 2        /* exact erf GELU */
 #define FIE_ACT_QUICK_GELU 3  /* x * sigmoid(1.702 x), CLIP-L */
 #define FIE_ACT_GEGLU 4       /* weight rows interleaved (value, gate): out[j] = v_j * gelu(g_j); N counts both */
+#define FIE_ACT_RELU 5        /* max(x, 0): fie_gemm_f32 and fie_conv3x3_nhwc_f32 only (the LPIPS tower); every f16 / f8 entry refuses it */
 
 typedef struct fie_ctx fie_ctx;
 
@@ -358,6 +359,7 @@ int fie_conv3x3_x8_nhwc_f16(fie_ctx* ctx, const void* X8, int B, int H, int W, i
  *   fie_gemm_f32: as fie_gemm_f16 with plain (unpacked) weights W [N][ldw] -- or [K][ldw] when w_is_kn -- and a two-level
  *     batch (z1 < nb1, z2 < nb2; element strides sA*, sW*, sC*) that serves the attention products over (image, head).
  *   fie_conv3x3_nhwc_f32: weights [Cout][(ky, kx, ci)] (ldw >= 9*Cin).
+ *   These two also take act = FIE_ACT_RELU (max(x, 0), in the epilogue's usual place: bias -> act -> scale -> residual).
  *   fie_softmax_rows_f32: in-place softmax(scale * S) per row, keys > (row % tq) masked when causal.
  *   the *_f32 norm / element-wise entries mirror their f16 twins with fp32 tensors. */
 int fie_gemm_f32(fie_ctx* ctx, const float* A1, int64_t lda1, int K1, const float* A2, int64_t lda2, const float* W,
@@ -728,6 +730,25 @@ int fie_dino_patches_u8_f32(fie_ctx* ctx, const uint8_t* src, int n, int H, int 
 int64_t fie_selfsim_workspace_bytes(int n, int T);
 int fie_selfsim_mse_f16(fie_ctx* ctx, const void* keys_a, const void* keys_b, int64_t ld, int n, int T, int C, void* workspace, double* out);
 int fie_selfsim_mse_f32(fie_ctx* ctx, const void* keys_a, const void* keys_b, int64_t ld, int n, int T, int C, void* workspace, double* out);
+
+/* ---- LPIPS (SqueezeNet 1.1) on the device: what stands around the Fire modules, which run on fie_gemm_f32 / fie_conv3x3_nhwc_f32
+ * with FIE_ACT_RELU.  fp32 only, in every context.  All asynchronous on the ctx stream, none synchronises, none uses atomics.
+ *   fie_lpips_stem_u8_f32    src: u8 [n, H, W, 3]; mask: NULL or u8 [n, H, W], a pixel with a non-zero byte counts as bytes (0, 0, 0).  lut f32 [3][256]:
+ *                            byte -> scaled input per channel (fie_amd/lpips.py: input_lut); w f32 [27][64], k = (ky * 3 + kx) * 3 + ci; bias f32 [64].
+ *                            out f32 [n, OH, OW, 64] = relu(conv k3 stride 2 without padding), OH = (H - 3) / 2 + 1, OW likewise.  H, W >= 3; out, w,
+ *                            bias 16-byte aligned.  One launch.
+ *   fie_maxpool3s2_nhwc_f32  x f32 [n, H, W, C] -> y f32 [n, OH, OW, C], MaxPool2d(3, stride 2, ceil_mode=True): OH = ceil((H - 3) / 2) + 1, windows
+ *                            clipped at the far edge, bit-equal to ATen's.  H, W >= 2, C % 4 == 0, 16-byte aligned.  One launch.
+ *   fie_lpips_layer_f32      fa, fb f32 [P, HW, C] contiguous: one tap of P pairs.  out[p * ld_out] = mean over the HW pixels of
+ *                            sum_c w[c] (fa / sqrt(1e-8 + sum_c fa^2) - fb / sqrt(1e-8 + sum_c fb^2))^2 as a double.  C % 64 == 0, C <= 512; P <= 65535.
+ *                            workspace: fie_lpips_layer_workspace_bytes(P, HW) bytes (-1 for shapes the op refuses), 8-byte aligned: one fp64
+ *                            partial per block of 64 pixels.  Two launches.  Deterministic: a pair's bits depend neither on P nor on its position, an
+ *                            identical pair gives exactly 0, an all-zero pixel contributes 0. */
+int fie_lpips_stem_u8_f32(fie_ctx* ctx, const uint8_t* src, const uint8_t* mask, int n, int H, int W, const float* lut, const float* w, const float* bias,
+                          float* out);
+int fie_maxpool3s2_nhwc_f32(fie_ctx* ctx, const float* x, int n, int H, int W, int C, float* y);
+int64_t fie_lpips_layer_workspace_bytes(int P, int HW);
+int fie_lpips_layer_f32(fie_ctx* ctx, const float* fa, const float* fb, int P, int HW, int C, const float* w, void* workspace, double* out, int64_t ld_out);
 
 #ifdef __cplusplus
 }

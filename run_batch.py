@@ -6,7 +6,7 @@ shards the selected entries image-parallel over N GPUs (fie_amd.dist) and rank 0
     python run_batch.py --num_images 50 --editing_types 0 1 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run_batch.py --model ssd-1b
 
-Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir, --dino_dir.
+Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir, --dino_dir, --lpips_dir.
 """
 import argparse
 import json
@@ -221,7 +221,16 @@ def add_dino_args(p):
     return p
 
 
-METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse", "clip_score", "clip_score_edited", "dino_distance")
+def add_lpips_args(p):
+    """[additive] LPIPS of every edit.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--lpips_dir", type=str, default=None,
+                   help="[additive] with --metrics: a local directory with the LPIPS SqueezeNet weights (model.safetensors, or torchvision's "
+                        "squeezenet1_1*.pth beside the lpips package's squeeze.pth); adds lpips (and bg_lpips with --use_mask) to every row.  "
+                        "Default: FIE_LPIPS_DIR, else <weights_dir>/lpips when it exists")
+    return p
+
+
+METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse", "clip_score", "clip_score_edited", "dino_distance", "lpips", "bg_lpips")
 
 
 def select_entries(mapping, args, say=print):
@@ -433,8 +442,8 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    parser = add_tile_args(add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_outpaint_args(add_grow_args(
-        add_blend_args(add_mask_args(build_parser()))))))))))
+    parser = add_tile_args(add_lpips_args(add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_outpaint_args(add_grow_args(
+        add_blend_args(add_mask_args(build_parser())))))))))))
     args = parser.parse_args(argv)
     try:
         tile_kwargs(args)
@@ -477,8 +486,12 @@ def main(argv=None):
     mine = fdist.shard([(i, k, e) for i, (k, e) in enumerate(selected)], rank, world)
 
     say(f"\n[3/3] Initializing FastEditor ({model_suffix})...")
-    clip_dir = dino_dir = None
+    clip_dir = dino_dir = lpips_dir = None
     if args.metrics:
+        from fie_amd import lpips as hlpips
+        lpips_dir = hlpips.resolve_dir(args.lpips_dir)
+        if lpips_dir is None and args.weights_dir and os.path.isdir(os.path.join(args.weights_dir, "lpips")):
+            lpips_dir = os.path.join(args.weights_dir, "lpips")
         from fie_amd import dino as hdino
         dino_dir = hdino.resolve_dir(args.dino_dir)
         if dino_dir is None and args.weights_dir and os.path.isdir(os.path.join(args.weights_dir, "dino")):
@@ -495,7 +508,7 @@ def main(argv=None):
         editor = FastEditor(model_name=args.model, device="cuda" if world == 1 else f"cuda:{local % max(torch.cuda.device_count(), 1)}",
                             enable_cpu_offload=not args.no_cpu_offload, use_full_precision=args.full_precision,
                             use_full_controlnet=args.full_controlnet, weights_dir=args.weights_dir,
-                            clip_score_dir=clip_dir, dino_dir=dino_dir)
+                            clip_score_dir=clip_dir, dino_dir=dino_dir, lpips_dir=lpips_dir)
     if hasattr(editor, "pipe"):
         editor.pipe.set_progress_bar_config(disable=True)
     mem = editor.get_memory_usage()

@@ -5,7 +5,8 @@ MI355X-native `FastEditor`.
     python run_single_image.py --image path/to/image.jpg --prompt "a rusty bicycle"
 
 `--compute_metrics` reports the metrics this build restates (SSIM, PSNR, MSE); LPIPS / CLIP score / DINO need
-checkpoints that cannot be fetched offline and are reported as unavailable instead of silently skipped."""
+checkpoints that cannot be fetched offline: each is computed on the device from a local directory (`--lpips_dir`,
+`--clip_score_dir`, `--dino_dir`) and reported as unavailable, instead of silently skipped, without one."""
 import argparse
 import os
 
@@ -88,6 +89,9 @@ def build_parser():
     a("--dino_dir", type=str, default=None,
       help="[additive] with --compute_metrics: a local transformers ViTModel directory (facebook/dino-vitb8 is the reference's): fills the DINO "
            "structure distance of a square pair.  Default: FIE_DINO_DIR, else <FIE_WEIGHTS_DIR>/dino when it exists")
+    a("--lpips_dir", type=str, default=None,
+      help="[additive] with --compute_metrics: a local directory with the LPIPS SqueezeNet weights (model.safetensors, or torchvision's "
+           "squeezenet1_1*.pth beside the lpips package's squeeze.pth): fills LPIPS.  Default: FIE_LPIPS_DIR, else <FIE_WEIGHTS_DIR>/lpips when it exists")
     return p
 
 
@@ -228,7 +232,7 @@ def main(argv=None):
     if args.compute_metrics:
         print("\n[4/4] Computing metrics...")
         from src.metrics import MetricsCalculator
-        calc = MetricsCalculator(device="cuda", clip_dir=args.clip_score_dir, dino_dir=args.dino_dir)
+        calc = MetricsCalculator(device="cuda", clip_dir=args.clip_score_dir, dino_dir=args.dino_dir, lpips_dir=args.lpips_dir)
         metrics = calc.calculate_all_metrics(source_img=source_img, edited_img=edited_img, prompt=args.prompt)
         labels = [("ssim", "SSIM (structure preservation):  ", ".4f", ""), ("lpips", "LPIPS (perceptual distance):    ", ".4f", ""),
                   ("psnr", "PSNR (signal quality):          ", ".2f", " dB"), ("mse", "MSE (pixel difference):         ", ".6f", ""),

@@ -3,7 +3,8 @@
 Evaluation only (not part of the denoising hot path): plain torch ops, as the reference's
 torchmetrics are.  Restated here: SSIM (torchmetrics defaults: 11x11 Gaussian, sigma 1.5, k1/k2 0.01/0.03,
 data_range 1), PSNR and MSE, all on 512x512 LANCZOS-resized RGB in [0,1] (reference :227-239, :291-347).
-LPIPS(squeeze) needs a checkpoint that only exists on the hub (reference :179-183); offline it returns None rather than a made-up number.
+LPIPS(squeeze) (reference :179-183, :241-269) runs on the device when a local weight directory is given (`lpips_dir=`, else FIE_LPIPS_DIR, else
+<FIE_WEIGHTS_DIR>/lpips): fie_amd/lpips.py; without one, and on the CPU, it returns None rather than a made-up number.
 The DINO ViT-B/8 structure distance (reference :24-147) runs on the device when a local transformers `ViTModel` directory is given
 (`dino_dir=`, else FIE_DINO_DIR, else <FIE_WEIGHTS_DIR>/dino): fie_amd/dino.py; without one, and on the CPU, it returns None.  CLIPScore(ViT-B/16) (reference :184-186, :271-289) runs on the device when a local
 `CLIPModel` directory is given (`clip_dir=`, else FIE_CLIP_SCORE_DIR, else <FIE_WEIGHTS_DIR>/clip_score): fie_amd/clip_score.py,
@@ -23,6 +24,7 @@ from PIL import Image
 import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory)
 from fie_amd import clip_score as hclip
 from fie_amd import dino as hdino
+from fie_amd import lpips as hlpips
 from fie_amd import mask as hmask
 from fie_amd import metrics as hmetrics
 
@@ -30,7 +32,7 @@ TARGET = hmetrics.TARGET
 
 
 class MetricsCalculator:
-    def __init__(self, device="cuda", clip_dir=None, dino_dir=None, dino_layer=hdino.DEFAULT_LAYER):
+    def __init__(self, device="cuda", clip_dir=None, dino_dir=None, dino_layer=hdino.DEFAULT_LAYER, lpips_dir=None):
         self.device = device
         print(f"[MetricsCalculator] Initializing on {device}...")
         d = torch.arange(-5.0, 6.0)
@@ -52,8 +54,14 @@ class MetricsCalculator:
         if dino_dir:
             print(f"[MetricsCalculator] Loading the DINO structure distance model from {dino_dir}")
             self._dino = hdino.load(dino_dir, self._ctx, layer=dino_layer)
-        print("[MetricsCalculator] Initialization complete! (LPIPS: unavailable offline" + ("" if self._clip else "; CLIP score: no model directory")
-              + ("" if self._dino else "; DINO distance: no model directory") + ")")
+        self._lpips = None                              # fie_amd.lpips.LpipsScorer: only on a GPU and only from a local weight directory
+        lpips_dir = hlpips.resolve_dir(lpips_dir) if self._ctx is not None else None
+        if lpips_dir:
+            print(f"[MetricsCalculator] Loading the LPIPS model from {lpips_dir}")
+            self._lpips = hlpips.load(lpips_dir, self._ctx)
+        missing = [what for what, have in (("LPIPS: no weight directory", self._lpips), ("CLIP score: no model directory", self._clip),
+                                           ("DINO distance: no model directory", self._dino)) if not have]
+        print("[MetricsCalculator] Initialization complete!" + (f" ({'; '.join(missing)})" if missing else ""))
 
     def _pil_to_tensor(self, img):
         a = np.array(img).astype(np.float32) / 255.0
@@ -142,7 +150,35 @@ class MetricsCalculator:
         return float("inf") if m == 0 else float(10.0 * np.log10(1.0 / m))
 
     def calculate_lpips(self, img1, img2):
-        return None
+        """The reference's LPIPS (SqueezeNet, both images LANCZOS-resized to 512 x 512), or None without a weight directory / on the CPU."""
+        if self._lpips is None or img1 is None or img2 is None:
+            return None
+        return self.calculate_lpipses([img1], [img2])[0]["lpips"]
+
+    def calculate_lpipses(self, sources, editeds, masks=None):
+        """[additive] {"lpips": float} per (source, edited) pair of two lists of PIL images; `masks` (None, or per pair None / a mask as
+        calculate_pairs takes it) adds "bg_lpips" where a mask is given: the same number with both images' bytes set to 0 inside the binarised
+        512 x 512 mask, as bg_ssim treats them.  One upload per image, all images through the tower in batched passes, one synchronisation.
+        Without a weight directory every entry is None."""
+        if len(sources) != len(editeds) or (masks is not None and len(masks) != len(sources)):
+            raise ValueError("sources, editeds and masks must be lists of one length")
+        if self._lpips is None:
+            return [None] * len(sources)
+        if not sources:
+            return []
+        ctx = self._ctx
+        bins = None if masks is None else [None if m is None else hmetrics.binary_mask(m) for m in masks]
+        with torch.cuda.device(ctx.device):
+            a = [self._upload(im) for im in sources]
+            b = [self._upload(im) for im in editeds]
+            mk = None if bins is None else [None if m is None else torch.from_numpy(m).to(ctx.device) for m in bins]
+            rows = self._lpips.scores(a, b, mk).cpu().numpy()
+        out = []
+        for i, row in enumerate(rows):
+            out.append({"lpips": hlpips.total(row[:7])})
+            if bins is not None and bins[i] is not None:
+                out[-1]["bg_lpips"] = hlpips.total(row[7:])
+        return out
 
     def calculate_clip_score(self, img, text):
         """max(100 cos(image embedding, text embedding), 0) of the reference's CLIPScore, or None without a model directory / on the CPU."""
@@ -241,13 +277,19 @@ class MetricsCalculator:
     def with_unavailable(self, m, source_img=None, edited_img=None, prompt="", mask=None):
         """A calculate_pairs() dict in calculate_all_metrics()'s key order, with the metrics that need hub checkpoints as None.  `clip_score`
         is filled when the calculator has a CLIP model (and `clip_score_edited`, behind the bg_* keys, when a mask comes with it),
-        `dino_distance` when it has a DINO model and both images are square."""
+        `dino_distance` when it has a DINO model and both images are square, `lpips` when it has the LPIPS weights (and `bg_lpips`, directly
+        behind `bg_mse`, when a mask comes with it)."""
         clip = {"clip_score": None}
         if self._clip is not None and edited_img is not None:
             clip = self.calculate_clip_scores([edited_img], [prompt], None if mask is None else [mask])[0]
-        out = {"ssim": m["ssim"], "lpips": self.calculate_lpips(source_img, edited_img), "clip_score": clip["clip_score"],
+        lp = {"lpips": None}
+        if self._lpips is not None and source_img is not None and edited_img is not None:
+            lp = self.calculate_lpipses([source_img], [edited_img], None if mask is None else [mask])[0]
+        out = {"ssim": m["ssim"], "lpips": lp["lpips"], "clip_score": clip["clip_score"],
                "psnr": m["psnr"], "mse": m["mse"], "dino_distance": self._dino_or_none(source_img, edited_img)}
         out.update({k: m[k] for k in hmetrics.BG_KEYS if k in m})
+        if "bg_lpips" in lp:
+            out["bg_lpips"] = lp["bg_lpips"]
         if "clip_score_edited" in clip:
             out["clip_score_edited"] = clip["clip_score_edited"]
         return out

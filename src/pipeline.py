@@ -6,7 +6,9 @@ signatures, defaults, attributes and error behaviour; `self.pipe` is an `fie_amd
 HIP library or GPU raises.  Additive: `set_in_flight(n)` / `worker_slot(i)` (several edits in flight from worker threads), and keyword-only knobs: `weights_dir`, `seed_weights`, `noise_dtype`, `weight_dtype` ("f8e4m3": fp8 UNet / ControlNet weights, BASELINE config 5), `broadcast_weights`
 (under torch.distributed with world_size > 1, rank 0's synthetic weights are broadcast over RCCL instead of regenerated), `clip_score_dir` (a local
 transformers CLIPModel directory: `edit(..., metrics=True)` then also returns the CLIP score of the edit), `dino_dir` (a local
-transformers ViTModel directory: `edit(..., metrics=True)` then also returns the DINO structure distance of the edit).
+transformers ViTModel directory: `edit(..., metrics=True)` then also returns the DINO structure distance of the edit),
+`lpips_dir` (a local directory with the LPIPS SqueezeNet weights: `edit(..., metrics=True)` then also returns the LPIPS of the edit, DESIGN.md
+section 19).
 """
 import os
 import threading
@@ -46,7 +48,8 @@ class FastEditor:
 
     def __init__(self, model_name="sdxl", device="cuda", dtype=torch.float16, enable_cpu_offload=True,
                  use_full_precision=False, use_full_controlnet=False, *, weights_dir=None, seed_weights=1234,
-                 noise_dtype=None, broadcast_weights=True, weight_dtype="f16", clip_score_dir=None, dino_dir=None, dino_layer=11):
+                 noise_dtype=None, broadcast_weights=True, weight_dtype="f16", clip_score_dir=None, dino_dir=None, dino_layer=11,
+                 lpips_dir=None):
         if model_name not in self.MODEL_CONFIGS and model_name not in self._EXTRA_STACKS:
             raise ValueError(f"Unknown model: {model_name}. Choose from {list(self.MODEL_CONFIGS.keys())}")
         self.model_name = model_name
@@ -118,6 +121,12 @@ class FastEditor:
             from fie_amd import dino as hdino
             log(f"Loading the DINO structure distance model from {dino_dir}")
             self.dino_scorer = hdino.load(dino_dir, ctx, layer=dino_layer)
+        self.lpips_scorer = None               # fie_amd.lpips.LpipsScorer: only from a directory, never a made-up number
+        self._lpips_rows = {}                  # (slot, images, columns) -> pinned f64 [images, columns]: where an edit's LPIPS layer values land
+        if lpips_dir:
+            from fie_amd import lpips as hlpips
+            log(f"Loading the LPIPS model from {lpips_dir}")
+            self.lpips_scorer = hlpips.load(lpips_dir, ctx)
         del sds
         log("Enabling memory optimizations...")
         # 288 GB of HBM: offload / slicing flags are accepted and ignored (reference toggles them at :165-179)
@@ -183,6 +192,8 @@ class FastEditor:
         `FastEditor(clip_score_dir=...)` the dict also holds `clip_score` (the result against `prompt`) and, with a mask,
         `clip_score_edited` (the result zeroed outside the edited region).  With `FastEditor(dino_dir=...)` the dict also holds `dino_distance`: the
         structure distance between the ORIGINAL source and the result; None when the source or the result is not square.
+        With `FastEditor(lpips_dir=...)` the dict also holds `lpips` (SqueezeNet LPIPS of source and result at 512x512)
+        and, with a mask, `bg_lpips` (both images zeroed inside the edited region, as bg_ssim).
         [additive] `output_size`: None / "edit" returns the result at the edit size (above); "source" returns it at the source image's own
         (width, height): the u8 result LANCZOS-resized on the device, bit-exact with `result.resize(image.size, Image.LANCZOS)`, and -- with a mask
         and `paste_back` -- composited THERE against the source as uploaded: the caller's own bytes where the feathered mask is 0, the resized
@@ -332,7 +343,9 @@ class FastEditor:
         (`clip_scorer`) the hook also queues the CLIP score of every result against its prompt (cached text embedding, one batched pass of the
         image tower, the masked variants in the same pass) and returns (metric rows, CLIP rows, which (image, masked) each CLIP row is).  With a DINO
         model (`dino_scorer`) it queues, behind those, the structure distance of every (original source, result) pair of square images -- one batched
-        pass of the tower per (source size, result size) -- and the tuple grows by (distance rows, which image each row is)."""
+        pass of the tower per (source size, result size) -- and the tuple grows by (distance rows, which image each row is).  With the LPIPS
+        weights (`lpips_scorer`) it queues the LPIPS layer values of every pair on the 512x512 tensors and the binary masks it has already built
+        (the background variant where an image has a mask), and the tuple's sixth entry is their rows."""
         ctx = self.pipe.ctx
         th, tw = hmetrics.TARGET[1], hmetrics.TARGET[0]
         to512 = lambda t: t if tuple(t.shape[:2]) == (th, tw) else ctx.resize_lanczos(t.contiguous(), th, tw)
@@ -352,6 +365,11 @@ class FastEditor:
             if host is None:
                 host = self._metric_rows[(slot, len(outs))] = torch.empty((len(outs), 4), dtype=torch.int64).pin_memory()
             host.copy_(rows, non_blocking=True)
+            if self.lpips_scorer is not None:
+                return self._with_lpips(score_more(outs, host), self._lpips_queue(slot, a, b, mk, [m is not None for m in omasks]))
+            return score_more(outs, host)
+
+        def score_more(outs, host):
             if self.clip_scorer is None and self.dino_scorer is None:
                 return host
             if self.clip_scorer is None:
@@ -370,6 +388,24 @@ class FastEditor:
                 return (host, chost, items) + self._dino_queue(slot, origs, outs)
             return host, chost, items
         return score
+
+    @staticmethod
+    def _with_lpips(extra, lpips_rows):
+        """The scorer's result with the LPIPS rows as its sixth entry."""
+        return ((tuple(extra) if isinstance(extra, tuple) else (extra, None, ())) + (None, ()))[:5] + (lpips_rows,)
+
+    def _lpips_queue(self, slot, a, b, mk, has_mask):
+        """Queues the LPIPS layer values of the pairs (a[i], b[i]) -- u8 [n, 512, 512, 3] -- and, where has_mask[i], of their background variants
+        under the 0 / 1 masks mk u8 [n, 512, 512], on the current stream, and the copy of the rows into pinned host memory of the slot.
+        -> f64 [n, 7] (no mask at all) or [n, 14] on the host."""
+        n = a.shape[0]
+        with self.pipe.eager_lock:
+            rows = self.lpips_scorer.scores(list(a), list(b), None if mk is None else [mk[i] if has_mask[i] else None for i in range(n)])
+        lhost = self._lpips_rows.get((slot, n, rows.shape[1]))
+        if lhost is None:
+            lhost = self._lpips_rows[(slot, n, rows.shape[1])] = torch.empty(tuple(rows.shape), dtype=torch.float64).pin_memory()
+        lhost.copy_(rows, non_blocking=True)
+        return lhost
 
     def _dino_queue(self, slot, origs, outs):
         """Queues the structure distances of the square (original, result) pairs on the current stream and the copy of their 8 bytes each into pinned
@@ -396,6 +432,7 @@ class FastEditor:
         return dhost, tuple(order)
 
     def _scores(self, extra, has_mask):
+        lpips_rows = extra[5] if isinstance(extra, tuple) and len(extra) > 5 else None
         host_rows, clip_rows, items, dino_rows, dino_items = (tuple(extra) + (None, ()))[:5] if isinstance(extra, tuple) else (extra, None, (), None, ())
         out = hmetrics.rows_to_dicts(host_rows.numpy().copy(), hmetrics.TARGET[1], hmetrics.TARGET[0], has_mask)
         for (i, masked), row in zip(items, clip_rows.numpy().copy() if clip_rows is not None else ()):
@@ -405,6 +442,12 @@ class FastEditor:
                 m["dino_distance"] = None
             for i, v in zip(dino_items, dino_rows.numpy().copy() if dino_rows is not None else ()):
                 out[i]["dino_distance"] = float(v)
+        if lpips_rows is not None:
+            from fie_amd import lpips as hlpips
+            for m, row, masked in zip(out, lpips_rows.numpy().copy(), has_mask):
+                m["lpips"] = hlpips.total(row[:7])
+                if masked:
+                    m["bg_lpips"] = hlpips.total(row[7:14])
         return out
 
     def _grow_host(self, mask_l, grow):
