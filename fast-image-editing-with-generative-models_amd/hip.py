@@ -1106,6 +1106,44 @@ class Context:
         _chk(lib().fie_metrics_pairs_u8(self.h, _p(a), _p(b), _p(mask), n, h, w, _p(out), _p(ws), nbytes))
         return out
 
+    def sweep_select(self, imgs, rows, clip=None, rule="strongest", floor=float("-inf"), bg=False, out=None, out_idx=None):
+        """The selector of a strength sweep (fie_sweep_select_u8).  imgs: 1 .. 16 u8 device tensors of one shape, each with
+        contiguous memory at any address, strongest variant first; rows: the int64 [k, 4] device rows of metrics_pairs(); clip: None, or the f32
+        [>= k, 2] device rows of clip_score() (rule "clip_score" needs them); floor: float64 in raw ssim_sum units (fie_amd/sweep.py: ssim_floor);
+        bg: compare bg_ssim_sum.  -> (u8 tensor of the images' shape holding the winner, int32 [1] device tensor holding its index), exactly
+        fie_amd/sweep.py: select_numpy.  `out` / `out_idx`: tensors to write into (out: the images' shape, contiguous memory at any address, not
+        an image's).  One launch, no synchronisation."""
+        from . import sweep as hsweep
+        self.sync_stream()
+        imgs = list(imgs)
+        if not 1 <= len(imgs) <= hsweep.MAX_VARIANTS:
+            raise ValueError(f"sweep_select: {len(imgs)} images: 1 .. {hsweep.MAX_VARIANTS}")
+        if rule not in hsweep.RULES:
+            raise ValueError(f"sweep_select: rule={rule!r}: one of {sorted(hsweep.RULES)}")
+        k, shape = len(imgs), tuple(imgs[0].shape)
+        for t in imgs:
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != shape or not t.is_contiguous() or t.numel() == 0:
+                raise ValueError(f"sweep_select: contiguous u8 images of one shape, got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t).__name__)}")
+        if not torch.is_tensor(rows) or rows.dtype != torch.int64 or tuple(rows.shape) != (k, 4) or not rows.is_contiguous():
+            raise ValueError(f"sweep_select: rows must be a contiguous int64 {(k, 4)} tensor")
+        if rule == "clip_score" and clip is None:
+            raise ValueError("sweep_select: rule 'clip_score' needs the CLIP rows")
+        if clip is not None and (not torch.is_tensor(clip) or clip.dtype != torch.float32 or clip.dim() != 2 or clip.shape[0] < k or clip.shape[1] != 2
+                                 or not clip.is_contiguous()):
+            raise ValueError(f"sweep_select: clip must be a contiguous f32 [>= {k}, 2] tensor")
+        if out is None:
+            out = self._alloc(shape, torch.uint8)
+        elif not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"sweep_select: out must be a contiguous u8 {shape} tensor")
+        if out_idx is None:
+            out_idx = torch.empty(1, device=self.device, dtype=torch.int32)
+        elif not torch.is_tensor(out_idx) or out_idx.dtype != torch.int32 or out_idx.numel() != 1:
+            raise ValueError("sweep_select: out_idx must be an int32 tensor of one element")
+        ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in imgs])
+        _chk(lib().fie_sweep_select_u8(self.h, ptrs, k, imgs[0].numel(), _p(rows), _p(clip), hsweep.RULES[rule], float(floor), int(bool(bg)),
+                                       _p(out), _p(out_idx)))
+        return out, out_idx
+
     # ------------------------------------------------------------------ CLIP score (csrc/clip_score.hip, DESIGN.md section 11)
     def clip_mask(self, rgb_u8, mask_l, out=None):
         """u8 [n, H, W, 3] (or [H, W, 3]) images with every pixel outside the edited region set to 0.  mask_l: u8 [n, MH, MW] (or [MH, MW]), L >= 128 =

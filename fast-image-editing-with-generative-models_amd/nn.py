@@ -189,7 +189,8 @@ class TBlock:
     def _text_kv(self, ctx, text):
         """Cross-attention K | V of the text, [B * 77, 2 c]: invariant over the denoising steps of one image, so computed once per image -- and for ALL blocks
         of the net in ONE GEMM (M = B * 77 rows against the concatenated to_k / to_v matrices: one pass over the weights at HBM rate instead of 20-36 launches
-        of 16 us at 0.04 of the MFMA peak); a block takes its column range of the result."""
+        of 16 us at 0.04 of the MFMA peak); a block takes its column range of the result.  `text` holds the rows of ALL images of the job and so does the
+        cache: a step that runs a leading slice of them (a strength sweep's ragged steps, pipe.py) reads the leading batch * text_len rows."""
         if self.kv_cache is None:
             net = self.kv_net
             if net is not None and ctx.kv_group and not ctx.calib:
@@ -211,7 +212,7 @@ class TBlock:
         h = self.o1(ctx, a, residual=h, a_scale=s[1])
         y = ctx.layernorm(h, self.ln[1].g, self.ln[1].b, out_f8=True, out_inv_scale=1.0 / s[2])
         q = self.q2(ctx, y, a_scale=s[2])
-        kv = self._text_kv(ctx, text)
+        kv = self._text_kv(ctx, text)[:batch * text_len]
         a = ctx.attention(q, kv[:, :c], kv[:, c:], self.heads, self.hd, tokens, text_len, batch, out_f8=True, out_inv_scale=1.0 / s[3])
         h = self.o2(ctx, a, residual=h, a_scale=s[3])
         y = ctx.layernorm(h, self.ln[2].g, self.ln[2].b, out_f8=True, out_inv_scale=1.0 / s[4])
@@ -231,7 +232,7 @@ class TBlock:
             a = ctx.attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], self.heads, self.hd, tokens, tokens, batch)
             h = self.o1(ctx, a, residual=h)
             q = ctx.gemm_ln(h, w2, c, t2) if "q2" in which else self.q2(ctx, ctx.layernorm(h, self.ln[1].g, self.ln[1].b))
-            kv = self._text_kv(ctx, text)
+            kv = self._text_kv(ctx, text)[:batch * text_len]
             a = ctx.attention(q, kv[:, :c], kv[:, c:], self.heads, self.hd, tokens, text_len, batch)
             h = self.o2(ctx, a, residual=h)
             f = ctx.gemm_ln(h, wf, 8 * c, tf, act=hip.ACT_GEGLU) if ctx.ln_fold_ff1 else self.ff1(ctx, ctx.layernorm(h, self.ln[2].g, self.ln[2].b))
@@ -245,7 +246,7 @@ class TBlock:
         y = ctx.layernorm(h, self.ln[1].g, self.ln[1].b)
         rec(y, 2)
         q = self.q2(ctx, y)
-        kv = self._text_kv(ctx, text)
+        kv = self._text_kv(ctx, text)[:batch * text_len]
         a = ctx.attention(q, kv[:, :c], kv[:, c:], self.heads, self.hd, tokens, text_len, batch)
         rec(a, 3)
         h = self.o2(ctx, a, residual=h)
@@ -370,21 +371,23 @@ class _CondNet:
         self._kv_out = None
 
     def time_rowbias(self, t_dev):
-        """silu(time_emb + add_emb) -> all resnets' time projections in one GEMM.  t_dev: f32 [B, 1] on device."""
+        """silu(time_emb + add_emb) -> all resnets' time projections in one GEMM.  t_dev: f32 [B, 1] on device; B may be a leading slice of the
+        rows begin_image() saw (a strength sweep's ragged steps)."""
         ctx = self.ctx
         ch0 = self.cfg["block_out_channels"][0]
+        add_emb = self.add_emb[:t_dev.shape[0]]
         if self.te is not None and t_dev.shape[0] <= 4:
             ctx.sync_stream()
             key = (ctx._stream, ctx.ws_tag)       # launches that may run concurrently (other stream, other graph slot) never share the barrier counters
             ws = self.te_ws.get(key)
             if ws is None:
                 ws = self.te_ws[key] = ctx.time_embed_workspace(self.te[0].shape[0])
-            return self.temb_proj(ctx, ctx.time_embed(t_dev, *self.te, ws, add=self.add_emb))
+            return self.temb_proj(ctx, ctx.time_embed(t_dev, *self.te, ws, add=add_emb))
         s = ctx._alloc((t_dev.shape[0], ch0))
         ctx.sinusoid(t_dev, ch0, s)
         # emb = time_emb + add_emb; resnets consume Linear(SiLU(emb)): add_emb rides in as a per-row bias so the
         # second MLP GEMM's epilogue emits SiLU(emb) directly
-        semb = self.t2(ctx, self.t1(ctx, s, act=hip.ACT_SILU), rowbias=self.add_emb, rows_per_batch=1, act=hip.ACT_SILU)
+        semb = self.t2(ctx, self.t1(ctx, s, act=hip.ACT_SILU), rowbias=add_emb, rows_per_batch=1, act=hip.ACT_SILU)
         return self.temb_proj(ctx, semb)
 
     def encode(self, x, temb_all, text, text_len):

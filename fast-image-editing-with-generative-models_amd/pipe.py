@@ -311,6 +311,31 @@ class HipImg2ImgPipeline:
                 job[k] = torch.cat([j[k] for j in jobs], dim=0)
         return job
 
+    def prepare_sweep(self, prompt, negative_prompt="", image=None, control_image=None, strengths="all", num_inference_steps=4,
+                      guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None, mask_image=None, mask_blur=0, paste_back=True, *,
+                      masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0):
+        """[additive] A strength sweep as ONE device job: one image, one prompt pair, and the k variants of
+        fie_amd/sweep.py: variants(num_inference_steps, strengths) as the k "images" of the job, strongest first.  Everything that does not depend
+        on the strength runs once (tokenisation, both text encoders, the mask preparation, the fill, the VAE encode, the edge-map embedding); the
+        UNet and the ControlNet run each loop step on the rows of the variants that have joined the loop by then -- a leading slice, rows being
+        image-major as in prepare_batch().  One generator: variant i consumes the noise a single call with that generator and strength draws (its
+        stream is a prefix of the longest variant's).  The other arguments are prepare()'s.  A sweep of ONE variant is the single-image job."""
+        from . import sweep as hsweep
+        vs = hsweep.variants(num_inference_steps, strengths)
+        job = self._prepare(prompt, negative_prompt, image, control_image, vs[0][1][0], num_inference_steps, guidance_scale,
+                            controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content,
+                            hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later),
+                            hmask.check_grow(mask_grow, mask_image is not None))
+        if len(vs) == 1:
+            return job                                    # the single-image job (and its graph)
+        plans = [self.scheduler.plan(num_inference_steps, v[1][0]) for v in vs]
+        assert [len(p) for p in plans] == [m for m, _ in vs] and plans[0] == job["steps"] and len(job["noises"]) == hsweep.noise_count(plans)
+        job["sweep"] = tuple(m for m, _ in vs)
+        job["plans"] = plans
+        job["sched"] = hsweep.schedule(plans)
+        job["t_dev"] = [t.repeat(len(row), 1) for t, row in zip(job["t_dev"], job["sched"])]       # one timestep for the rows active at that step
+        return job
+
     def _side_stream(self):
         """Second stream for the independent branches of one edit (CLIP beside the VAE encode, UNet encoder beside the
         ControlNet trunk).  `fork_streams = False` keeps the whole edit on one stream.  Overlap between the branches
@@ -332,6 +357,8 @@ class HipImg2ImgPipeline:
     @torch.no_grad()
     def run_device(self, job):
         """Device side: everything between the H2D and D2H copies.  Returns the u8 HWC image on the device."""
+        if job.get("sweep"):                              # a strength sweep's ragged job (prepare_sweep)
+            return self._run_sweep(job)
         ctx, dev = self.ctx, self.ctx.device
         h, w = job["hw"]
         nb, steps = job["nb"], job["steps"]
@@ -445,6 +472,108 @@ class HipImg2ImgPipeline:
             job["_result"]["z0"] = z0                     # a masked edit's clean source latents (its blend target)
         return out_u8
 
+    @torch.no_grad()
+    def _run_sweep(self, job):
+        """run_device() of a strength sweep (prepare_sweep): k variants of ONE image, variant i joining the loop at step M - m_i.  Same stages, marks
+        and streams as run_device().  Once per sweep: the text encoders, begin_image, the fill, the edge-map embedding, the VAE encode.  Per variant:
+        latent_prep on the one moments tensor with its own first-step scalars, lcm_step with its own step record, the decode and the paste-back.  Per
+        loop step the two networks run on the leading act * nb rows.  The per-job state -- add_emb, the text and with it the text K/V caches of
+        the transformer blocks, the edge-map embedding -- covers all k * nb rows from the start (the FIRST step runs the fewest rows and fills the
+        caches), and a step reads their leading rows.  Returns u8 [k, h, w, 3], strongest variant first."""
+        ctx, dev = self.ctx, self.ctx.device
+        h, w = job["hw"]
+        nb, plans, sched = job["nb"], job["plans"], job["sched"]
+        k = len(plans)
+        lh, lw = h // 8, w // 8
+        hw = lh * lw
+        self._mark("start")
+        main = torch.cuda.current_stream(dev)
+        side = self._side_stream()
+        img, ctl = job["img_u8"], job["ctl_u8"]
+        src = img                                         # what the VAE encodes; `img` keeps feeding the composites
+        content = job.get("content")
+        if content is not None:
+            filled, ctl = ctx.mask_fill(img, job["mask_l"][0], ctl, fill=content == "fill")
+            if content == "fill":
+                src = filled
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            if self.cpp_walks:
+                pl, _ = cabi.clip_forward(self.clip_l, self.weight_prefix + "text_encoder.", job["ids_l"])
+                pg, pooled = cabi.clip_forward(self.clip_g, self.weight_prefix + "text_encoder_2.", job["ids_g"], job["eos_rows"])
+            else:
+                pl, _ = self.clip_l(job["ids_l"])
+                pg, pooled = self.clip_g(job["ids_g"], eos_rows=job["eos_rows"])
+            # one prompt pair: its nb rows stand for every variant (torch copies, as the CFG repeat of the edge-map embedding is)
+            text = torch.cat([pl, pg], dim=1).repeat(k, 1)
+            for net in (self.unet, self.controlnet):
+                net.begin_image(pooled, job["time_ids"])
+                net.add_emb = net.add_emb.repeat(k, 1)
+            cond_emb = self.controlnet.cond_embedding(ctx.pixels_in(ctl, False)).repeat_interleave(k * nb, dim=0)
+            tb0 = (self.unet.time_rowbias(job["t_dev"][0]), self.controlnet.time_rowbias(job["t_dev"][0]))
+        text_len = text.shape[0] // (k * nb)
+        mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")
+        latents = torch.empty((k, hw, 4), device=dev, dtype=torch.float32)
+        z0 = torch.empty((hw, 4), device=dev, dtype=torch.float32) if mask_lat is not None else None
+        model_in = torch.empty((k * nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
+        sf = self.cfgs["vae"]["scaling_factor"]
+        noises = job["noises"]
+        x_img = ctx.pixels_in(src, True)
+        moments = cabi.vae_encode(self.vae, x_img) if self.cpp_walks else self.vae.encode_moments(x_img)[0]
+        for i, p in enumerate(plans):                     # z0 does not depend on the variant: every variant writes the same values
+            rows = model_in[i * nb:(i + 1) * nb]
+            if mask_lat is None:
+                ctx.latent_prep(moments, noises[0], noises[1], hw, sf, p[0]["sqrt_ab"], p[0]["sqrt_1mab"], latents[i], rows)
+            elif job.get("content_lat") is None:
+                ctx.latent_prep_src(moments, noises[0], noises[1], hw, sf, p[0]["sqrt_ab"], p[0]["sqrt_1mab"], latents[i], rows, z0)
+            else:
+                ctx.latent_prep_src_content(moments, noises[0], noises[1], hw, sf, p[0]["sqrt_ab"], p[0]["sqrt_1mab"], latents[i], rows, z0,
+                                            job["content_lat"][0], content)
+        main.wait_stream(side)
+        self._mark("clip+vae_encode")
+        decode_in = torch.empty((k, lh, lw, 8), device=dev, dtype=ctx.dtype)
+        self._mark("cond_embed")
+        for step, (active, t_dev) in enumerate(zip(sched, job["t_dev"])):
+            r = len(active) * nb                          # the rows of this step: the variants that have joined the loop
+            tb_u, tb_c = tb0 if step == 0 else (self.unet.time_rowbias(t_dev), self.controlnet.time_rowbias(t_dev))
+            self._mark("embed")
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                c_skips, c_mid = self.controlnet.encode_cond(model_in[:r], cond_emb[:r], tb_c, text, text_len)
+            skips, mid = self.unet.encode(self.unet.conv_in(ctx, model_in[:r]), tb_u, text, text_len)
+            main.wait_stream(side)
+            self._mark("unet_enc+controlnet")
+            skips, mid = self.controlnet.add_residuals(c_skips, c_mid, job["cn_scale"], skips, mid)
+            eps = self.unet.decode(mid, skips, tb_u, text, text_len)
+            self._mark("unet_dec")
+            for i, st, zi in active:
+                z = None if zi is None else noises[zi]
+                if mask_lat is None:
+                    ctx.lcm_step(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
+                                 st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
+                                 1.0 / sf, decode_in[i:i + 1])
+                else:
+                    ctx.lcm_step_masked(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
+                                        st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
+                                        1.0 / sf, decode_in[i:i + 1], mask_lat[0], z0, noises[1])
+            self._mark("lcm_step")
+        dec = (lambda z: cabi.vae_decode(self.vae, z)) if self.cpp_walks else self.vae.decode
+        if job.get("blend"):
+            outs = [ctx.multiband_blend(ctx.pixels_out(dec(decode_in[i:i + 1])), img, job["blend_l"][0],
+                                        None if mask_px is None else mask_px[0], job["blend"][1]) for i in range(k)]
+        elif mask_px is None:
+            outs = [ctx.pixels_out(dec(decode_in[i:i + 1])) for i in range(k)]
+        else:
+            outs = [ctx.pixels_out_composite(dec(decode_in[i:i + 1]), img, mask_px[0]) for i in range(k)]
+        out_u8 = torch.stack(outs)
+        self._mark("vae_decode")
+        self.last_stats = dict(unet_evals=len(sched), cfg_batch=nb, latent_hw=(lh, lw), images=k, sweep=job["sweep"])
+        self._latents = latents
+        job["_result"] = dict(stats=dict(self.last_stats), latents=latents)
+        if z0 is not None:
+            job["_result"]["z0"] = z0
+        return out_u8
+
     def _run_eager(self, job):
         """run_device() with the tuner meeting new shapes (as the eager warm-up of a capture does): an eager call and a graph replay of
         the same job then use the same kernels.  That matters since round 3: a split-K choice changes the fp32 summation order, so
@@ -532,6 +661,8 @@ class HipImg2ImgPipeline:
         if job.get("mask_lat") is not None:              # masked: (masked, mask_blur, paste_back); an unmasked key is what it was
             # + the masked-content mode, unless "original"; + ("multiband", levels), unless the blend is "alpha"
             base = base + ((True,) + job["mask_cfg"] + ((job["content"],) if job.get("content") else ()) + ((job["blend"],) if job.get("blend") else ()),)
+        if job.get("sweep"):                             # a strength sweep: + the step counts of its variants
+            base = base + (("sweep", job["sweep"]),)
         # A forked graph owns extra runtime streams; past ~8 such graphs in one process new ones start sharing hardware queues
         # with their own launch stream and replay 50 % slower (measured: 82 -> 125 ms, tools/edit_ab.py).  Beyond the budget a
         # new key is captured on one stream instead (87 ms): slower than a healthy forked graph, never pathological.
@@ -674,7 +805,9 @@ class HipImg2ImgPipeline:
         shrunk by an exact disk before anything reads it (prepare()).  `after_device` (additive): a callable given the u8 result
         while it is still on the device, on the slot's stream behind the device job and outside its graph; it may queue more work there (FastEditor
         scores the edit) and whatever it returns comes back as `.extra`, complete once the image has reached the host.  A hook that returns a
-        `DeviceOutput` replaces the image: its tensor(s) take the final device-to-host copy (FastEditor's full-resolution back end)."""
+        `DeviceOutput` replaces the image: its tensor(s) take the final device-to-host copy (FastEditor's full-resolution back end).
+        `strength` (additive): a list of strengths or "all" makes the call a strength sweep (prepare_sweep): `.images` holds one image per distinct
+        step count, strongest first, and the hooks see u8 [k, h, w, 3] as they do for a batch."""
         if slot and not self.use_graph:
             raise ValueError("slots > 0 need hipGraph replay (the eager path shares per-image state)")
         caller, st = torch.cuda.current_stream(self.ctx.device), self.slot_stream(slot)
@@ -727,6 +860,18 @@ class HipImg2ImgPipeline:
                 return self._to_host(extra.out, slot, varying=True), extra.extra
             return self._to_host(out_u8, slot), extra       # device -> host sync, as `.images[0]` implies upstream
 
+        if isinstance(strength, (list, tuple, str)):     # [additive] a strength sweep: one image, one variant per distinct step count (prepare_sweep)
+            if isinstance(prompt, (list, tuple)):
+                raise ValueError("a strength sweep runs on one image: `strength` is a list and `prompt` is one too")
+            job = self.prepare_sweep(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
+                                     controlnet_conditioning_scale, generator, *mask_args, masked_content=masked_content, **blend_kw)
+            arr, extra = run(job)
+            if post_check is not None and post_check():
+                self.repeated_jobs += 1
+                arr, extra = run(job)
+            if not isinstance(arr, list):
+                arr = [arr] if arr.ndim == 3 else list(arr)
+            return types.SimpleNamespace(images=arr if output_type == "np" else [Image.fromarray(a) for a in arr], extra=extra)
         if isinstance(prompt, (list, tuple)):            # [additive] a batch: lists of prompts / images / generators
             job = self.prepare_batch(list(prompt), negative_prompt if isinstance(negative_prompt, (list, tuple)) else None,
                                      list(image), list(control_image), strength, num_inference_steps, guidance_scale,

@@ -750,6 +750,24 @@ int fie_maxpool3s2_nhwc_f32(fie_ctx* ctx, const float* x, int n, int H, int W, i
 int64_t fie_lpips_layer_workspace_bytes(int P, int HW);
 int fie_lpips_layer_f32(fie_ctx* ctx, const float* fa, const float* fb, int P, int HW, int C, const float* w, void* workspace, double* out, int64_t ld_out);
 
+/* ---- Strength sweeps: the winner among k finished variants of one edit, picked and copied on the device.
+ *   imgs: a HOST array of k device pointers (they travel as kernel arguments: no pointer table in memory), 1 <= k <= 16, each to `bytes` bytes of
+ *   u8 at ANY address, 1 <= bytes <= 2^31; variants come strongest first.  rows: the k result rows of fie_metrics_pairs_u8 on the device.
+ *   clip_or_null: f32 [k, 2] on the device, the rows of fie_clip_score_* (the score is column 1); needed by rule 1 only.
+ *   With sums[i] = the double in field 1 of row i (ssim_sum), or field 3 (bg_ssim_sum) when bg == 1, and ok[i] = sums[i] >= floor (`floor` is in
+ *   the same raw units: min SSIM * 3 (H - 10) (W - 10), or -inf; a NaN never passes):
+ *       nobody passes   the index of the largest non-NaN sums[i], ties to the larger index; k - 1 when all are NaN
+ *       rule 0          the smallest passing index ("strongest": the most editing the preservation budget allows)
+ *       rule 1          the passing index with the largest clip[i][1], ties to the larger index (the weaker edit); a NaN score never wins; when
+ *                       all are NaN the largest passing index
+ *   float64 and float32 compares only (fie_amd/sweep.py: select_numpy restates it).  out_img: `bytes` bytes at any address, overlapping no
+ *   image; receives imgs[winner].  out_idx: one int32 on the device; receives the winner.  Nothing else is written.  FIE_EINVAL ("bad argument")
+ *   for anything else, NULL pointers included.  One launch, asynchronous on the ctx stream: every block evaluates the rule for itself and copies
+ *   its share -- aligned 16-byte stores, 16-byte loads where the source is congruent to the output mod 16 and aligned dwords otherwise, the up to
+ *   15 bytes in front of and behind them by bytes.  No atomics, no workspace, no block waits for another. */
+int fie_sweep_select_u8(fie_ctx* ctx, const void* const* imgs, int k, int64_t bytes, const int64_t* rows, const float* clip_or_null, int rule,
+                        double floor, int bg, void* out_img, int32_t* out_idx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ shards the selected entries image-parallel over N GPUs (fie_amd.dist) and rank 0
     python run_batch.py --num_images 50 --editing_types 0 1 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run_batch.py --model ssd-1b
 
-Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir, --dino_dir, --lpips_dir.
+Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir, --dino_dir, --lpips_dir,
+--auto_strength, --min_ssim, --strengths.
 """
 import argparse
 import json
@@ -230,6 +231,63 @@ def add_lpips_args(p):
     return p
 
 
+def strengths_arg(text):
+    """argparse type of --strengths: 'all' or 'a,b,c' -> "all" or a list of floats (fie_amd/sweep.py: variants checks the values)."""
+    if text.strip() == "all":
+        return "all"
+    try:
+        vals = [float(v) for v in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--strengths {text!r}: 'all' or comma-separated numbers in [0, 1]") from None
+    if not vals or any(not 0.0 <= v <= 1.0 for v in vals):
+        raise argparse.ArgumentTypeError(f"--strengths {text!r}: 'all' or comma-separated numbers in [0, 1]")
+    return vals
+
+
+def add_sweep_args(p):
+    """[additive] strength sweeps.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--auto_strength", type=str, default=None, choices=["clip_score", "strongest"],
+                   help="[additive] choose each image's strength on the device: every distinct step count of --strengths is edited in ONE device job "
+                        "and scored there; 'strongest' keeps the strongest edit whose SSIM against the source (the background's with --use_mask) stays "
+                        "at or above --min_ssim, 'clip_score' the edit with the best CLIP score (needs --clip_score_dir; among those that pass "
+                        "--min_ssim when given).  Only the chosen image leaves the device; the chosen strength and step count go into --results_json.  "
+                        "Not with --batch_size > 1, --tiles, --region mask; --strength is ignored")
+    p.add_argument("--min_ssim", type=float, default=None, help="[additive] with --auto_strength: the SSIM every candidate must keep, -1..1")
+    p.add_argument("--strengths", type=strengths_arg, default="all", metavar="{all,a,b,c}",
+                   help="[additive] with --auto_strength: the strengths to try, 'all' (one per step count 1..--steps) or comma-separated numbers")
+    return p
+
+
+def sweep_kwargs(args):
+    """The --auto_strength / --min_ssim / --strengths flags (absent on a parser without add_sweep_args) -> edit_sweep()'s keyword arguments, or {}."""
+    select = getattr(args, "auto_strength", None)
+    min_ssim = getattr(args, "min_ssim", None)
+    if select is None:
+        if min_ssim is not None:
+            raise ValueError("--min_ssim needs --auto_strength")
+        return {}
+    if max(1, getattr(args, "batch_size", 1)) > 1:
+        raise ValueError("--auto_strength with --batch_size > 1: a sweep is one device job per image")
+    if getattr(args, "tiles", None) is not None:
+        raise ValueError("--auto_strength with --tiles: a sweep runs as one device job")
+    if getattr(args, "region", "none") == "mask":
+        raise ValueError("--auto_strength with --region mask: a sweep runs on the whole image")
+    if select == "strongest" and min_ssim is None:
+        raise ValueError("--auto_strength strongest needs --min_ssim")
+    if min_ssim is not None and not -1.0 <= min_ssim <= 1.0:
+        raise ValueError(f"--min_ssim {min_ssim}: a number in -1..1")
+    kw = dict(select=select, strengths=getattr(args, "strengths", "all"))
+    if min_ssim is not None:
+        kw["min_ssim"] = min_ssim
+    return kw
+
+
+def full_parser():
+    """The parser main() reads: build_parser() and every additive group."""
+    return add_sweep_args(add_tile_args(add_lpips_args(add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_outpaint_args(
+        add_grow_args(add_blend_args(add_mask_args(build_parser()))))))))))))
+
+
 METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse", "clip_score", "clip_score_edited", "dino_distance", "lpips", "bg_lpips")
 
 
@@ -337,6 +395,7 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
         if not masked:
             raise ValueError("--mask_grow needs --use_mask")
         extra = dict(extra, mask_grow=mask_grow)
+    sweep = sweep_kwargs(args)                     # --auto_strength: one edit_sweep() per image in place of edit()
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
     def flush():
@@ -346,7 +405,14 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
                   canny_low_threshold=args.canny_low, canny_high_threshold=args.canny_high, seed=args.seed, **extra)
         try:
             t0 = time.time()
-            if bs == 1:
+            if sweep:
+                mkw = dict(mask=pending[0][6]) if use_mask else {}
+                out, info = editor.edit_sweep(image=pending[0][4], prompt=pending[0][5], negative_prompt=args.negative_prompt,
+                                              **{k: v for k, v in kw.items() if k not in ("strength", "metrics")}, **mkw, **sweep)
+                score = dict(chosen_strength=info["strength"][0], chosen_steps=info["steps"],
+                             **({k: info[k] for k in METRIC_KEYS if k in info} if with_metrics else {}))
+                edited = ([out], [score])
+            elif bs == 1:
                 mkw = dict(mask=pending[0][6]) if use_mask else {}
                 edited = editor.edit(image=pending[0][4], prompt=pending[0][5], negative_prompt=args.negative_prompt, **kw, **mkw)
                 edited = ([edited[0]], [edited[1]]) if with_metrics else [edited]
@@ -355,7 +421,7 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
                 edited = editor.edit_batch(images=[p[4] for p in pending], prompts=[p[5] for p in pending],
                                            negative_prompts=[args.negative_prompt] * len(pending), **kw, **mkw)
             dt = (time.time() - t0) / len(pending)
-            edited, scores = edited if with_metrics else (edited, [{}] * len(pending))
+            edited, scores = edited if with_metrics or sweep else (edited, [{}] * len(pending))
             for (index, image_id, rel, output_path, source_img, prompt, _), out, score in zip(pending, edited, scores):
                 res["total_time"] += dt
                 out.save(output_path)
@@ -419,6 +485,11 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
         print(f"\nAverage time per image: {tot['total_time'] / tot['processed']:.2f}s")
         print(f"Total time: {tot['total_time']:.2f}s ({tot['total_time'] / 60:.1f} minutes)")
         print(f"Throughput: {tot['processed'] / wall:.2f} images/sec wall-clock on {world} GPU(s)")
+        if getattr(args, "auto_strength", None):
+            chosen = [r["chosen_steps"] for r in tot.get("rows", []) if r.get("chosen_steps") is not None]
+            print(f"\nChosen step counts (--auto_strength {args.auto_strength}, of {args.steps} steps):")
+            for m in sorted(set(chosen), reverse=True):
+                print(f"  {m} steps: {chosen.count(m)} images")
         if getattr(args, "metrics", False):
             import numpy as np
             print("\nMetrics of the edits (512x512, before JPEG encoding):")
@@ -442,11 +513,11 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 
 
 def main(argv=None):
-    parser = add_tile_args(add_lpips_args(add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_outpaint_args(add_grow_args(
-        add_blend_args(add_mask_args(build_parser())))))))))))
+    parser = full_parser()
     args = parser.parse_args(argv)
     try:
         tile_kwargs(args)
+        sweep_kwargs(args)
     except ValueError as e:
         parser.error(str(e))
     masked = args.use_mask or args.outpaint is not None                # --outpaint: the new border is a mask
@@ -487,6 +558,11 @@ def main(argv=None):
 
     say(f"\n[3/3] Initializing FastEditor ({model_suffix})...")
     clip_dir = dino_dir = lpips_dir = None
+    if args.auto_strength == "clip_score" and not args.metrics:     # the selector reads the CLIP rows: the model is needed without --metrics too
+        from fie_amd import clip_score as hclip
+        clip_dir = hclip.resolve_dir(args.clip_score_dir)
+        if clip_dir is None and args.weights_dir and os.path.isdir(os.path.join(args.weights_dir, "clip_score")):
+            clip_dir = os.path.join(args.weights_dir, "clip_score")
     if args.metrics:
         from fie_amd import lpips as hlpips
         lpips_dir = hlpips.resolve_dir(args.lpips_dir)
@@ -500,6 +576,8 @@ def main(argv=None):
         clip_dir = hclip.resolve_dir(args.clip_score_dir)
         if clip_dir is None and args.weights_dir and os.path.isdir(os.path.join(args.weights_dir, "clip_score")):
             clip_dir = os.path.join(args.weights_dir, "clip_score")
+    if args.auto_strength == "clip_score" and clip_dir is None:
+        parser.error("--auto_strength clip_score needs a CLIP model: --clip_score_dir (or FIE_CLIP_SCORE_DIR, or <weights_dir>/clip_score)")
     from src.pipeline import FastEditor
     import contextlib
     import io

@@ -119,6 +119,39 @@ def add_tile_args(p):
     return p
 
 
+def strengths_arg(text):
+    """argparse type of --strengths: 'all' or 'a,b,c' -> "all" or a list of floats (fie_amd/sweep.py: variants checks the values)."""
+    if text.strip() == "all":
+        return "all"
+    try:
+        vals = [float(v) for v in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--strengths {text!r}: 'all' or comma-separated numbers in [0, 1]") from None
+    if not vals or any(not 0.0 <= v <= 1.0 for v in vals):
+        raise argparse.ArgumentTypeError(f"--strengths {text!r}: 'all' or comma-separated numbers in [0, 1]")
+    return vals
+
+
+def add_sweep_args(p):
+    """[additive] strength sweeps, kept apart from build_parser() like add_tile_args."""
+    p.add_argument("--sweep", action="store_true",
+                   help="[additive] edit the image at several strengths in ONE device job (every distinct step count of --strengths), scored on "
+                        "the device.  Not with --tiles, --region mask; --strength is ignored")
+    p.add_argument("--strengths", type=strengths_arg, default="all", metavar="{all,a,b,c}",
+                   help="[additive] with --sweep: the strengths to try, 'all' (one per step count 1..--steps) or comma-separated numbers")
+    p.add_argument("--select", type=str, default="none", choices=["none", "clip_score", "strongest"],
+                   help="[additive] with --sweep: 'none' saves every variant as <name>_steps<m>.jpg; 'strongest' keeps the strongest edit whose SSIM "
+                        "against the source (the background's with --mask) stays at or above --min_ssim; 'clip_score' the edit with the best CLIP "
+                        "score (needs --clip_score_dir).  The choice is made on the device and only the chosen image leaves it")
+    p.add_argument("--min_ssim", type=float, default=None, help="[additive] with --sweep --select: the SSIM every candidate must keep, -1..1")
+    return p
+
+
+def full_parser():
+    """The parser main() reads: build_parser() and every additive group."""
+    return add_sweep_args(add_tile_args(build_parser()))
+
+
 def save_plot(path, source_img, edited_img, model, prompt):
     import matplotlib
     matplotlib.use("Agg")
@@ -137,8 +170,25 @@ def save_plot(path, source_img, edited_img, model, prompt):
 
 
 def main(argv=None):
-    parser = add_tile_args(build_parser())
+    parser = full_parser()
     args = parser.parse_args(argv)
+    if not args.sweep and (args.select != "none" or args.min_ssim is not None):
+        parser.error("--select and --min_ssim need --sweep")
+    if args.sweep:
+        if args.tiles is not None or args.region != "none":
+            parser.error("--sweep does not go with --tiles or --region mask: a sweep is one device job on the whole image")
+        if args.select == "strongest" and args.min_ssim is None:
+            parser.error("--select strongest needs --min_ssim")
+        if args.select == "none" and args.min_ssim is not None:
+            parser.error("--min_ssim needs --select")
+        if args.min_ssim is not None and not -1.0 <= args.min_ssim <= 1.0:
+            parser.error("--min_ssim: a number in -1..1")
+        if args.select == "clip_score":
+            import fie_amd  # noqa: F401
+            from fie_amd import clip_score as hclip
+            args.clip_score_dir = hclip.resolve_dir(args.clip_score_dir)
+            if args.clip_score_dir is None:
+                parser.error("--select clip_score needs --clip_score_dir")
     masked = args.mask is not None or args.outpaint is not None        # --outpaint: the new border is a mask
     if args.tiles is not None and (args.resolution != "square" or args.region != "none" or args.outpaint is not None):
         parser.error("--tiles does not go with --resolution, --region mask or --outpaint: the tile size is the edit size and the output has the "
@@ -175,7 +225,7 @@ def main(argv=None):
     from src.pipeline import FastEditor
     editor = FastEditor(model_name=args.model, device="cuda", enable_cpu_offload=not args.no_cpu_offload,
                         use_full_precision=args.full_precision, use_full_controlnet=args.full_controlnet,
-                        weights_dir=args.weights_dir)
+                        weights_dir=args.weights_dir, **(dict(clip_score_dir=args.clip_score_dir) if args.sweep and args.select == "clip_score" else {}))
     mem = editor.get_memory_usage()
     print(f"      GPU Memory: {mem['allocated_gb']:.2f}GB allocated, {mem['reserved_gb']:.2f}GB reserved")
 
@@ -215,10 +265,26 @@ def main(argv=None):
         extra.pop("output_size", None)
         print(f"      Tiles: {args.tiles if args.tiles == 'auto' else '%dx%d' % args.tiles}, overlap {args.tile_overlap} px, {args.tile_batch} per device job")
     t0 = time.time()
-    edited_img = editor.edit(image=source_img, prompt=args.prompt, negative_prompt=args.negative_prompt,
-                             num_inference_steps=args.steps, guidance_scale=args.guidance,
-                             controlnet_conditioning_scale=args.control_scale, canny_low_threshold=args.canny_low,
-                             canny_high_threshold=args.canny_high, seed=args.seed, **extra)
+    variants = None
+    if args.sweep:
+        extra.pop("strength", None)
+        if args.select != "none":
+            extra.update(select=args.select, **({} if args.min_ssim is None else dict(min_ssim=args.min_ssim)))
+        edited_img, info = editor.edit_sweep(image=source_img, prompt=args.prompt, negative_prompt=args.negative_prompt, strengths=args.strengths,
+                                             num_inference_steps=args.steps, guidance_scale=args.guidance,
+                                             controlnet_conditioning_scale=args.control_scale, canny_low_threshold=args.canny_low,
+                                             canny_high_threshold=args.canny_high, seed=args.seed, **extra)
+        variants = info if args.select == "none" else info["variants"]
+        for v in variants:
+            print(f"      {v['steps']} steps (strength {', '.join(format(s, 'g') for s in v['strength'])}): SSIM {v['ssim']:.4f}"
+                  + (f", background SSIM {v['bg_ssim']:.4f}" if "bg_ssim" in v else "") + (f", CLIP score {v['clip_score']:.2f}" if "clip_score" in v else ""))
+        if args.select != "none":
+            print(f"      Chosen by '{args.select}': {info['steps']} steps (variant {info['index']})")
+    else:
+        edited_img = editor.edit(image=source_img, prompt=args.prompt, negative_prompt=args.negative_prompt,
+                                 num_inference_steps=args.steps, guidance_scale=args.guidance,
+                                 controlnet_conditioning_scale=args.control_scale, canny_low_threshold=args.canny_low,
+                                 canny_high_threshold=args.canny_high, seed=args.seed, **extra)
     elapsed = time.time() - t0
     print(f"      Editing completed in {elapsed:.2f} seconds")
     mem = editor.get_memory_usage()
@@ -226,8 +292,15 @@ def main(argv=None):
 
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
     output_path = os.path.join(edited_dir, f"edited_{stamp}.jpg")
-    edited_img.save(output_path)
-    print(f"\n      Saved edited image to: {output_path}")
+    if isinstance(edited_img, list):                 # --sweep --select none: every variant, named by its step count; the strongest goes on below
+        for im, v in zip(edited_img, variants):
+            path = os.path.join(edited_dir, f"edited_{stamp}_steps{v['steps']}.jpg")
+            im.save(path)
+            print(f"\n      Saved the {v['steps']}-step variant to: {path}")
+        edited_img = edited_img[0]
+    else:
+        edited_img.save(output_path)
+        print(f"\n      Saved edited image to: {output_path}")
 
     if args.compute_metrics:
         print("\n[4/4] Computing metrics...")

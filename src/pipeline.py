@@ -8,7 +8,8 @@ HIP library or GPU raises.  Additive: `set_in_flight(n)` / `worker_slot(i)` (sev
 transformers CLIPModel directory: `edit(..., metrics=True)` then also returns the CLIP score of the edit), `dino_dir` (a local
 transformers ViTModel directory: `edit(..., metrics=True)` then also returns the DINO structure distance of the edit),
 `lpips_dir` (a local directory with the LPIPS SqueezeNet weights: `edit(..., metrics=True)` then also returns the LPIPS of the edit, DESIGN.md
-section 19).
+section 19), and `edit_sweep(...)`: edit() at several strengths as one device job, scored on the device, the winner picked there (DESIGN.md
+section 20).
 """
 import os
 import threading
@@ -109,6 +110,8 @@ class FastEditor:
         self._fullres_out = {}                 # (slot, image) -> flat u8 buffer on the device, grown to the largest source: the full-resolution back end's output (output_size="source")
         self._tile_bufs = {}                   # (slot, tiles, th, tw) -> u8 [tiles, th, tw, 3] on the device: where the tile results of a tiled edit meet (tiles=...)
         self._metric_rows = {}                 # (slot, images) -> pinned int64 [images, 4]: where an edit's metric rows land (metrics=True)
+        self._sweep_out = {}                   # slot -> flat u8 buffer on the device, grown to the largest image: where a sweep's winner lands (edit_sweep(select=...))
+        self._sweep_idx = {}                   # slot -> pinned int32 [1]: where a sweep's winning index lands
         self.clip_scorer = None                # fie_amd.clip_score.ClipScorer: only from a directory, never a made-up number
         self._clip_rows = {}                   # (slot, rows) -> pinned f32 [rows, 2]: where an edit's CLIP score rows land
         if clip_score_dir:
@@ -333,10 +336,118 @@ class FastEditor:
                     if buf is None or buf.numel() < src.numel():
                         buf = self._fullres_out[(slot, i)] = torch.empty(src.numel(), device=src.device, dtype=torch.uint8)
                     outs.append(ctx.fullres_paste(o.contiguous(), src, m, blur if m is not None else 0.0, out=buf[:src.numel()].view(src.shape)))
-            return DeviceOutput(outs if batch else outs[0], then(outs if batch else outs[0]) if then is not None else None)
+            extra = then(outs if batch else outs[0]) if then is not None else None
+            if isinstance(extra, DeviceOutput):           # `then` chose what travels itself (edit_sweep's selector: the winner alone)
+                return extra
+            return DeviceOutput(outs if batch else outs[0], extra)
         return backend
 
-    def _scorer(self, slot, origs, omasks, prompts=None):
+    def _selector(self, slot, scorer, keep, rule, floor, bg):
+        """The `after_device` hook of edit_sweep(select=...): runs `scorer` (the _scorer hook, whose device rows arrive in `keep`) on the k variants,
+        then queues ONE fie_sweep_select_u8 launch behind it on the same stream: the winner's bytes go into a buffer of the slot and take the final
+        device-to-host copy in place of the k images; the index rides with the rows into pinned host memory.  -> DeviceOutput([winner], (the
+        scorer's result, the int32 [1] index on the host))."""
+        ctx = self.pipe.ctx
+
+        def pick(out_u8):
+            outs = list(out_u8) if isinstance(out_u8, list) or out_u8.dim() == 4 else [out_u8]
+            extra = scorer(out_u8)
+            with self.pipe.eager_lock:                    # the context's stream binding is shared by the threads of in-flight edits
+                n = outs[0].numel()
+                buf = self._sweep_out.get(slot)           # grown, never shrunk: with output_size="source" the size follows the caller's images
+                if buf is None or buf.numel() < n:
+                    buf = self._sweep_out[slot] = torch.empty(n, device=ctx.device, dtype=torch.uint8)
+                win, idx = ctx.sweep_select([o.contiguous() for o in outs], keep["rows"], keep.get("clip"), rule, floor, bg,
+                                            out=buf[:n].view(outs[0].shape))
+            ihost = self._sweep_idx.get(slot)
+            if ihost is None:
+                ihost = self._sweep_idx[slot] = torch.empty(1, dtype=torch.int32).pin_memory()
+            ihost.copy_(idx, non_blocking=True)
+            return DeviceOutput([win], (extra, ihost))
+        return pick
+
+    def edit_sweep(self, image, prompt, negative_prompt="", strengths="all", num_inference_steps=4, guidance_scale=1.5,
+                   controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
+                   paste_back=True, *, resolution=None, output_size=None, region=None, tiles=None, masked_content="original", blend="alpha",
+                   blend_levels=4, mask_grow=0, outpaint=None, select=None, min_ssim=None):
+        """[additive] edit() at several strengths as ONE device job, scored on the device, optionally with the winner picked there (DESIGN.md
+        section 20).  `strength` only decides how many of the `num_inference_steps` LCM steps an edit runs, so the distinct edits are those of the
+        distinct step counts m = min(int(N * s), N): `strengths` is "all" (one variant per m = 1 .. N) or a list of floats in [0, 1]; strengths with
+        the same m are one variant (fie_amd/sweep.py: variants; at most 16).  Variants are ordered strongest first.  Upload, resize, Canny map, text
+        encoders, mask preparation, fill, VAE encode and edge-map embedding run once; the UNet and the ControlNet run each loop step on the
+        variants that have joined by then; with `seed`, variant i is what edit(..., strength=s_i, seed=seed) returns up to fp16 tiling effects
+        (the bound of edit_batch against serial edits).  The other keywords are edit()'s (`metrics` is always on; `region` and `tiles` are a
+        ValueError).
+        select=None: returns (images, variants): variants[i] = {"strength": [the requested strengths of the variant], "steps": m, and the
+        metrics dict edit(..., strength=s_i, metrics=True) reports}.
+        select="strongest" (needs `min_ssim`): the strongest variant whose SSIM against the source -- `bg_ssim` with a mask -- is at least
+        `min_ssim`: the most editing the preservation budget allows.  select="clip_score" (needs FastEditor(clip_score_dir=...)): the variant
+        with the best CLIP score, among those that pass `min_ssim` when one is given; ties go to the weaker edit.  When no variant passes, the
+        one with the highest SSIM wins (fie_amd/sweep.py: select_numpy is the rule, word for word).  Both return (image, info): info holds
+        `index`, `strength`, `steps`, the winner's metrics, `variants` as above and `rows` / `clip_rows` (the raw rows the rule read).  The rule runs
+        in one HIP op behind the scorer (fie_sweep_select_u8): only the winner's image crosses to the host -- with output_size="source" one
+        source-size image instead of k -- behind one synchronisation."""
+        from fie_amd import sweep as hsweep
+        if region is not None:
+            raise ValueError("edit_sweep with a region: a sweep runs on the whole image")
+        if tiles is not None:
+            raise ValueError("edit_sweep with tiles: a sweep runs as one device job")
+        if select not in (None, "clip_score", "strongest"):
+            raise ValueError(f"select={select!r}: None, 'clip_score' or 'strongest'")
+        if select == "clip_score" and self.clip_scorer is None:
+            raise ValueError("select='clip_score' needs a CLIP model: FastEditor(clip_score_dir=...)")
+        if select == "strongest" and min_ssim is None:
+            raise ValueError("select='strongest' needs min_ssim: the SSIM every candidate must keep")
+        if min_ssim is not None:
+            if select is None:
+                raise ValueError("min_ssim without select: 'clip_score' or 'strongest'")
+            if isinstance(min_ssim, bool) or not isinstance(min_ssim, (int, float)) or not -1.0 <= float(min_ssim) <= 1.0:
+                raise ValueError(f"min_ssim={min_ssim!r}: a number in [-1, 1]")
+        vs = hsweep.variants(num_inference_steps, strengths)
+        full = hregion.check_output(output_size, None)
+        margins = hmask.check_outpaint(outpaint)
+        masked = mask is not None or margins is not None
+        hmask.check_args(mask_blur, paste_back, masked)
+        hmask.check_content(masked_content, masked)
+        hmask.check_blend(blend, blend_levels, masked, paste_back)
+        grow = hmask.check_grow(mask_grow, masked)
+        mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
+        size = buckets.target_size(resolution, hmask.canvas_size(image.size, margins))
+        generator = None
+        if seed is not None:
+            generator = torch.Generator(device=self.device).manual_seed(seed)
+        slot = getattr(self._tls, "slot", 0)
+        origs, omasks = [], []
+        with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
+            if margins is not None:
+                image, mask_l = self._outpaint_device(image, mask_l, margins)
+            source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False,
+                                                                 original=origs)
+            mask_dev = self._mask_device(mask_l, size, original=omasks, grow=grow)
+        k = len(vs)
+        # the hook order of edit(): the full-resolution back end first, for all k, then the scorer -- and the selector last
+        keep = {}
+        hook = self._scorer(slot, origs * k, omasks * k, [prompt] * k, keep=keep)
+        if select is not None:
+            hook = self._selector(slot, hook, keep, select, hsweep.ssim_floor(min_ssim, hmetrics.TARGET[1], hmetrics.TARGET[0]), masked)
+        if full:
+            hook = self._fullres(slot, origs * k, (omasks if paste_back else [None]) * k, mask_blur, hook)
+        res = self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev, control_image=control_dev,
+                        strength=[v[1][0] for v in vs], num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                        controlnet_conditioning_scale=controlnet_conditioning_scale, generator=generator, post_check=finish,
+                        mask_image=mask_dev, mask_blur=0 if full else mask_blur, paste_back=paste_back and not full, after_device=hook,
+                        masked_content=masked_content, blend=blend, blend_levels=blend_levels, paste_later=full)
+        extra, ihost = res.extra if select is not None else (res.extra, None)
+        variants = [{"strength": list(v[1]), "steps": v[0], **d} for v, d in zip(vs, self._scores(extra, [masked] * k))]
+        if select is None:
+            return res.images, variants
+        index = int(ihost[0])
+        rows = (extra[0] if isinstance(extra, tuple) else extra).numpy().copy()
+        clip_rows = extra[1].numpy()[:k].copy() if isinstance(extra, tuple) and extra[1] is not None else None
+        info = dict(variants[index], index=index, variants=variants, rows=rows, clip_rows=clip_rows)
+        return res.images[0], info
+
+    def _scorer(self, slot, origs, omasks, prompts=None, keep=None):
         """The `after_device` hook of an edit with metrics=True: queues, on the edit's stream behind its result, the LANCZOS resizes to
         512x512 (sources, results, masks), ONE fie_metrics_pairs_u8 launch pair for all images of the job and the copy of the 32-byte result
         rows into pinned host memory of the slot.  The edit's own final synchronisation (the image's D2H) completes them.  With a CLIP model
@@ -345,7 +456,8 @@ class FastEditor:
         model (`dino_scorer`) it queues, behind those, the structure distance of every (original source, result) pair of square images -- one batched
         pass of the tower per (source size, result size) -- and the tuple grows by (distance rows, which image each row is).  With the LPIPS
         weights (`lpips_scorer`) it queues the LPIPS layer values of every pair on the 512x512 tensors and the binary masks it has already built
-        (the background variant where an image has a mask), and the tuple's sixth entry is their rows."""
+        (the background variant where an image has a mask), and the tuple's sixth entry is their rows.  `keep`: a dict that receives the DEVICE
+        tensors of the metric rows ("rows") and of the CLIP rows ("clip"), for work queued behind the scorer (edit_sweep's selector)."""
         ctx = self.pipe.ctx
         th, tw = hmetrics.TARGET[1], hmetrics.TARGET[0]
         to512 = lambda t: t if tuple(t.shape[:2]) == (th, tw) else ctx.resize_lanczos(t.contiguous(), th, tw)
@@ -361,6 +473,8 @@ class FastEditor:
                     zero = lambda: torch.zeros((th, tw), device=ctx.device, dtype=torch.uint8)
                     mk = stack([zero() if m is None else hmetrics.binary_mask_device(ctx, m) for m in omasks])
                 rows = ctx.metrics_pairs(a, b, mk)
+                if keep is not None:
+                    keep["rows"] = rows
             host = self._metric_rows.get((slot, len(outs)))
             if host is None:
                 host = self._metric_rows[(slot, len(outs))] = torch.empty((len(outs), 4), dtype=torch.int64).pin_memory()
@@ -380,6 +494,8 @@ class FastEditor:
                 txts = [clip.text_embedding(prompts[i]) for i, _ in items]
                 emb = clip.image_embeddings([outs[i] for i, _ in items], [omasks[i] if masked else None for i, masked in items])
                 crow = clip.score_rows(emb, txts[0] if len(txts) == 1 else torch.cat(txts))
+                if keep is not None:
+                    keep["clip"] = crow
             chost = self._clip_rows.get((slot, len(items)))
             if chost is None:
                 chost = self._clip_rows[(slot, len(items))] = torch.empty((len(items), 2), dtype=torch.float32).pin_memory()
