@@ -87,6 +87,14 @@ def check_grow(mask_grow, have_mask=True):
     return int(mask_grow)
 
 
+def check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, have_mask=True, paste_later=False):
+    """The four rule sets above in the one order every entry point runs them: args, content, blend, grow.  `paste_later`: the caller composites
+    behind the job, which counts as a paste-back for `blend`.  Returns the normalised (content, (blend, levels), grow)."""
+    check_args(mask_blur, paste_back, have_mask)
+    return (check_content(masked_content, have_mask), check_blend(blend, blend_levels, have_mask, paste_back or paste_later),
+            check_grow(mask_grow, have_mask))
+
+
 def check_outpaint(outpaint):
     """The argument rules of `outpaint` (the canvas grown by four margins of new border, which becomes the mask): None, or a
     sequence (left, top, right, bottom) of integers in 0..4096 with at least one > 0.  Returns a tuple of ints, or None.  A mask is not needed:

@@ -250,26 +250,20 @@ class FastEditor:
         crosses to the host is the result.  `resolution`, `region`, `outpaint` and output_size="edit" with tiles are a
         ValueError; None (default) changes nothing."""
         tiles, tile_overlap, tile_batch = htiles.check(tiles, tile_overlap, tile_batch)
+        kw = dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                  controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
+                  canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
+                  masked_content=masked_content, blend=blend, blend_levels=blend_levels)
         if tiles is not None:
             self._check_tiled(resolution, region, outpaint, output_size)
             masked = mask is not None
-            hmask.check_args(mask_blur, paste_back, masked)
-            hmask.check_content(masked_content, masked)
-            hmask.check_blend(blend, blend_levels, masked, paste_back)
-            grow = hmask.check_grow(mask_grow, masked)
+            grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, masked)[2]
             return self._edit_tiled(image, prompt, negative_prompt, htiles.plan(image.size, tiles, tile_overlap), tile_batch,
-                                    hmask.to_l_array(mask, image.size) if masked else None, grow, metrics,
-                                    dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                                         controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
-                                         canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
-                                         masked_content=masked_content, blend=blend, blend_levels=blend_levels))
+                                    hmask.to_l_array(mask, image.size) if masked else None, grow, metrics, kw)
         full = hregion.check_output(output_size, region)
         margins = hmask.check_outpaint(outpaint)
         masked = mask is not None or margins is not None          # the new border is a mask of its own
-        hmask.check_args(mask_blur, paste_back, masked)
-        hmask.check_content(masked_content, masked)
-        hmask.check_blend(blend, blend_levels, masked, paste_back)
-        grow = hmask.check_grow(mask_grow, masked)
+        grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, masked)[2]
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
         if region is not None and margins is not None:            # a region crops on the host: the canvas comes back once, the rest is the call on it
             canvas, canvas_mask = self._outpaint_host(image, mask_l, margins)
@@ -288,10 +282,21 @@ class FastEditor:
             if metrics:
                 return hregion.paste(image, res[0], box), res[1]
             return hregion.paste(image, res, box)
+        res = self._single_job(image, prompt, negative_prompt, 1, resolution, mask_l, margins, grow, metrics, full, kw)
+        if not metrics:
+            return res.images[0]
+        return res.images[0], self._scores(res.extra, [masked])[0]
+
+    def _single_job(self, image, prompt, negative_prompt, k, resolution, mask_l, margins, grow, metrics, full, kw, select=None):
+        """The tail of edit() and edit_sweep() behind their argument checks: ONE device job on one image with k rows -- edit(): 1 and
+        kw["strength"] a float; edit_sweep(): its variants and kw["strength"] their list of strengths.  mask_l: None or the uint8 [H, W] mask;
+        margins: check_outpaint()'s tuple or None; grow: check_grow()'s radius; kw: the scalar keywords of edit().  `select`: None, or
+        (rule, floor, bg) of the selector that wraps the scorer (_selector).  Hooks, outermost first: _fullres, _selector, _scorer.
+        -> the pipeline's result."""
         size = buckets.target_size(resolution, hmask.canvas_size(image.size, margins))
         generator = None
-        if seed is not None:
-            generator = torch.Generator(device=self.device).manual_seed(seed)
+        if kw["seed"] is not None:
+            generator = torch.Generator(device=self.device).manual_seed(kw["seed"])
         # same data flow as the reference (:251-272) with the images kept in HBM: the LANCZOS resize to 1024x1024 (:251) runs
         # on the device (bit-exact with Pillow, csrc/resize.hip) on the uploaded original, and preprocess_image()'s PIL round
         # trip (D2H of the edge map + H2D again inside the pipeline) is skipped
@@ -304,21 +309,22 @@ class FastEditor:
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             if margins is not None:         # from here on the canvas and its mask stand where the image and the mask stood, already on the device
                 image, mask_l = self._outpaint_device(image, mask_l, margins)
-            source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False,
+            source_dev, control_dev, finish = self._canny_device(image, kw["canny_low_threshold"], kw["canny_high_threshold"], size=size, wait=False,
                                                                  original=origs)
             mask_dev = self._mask_device(mask_l, size, original=omasks, grow=grow)
-        hook = self._scorer(slot, origs, omasks, [prompt]) if metrics else None
-        if full:        # the edit-size job runs with its own paste-back off: the composite happens at the source's size, behind it
-            hook = self._fullres(slot, origs, omasks if paste_back else [None], mask_blur, hook)
-        res = self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev,
-                        control_image=control_dev, strength=strength, num_inference_steps=num_inference_steps,
-                        guidance_scale=guidance_scale, controlnet_conditioning_scale=controlnet_conditioning_scale,
-                        generator=generator, post_check=finish, mask_image=mask_dev, mask_blur=0 if full else mask_blur,
-                        paste_back=paste_back and not full, after_device=hook, masked_content=masked_content, blend=blend,
-                        blend_levels=blend_levels, paste_later=full)
-        if not metrics:
-            return res.images[0]
-        return res.images[0], self._scores(res.extra, [masked])[0]
+        hook = None
+        if metrics:
+            keep = {} if select is not None else None
+            hook = self._scorer(slot, origs * k, omasks * k, [prompt] * k, keep=keep)
+            if select is not None:
+                hook = self._selector(slot, hook, keep, *select)
+        if full:        # the edit-size job runs with its own paste-back off: the composite happens at the source's size, behind it, for all k rows
+            hook = self._fullres(slot, origs * k, (omasks if kw["paste_back"] else [None]) * k, kw["mask_blur"], hook)
+        return self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev, control_image=control_dev,
+                         strength=kw["strength"], num_inference_steps=kw["num_inference_steps"], guidance_scale=kw["guidance_scale"],
+                         controlnet_conditioning_scale=kw["controlnet_conditioning_scale"], generator=generator, post_check=finish,
+                         mask_image=mask_dev, mask_blur=0 if full else kw["mask_blur"], paste_back=kw["paste_back"] and not full,
+                         after_device=hook, masked_content=kw["masked_content"], blend=kw["blend"], blend_levels=kw["blend_levels"], paste_later=full)
 
     def _fullres(self, slot, origs, omasks, blur, then=None):
         """The `after_device` hook of an edit with output_size="source": queues, on the edit's stream behind its result and outside its graph, the
@@ -407,36 +413,15 @@ class FastEditor:
         full = hregion.check_output(output_size, None)
         margins = hmask.check_outpaint(outpaint)
         masked = mask is not None or margins is not None
-        hmask.check_args(mask_blur, paste_back, masked)
-        hmask.check_content(masked_content, masked)
-        hmask.check_blend(blend, blend_levels, masked, paste_back)
-        grow = hmask.check_grow(mask_grow, masked)
+        grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, masked)[2]
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
-        size = buckets.target_size(resolution, hmask.canvas_size(image.size, margins))
-        generator = None
-        if seed is not None:
-            generator = torch.Generator(device=self.device).manual_seed(seed)
-        slot = getattr(self._tls, "slot", 0)
-        origs, omasks = [], []
-        with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
-            if margins is not None:
-                image, mask_l = self._outpaint_device(image, mask_l, margins)
-            source_dev, control_dev, finish = self._canny_device(image, canny_low_threshold, canny_high_threshold, size=size, wait=False,
-                                                                 original=origs)
-            mask_dev = self._mask_device(mask_l, size, original=omasks, grow=grow)
         k = len(vs)
-        # the hook order of edit(): the full-resolution back end first, for all k, then the scorer -- and the selector last
-        keep = {}
-        hook = self._scorer(slot, origs * k, omasks * k, [prompt] * k, keep=keep)
-        if select is not None:
-            hook = self._selector(slot, hook, keep, select, hsweep.ssim_floor(min_ssim, hmetrics.TARGET[1], hmetrics.TARGET[0]), masked)
-        if full:
-            hook = self._fullres(slot, origs * k, (omasks if paste_back else [None]) * k, mask_blur, hook)
-        res = self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev, control_image=control_dev,
-                        strength=[v[1][0] for v in vs], num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                        controlnet_conditioning_scale=controlnet_conditioning_scale, generator=generator, post_check=finish,
-                        mask_image=mask_dev, mask_blur=0 if full else mask_blur, paste_back=paste_back and not full, after_device=hook,
-                        masked_content=masked_content, blend=blend, blend_levels=blend_levels, paste_later=full)
+        kw = dict(strength=[v[1][0] for v in vs], num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                  controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
+                  canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
+                  masked_content=masked_content, blend=blend, blend_levels=blend_levels)
+        rule = None if select is None else (select, hsweep.ssim_floor(min_ssim, hmetrics.TARGET[1], hmetrics.TARGET[0]), masked)
+        res = self._single_job(image, prompt, negative_prompt, k, resolution, mask_l, margins, grow, True, full, kw, select=rule)
         extra, ihost = res.extra if select is not None else (res.extra, None)
         variants = [{"strength": list(v[1]), "steps": v[0], **d} for v, d in zip(vs, self._scores(extra, [masked] * k))]
         if select is None:
@@ -643,10 +628,7 @@ class FastEditor:
         if htiles.check(tiles, tile_overlap, tile_batch)[0] is not None:
             self._check_tiled(resolution, region, outpaint, output_size)
             has_mask = [masks is not None and m is not None for m in (masks or [None] * len(images))]
-            hmask.check_args(mask_blur, paste_back, any(has_mask))
-            hmask.check_content(masked_content, any(has_mask))
-            hmask.check_blend(blend, blend_levels, any(has_mask), paste_back)
-            hmask.check_grow(mask_grow, any(has_mask))
+            hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, any(has_mask))
             negs = list(negative_prompts) if isinstance(negative_prompts, (list, tuple)) else [negative_prompts or ""] * len(images)
             if len(negs) != len(images):
                 raise ValueError(f"{len(negs)} negative prompts for {len(images)} images")
@@ -663,16 +645,13 @@ class FastEditor:
         margins = [hmask.check_outpaint(o) for o in outpaint] if isinstance(outpaint, list) else [hmask.check_outpaint(outpaint)] * len(images)
         outpainted = any(o is not None for o in margins)
         has_mask = [(masks is not None and masks[i] is not None) or o is not None for i, o in enumerate(margins)]
-        hmask.check_content(masked_content, any(has_mask))
-        hmask.check_blend(blend, blend_levels, any(has_mask), paste_back)
-        grow = hmask.check_grow(mask_grow, any(has_mask))
+        grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, any(has_mask))[2]
         regions = list(region) if isinstance(region, list) else [region] * len(images)
         if len(regions) != len(images):
             raise ValueError(f"{len(regions)} regions for {len(images)} images: one region (or None) per image")
         has_region = any(r is not None for r in regions)
         full = hregion.check_output(output_size, "mask" if has_region else None)
         if has_region and outpainted:       # regions crop on the host: the canvases come back once (edit()), the rest is the call on them
-            hmask.check_args(mask_blur, paste_back, True)
             canvases, cmasks = list(images), list(masks) if masks is not None else [None] * len(images)
             for i, o in enumerate(margins):
                 if o is not None:
@@ -683,7 +662,6 @@ class FastEditor:
                                    metrics=metrics, output_size=output_size, region=region, region_padding=region_padding,
                                    masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow)
         if has_region:
-            hmask.check_args(mask_blur, paste_back, masks is not None and any(m is not None for m in masks))
             mls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks or [None] * len(images), images)]
             if grow:        # grown first, cropped second (edit())
                 mls = [m if m is None else self._grow_host(m, grow) for m in mls]
@@ -718,7 +696,6 @@ class FastEditor:
                 for i, r, m in zip(idx, res, ms):
                     out[i], mets[i] = r, m
             return (out, mets) if metrics else out
-        hmask.check_args(mask_blur, paste_back, any(has_mask))
         mask_ls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks, images)] if masks is not None else None
         if outpainted and mask_ls is None:
             mask_ls = [None] * len(images)
