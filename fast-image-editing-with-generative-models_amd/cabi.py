@@ -335,11 +335,14 @@ def run_edit(pipe, job, step_cache=True):
     non-Python host would issue for the pipeline call at /root/reference/src/pipeline.py:261-272.  Returns the u8 HWC image on the device.
     A masked job (pipe.prepare(..., mask_image=...)) takes the masked entries: fie_latent_prep_src, fie_lcm_step_masked and, with the
     paste-back, fie_pixels_out_composite_* ("Mask-restricted edits").  The masked-content modes are not
-    part of this walk: a job prepared with one is refused rather than run as "original"; so is a job with blend="multiband" (section 15)."""
+    part of this walk: a job prepared with one is refused rather than run as "original"; so is a job with blend="multiband" (section 15) and a
+    soft mask's job (mask_mode="levels" / mask_ramp; section 21)."""
     if job.get("content"):
         raise NotImplementedError(f"run_edit: masked_content={job['content']!r} is not part of the C-ABI walk")
     if job.get("blend"):
         raise NotImplementedError(f"run_edit: blend={job['blend'][0]!r} is not part of the C-ABI walk")
+    if job.get("lvl_lat") is not None:
+        raise NotImplementedError("run_edit: a soft mask (mask_mode='levels' / mask_ramp) is not part of the C-ABI walk")
     ctx = pipe.ctx
     dev = ctx.device
     h, w = job["hw"]

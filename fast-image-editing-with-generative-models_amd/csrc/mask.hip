@@ -1,10 +1,14 @@
-// Mask-restricted edits (include/fie.h: fie_mask_prep, fie_latent_prep_src, fie_lcm_step_masked, fie_pixels_out_composite_*).
+// Mask-restricted edits (include/fie.h: fie_mask_prep, fie_latent_prep_src, fie_lcm_step_masked, fie_lcm_step_levels, fie_mask_levels_u8,
+// fie_mask_support_u8, fie_pixels_out_composite_*).
 // The semantics are those of the diffusers inpaint pipelines for a 4-channel UNet layered on the img2img edit:
 //   mask prep   binarise the edit-size u8 mask (L >= 128), nearest latent downsample m_lat[y][x] = m_px[8y][8x], optional separable
 //               Gaussian feather of m_px (sigma r, radius R = ceil(3r), clamp-to-edge) for the paste-back;
 //   latent prep today's K9 plus the clean source latent z0 it used to discard;
 //   LCM step    today's K8 plus, per latent pixel, lat = m_lat ? lat : (sab_prev z0 + s1mab_prev n_init), or z0 on the last step;
 //   composite   today's pixels_out, then the source u8 where m == 0, the decoded byte where m == 1, rint(m d + (1-m) src) between.
+// Soft masks: the latent mask holds levels v in 0 .. 255 and the step its place j among the K steps of the edit; a pixel
+// is inside after step j iff v K > 255 (K - 1 - j), i.e. it is edited for the last (v K + 254) / 255 steps.  The binary step is the case of
+// levels 0 / 1 with K = 1, j = 0 (v > 0): one kernel, one more integer multiply and compare per latent pixel.
 // lcm_step_kernel, latent_prep_kernel and pixels_out_kernel (pointwise.hip) are untouched: an unmasked edit launches exactly what it did.
 #include "image_ops.h"
 
@@ -68,6 +72,7 @@ struct LcmMaskedArgs {
     float sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p;
     T* model_in; int copies; float inv_sf; T* decode_in;
     const uint8_t* m_lat; const float* z0; const float* n_init;
+    int steps, thresh;                     // inside iff m_lat * steps > thresh; thresh = 255 (steps - 1 - step), 0 for a binary mask (steps = 1)
 };
 
 // Keeps a rounded product out of the backend's multiply-add fusion (-ffp-contract=fast fuses across statements): emits nothing.
@@ -92,7 +97,7 @@ __global__ void lcm_step_masked_kernel(LcmMaskedArgs<T> p) {
         }
         float4 l = *reinterpret_cast<const float4*>(p.lat + i * 4);
         const float4 z = *reinterpret_cast<const float4*>(p.z0 + i * 4);
-        const bool inside = p.m_lat[i] != 0;
+        const bool inside = (int)p.m_lat[i] * p.steps > p.thresh;
         float* lp = &l.x;
         const float* zp = &z.x;
         float o[8] = {0, 0, 0, 0, 0, 0, 0, 0}, od[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -147,6 +152,23 @@ __global__ void pixels_out_composite_kernel(const T* src, int64_t ld, int64_t nq
     }
 }
 
+// The latent levels of a soft mask: lvl_lat = mask_lat ? max(levels[8y][8x], 1) : 0 -- the support stays fie_mask_prep's mask_lat bit for bit
+__global__ void mask_levels_kernel(const uint8_t* __restrict__ levels, const uint8_t* __restrict__ m_lat, int lh, int lw, int W,
+                                   uint8_t* __restrict__ lvl_lat) {
+    const int n = lh * lw;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int y = i / lw, x = i - y * lw;
+        const uint8_t v = levels[(int64_t)(8 * y) * W + 8 * x];
+        lvl_lat[i] = m_lat[i] ? (v ? v : (uint8_t)1) : (uint8_t)0;
+    }
+}
+
+// The support of a level map: 255 where the level is > 0
+__global__ void mask_support_kernel(const uint8_t* __restrict__ levels, int64_t n, uint8_t* __restrict__ out) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = levels[i] ? 255 : 0;
+}
+
 template <typename T>
 int latent_prep_src_t(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW, float sf, float sqrt_ab,
                       float sqrt_1mab, float* latents_out, void* model_in, int copies, float* z0_out) {
@@ -161,14 +183,17 @@ int latent_prep_src_t(fie_ctx* ctx, const void* moments, const float* eps_post, 
 template <typename T>
 int lcm_step_masked_t(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents, const float* noise, int64_t HW,
                       float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out, float sqrt_ab_prev, float sqrt_1mab_prev, void* model_in,
-                      int copies, float inv_scaling, void* decode_in, const uint8_t* mask_lat, const float* z0, const float* noise_init) {
-    FIE_REQUIRE(ctx && eps && latents && HW > 0, "fie_lcm_step_masked: bad argument");
-    FIE_REQUIRE(mask_lat && z0 && (noise_init || !noise), "fie_lcm_step_masked: mask_lat, z0 and (before the last step) noise_init are required");
-    FIE_REQUIRE(nb == 1 || nb == 2, "fie_lcm_step_masked: nb=%d (1 or 2)", nb);
-    FIE_REQUIRE(ld_eps % 4 == 0 && ld_eps >= 4, "fie_lcm_step_masked: ld_eps must be a multiple of 4");
-    FIE_REQUIRE(sqrt_ab_t > 0.f, "fie_lcm_step_masked: sqrt(alpha_bar_t) must be positive");
+                      int copies, float inv_scaling, void* decode_in, const uint8_t* mask_lat, const float* z0, const float* noise_init,
+                      int steps = 1, int step = 0, const char* who = "fie_lcm_step_masked") {
+    FIE_REQUIRE(ctx && eps && latents && HW > 0, "%s: bad argument", who);
+    FIE_REQUIRE(mask_lat && z0 && (noise_init || !noise), "%s: mask_lat, z0 and (before the last step) noise_init are required", who);
+    FIE_REQUIRE(nb == 1 || nb == 2, "%s: nb=%d (1 or 2)", who, nb);
+    FIE_REQUIRE(ld_eps % 4 == 0 && ld_eps >= 4, "%s: ld_eps must be a multiple of 4", who);
+    FIE_REQUIRE(sqrt_ab_t > 0.f, "%s: sqrt(alpha_bar_t) must be positive", who);
+    FIE_REQUIRE(steps >= 1 && steps <= 255 && step >= 0 && step < steps, "%s: step %d of %d steps (1 .. 255 steps, step in 0 .. steps - 1)", who, step, steps);
     LcmMaskedArgs<T> p = {(const T*)eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out,
-                          sqrt_ab_prev, sqrt_1mab_prev, (T*)model_in, copies, inv_scaling, (T*)decode_in, mask_lat, z0, noise_init};
+                          sqrt_ab_prev, sqrt_1mab_prev, (T*)model_in, copies, inv_scaling, (T*)decode_in, mask_lat, z0, noise_init,
+                          steps, 255 * (steps - 1 - step)};
     fie_launch(ctx, lcm_step_masked_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, p);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
@@ -221,6 +246,37 @@ int fie_lcm_step_masked_f32(fie_ctx* ctx, const void* eps, int64_t ld_eps, int n
                             const float* z0, const float* noise_init) {
     return lcm_step_masked_t<float>(ctx, eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out, sqrt_ab_prev,
                                     sqrt_1mab_prev, model_in, copies, inv_scaling, decode_in, mask_lat, z0, noise_init);
+}
+int fie_lcm_step_levels(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents, const float* noise, int64_t HW,
+                        float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out, float sqrt_ab_prev, float sqrt_1mab_prev,
+                        void* model_in, int copies, float inv_scaling, void* decode_in, const uint8_t* lvl_lat, const float* z0,
+                        const float* noise_init, int steps, int step) {
+    return lcm_step_masked_t<half_t>(ctx, eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out, sqrt_ab_prev,
+                                     sqrt_1mab_prev, model_in, copies, inv_scaling, decode_in, lvl_lat, z0, noise_init, steps, step,
+                                     "fie_lcm_step_levels");
+}
+int fie_lcm_step_levels_f32(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents, const float* noise,
+                            int64_t HW, float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out, float sqrt_ab_prev,
+                            float sqrt_1mab_prev, void* model_in, int copies, float inv_scaling, void* decode_in, const uint8_t* lvl_lat,
+                            const float* z0, const float* noise_init, int steps, int step) {
+    return lcm_step_masked_t<float>(ctx, eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out, sqrt_ab_prev,
+                                    sqrt_1mab_prev, model_in, copies, inv_scaling, decode_in, lvl_lat, z0, noise_init, steps, step,
+                                    "fie_lcm_step_levels_f32");
+}
+int fie_mask_levels_u8(fie_ctx* ctx, const uint8_t* levels_e, const uint8_t* mask_lat, int H, int W, uint8_t* lvl_lat) {
+    FIE_REQUIRE(ctx && levels_e && mask_lat && lvl_lat, "fie_mask_levels_u8: NULL argument");
+    FIE_REQUIRE(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && (int64_t)H * W < ((int64_t)1 << 31),
+                "fie_mask_levels_u8: H, W must be positive multiples of 8 with H * W < 2^31 (got %d x %d)", H, W);
+    const int lh = H / 8, lw = W / 8;
+    fie_launch(ctx, mask_levels_kernel, dim3(grid_1d((int64_t)lh * lw, kPointwiseBlocks)), dim3(256), 0, levels_e, mask_lat, lh, lw, W, lvl_lat);
+    FIE_LAUNCH_CHECK();
+    return FIE_OK;
+}
+int fie_mask_support_u8(fie_ctx* ctx, const uint8_t* levels, int64_t n, uint8_t* out) {
+    FIE_REQUIRE(ctx && levels && out && n > 0, "fie_mask_support_u8: bad argument");
+    fie_launch(ctx, mask_support_kernel, dim3(grid_1d(n, kPointwiseBlocks)), dim3(256), 0, levels, n, out);
+    FIE_LAUNCH_CHECK();
+    return FIE_OK;
 }
 int fie_pixels_out_composite_f16_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, const uint8_t* source, const float* mask,
                                     uint8_t* dst) {

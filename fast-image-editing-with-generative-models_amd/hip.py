@@ -898,6 +898,53 @@ class Context:
         _chk(lib().fie_mask_grow_u8(self.h, _p(mask_l), h, w, int(radius), _p(out)))
         return out
 
+    def mask_ramp(self, mask_l, radius, out=None):
+        """A level map from a binary mask's outline (fie_mask_ramp_u8): 0 outside the mask (set = L >= 128), inside it
+        floor(255 d / radius) clipped to 255, d the Euclidean distance to the nearest unset pixel of the image; radius in 1 .. 64.  mask_l:
+        contiguous u8 [H, W] on the device, any size below 2^31 pixels.  -> u8 [H, W]; `out`: a contiguous u8 [H, W] tensor to write (not the
+        operand).  One launch, no synchronisation."""
+        self.sync_stream()
+        if not torch.is_tensor(mask_l) or mask_l.dim() != 2 or mask_l.dtype != torch.uint8 or not mask_l.is_contiguous():
+            raise ValueError(f"mask_ramp: a contiguous u8 [H, W] mask, got {tuple(getattr(mask_l, 'shape', ()))} {getattr(mask_l, 'dtype', type(mask_l).__name__)}")
+        if isinstance(radius, bool) or not isinstance(radius, numbers.Integral):
+            raise ValueError(f"mask_ramp: radius={radius!r}: an integer")
+        h, w = mask_l.shape
+        if out is None:
+            out = self._alloc((h, w), torch.uint8)
+        elif tuple(out.shape) != (h, w) or out.dtype != torch.uint8 or not out.is_contiguous() or out.data_ptr() == mask_l.data_ptr():
+            raise ValueError(f"mask_ramp: out must be a contiguous u8 {(h, w)} tensor of its own")
+        _chk(lib().fie_mask_ramp_u8(self.h, _p(mask_l), h, w, int(radius), _p(out)))
+        return out
+
+    def mask_support(self, levels, out=None):
+        """The support of a level map: u8 of any shape (contiguous) -> u8 of that shape, 255 where the level is > 0 (fie_mask_support_u8)."""
+        self.sync_stream()
+        if not torch.is_tensor(levels) or levels.dtype != torch.uint8 or not levels.is_contiguous() or levels.numel() == 0:
+            raise ValueError("mask_support: a contiguous, non-empty u8 tensor")
+        if out is None:
+            out = self._alloc(tuple(levels.shape), torch.uint8)
+        elif tuple(out.shape) != tuple(levels.shape) or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError(f"mask_support: out must be a contiguous u8 {tuple(levels.shape)} tensor")
+        _chk(lib().fie_mask_support_u8(self.h, _p(levels), levels.numel(), _p(out)))
+        return out
+
+    def mask_levels(self, levels_e, mask_lat, out=None):
+        """The latent levels of a soft mask (fie_mask_levels_u8): levels_e u8 [H, W] at the edit size, mask_lat u8 [H/8 * W/8] (mask_prep's, of
+        the support) -> u8 [H/8 * W/8]: mask_lat ? max(levels_e[8y, 8x], 1) : 0."""
+        self.sync_stream()
+        if not torch.is_tensor(levels_e) or levels_e.dim() != 2 or levels_e.dtype != torch.uint8 or not levels_e.is_contiguous():
+            raise ValueError("mask_levels: levels_e must be a contiguous u8 [H, W] tensor")
+        h, w = levels_e.shape
+        n = (h // 8) * (w // 8)
+        if h % 8 or w % 8 or mask_lat.dtype != torch.uint8 or mask_lat.numel() != n or not mask_lat.is_contiguous():
+            raise ValueError(f"mask_levels: H, W multiples of 8 and mask_lat a contiguous u8 tensor of {n} elements")
+        if out is None:
+            out = self._alloc((n,), torch.uint8)
+        elif out.dtype != torch.uint8 or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"mask_levels: out must be a contiguous u8 tensor of {n} elements")
+        _chk(lib().fie_mask_levels_u8(self.h, _p(levels_e), _p(mask_lat), h, w, _p(out)))
+        return out
+
     def outpaint_canvas(self, src, mask_l, margins, out=None):
         """The canvas of an outpainting edit and its mask (fie_outpaint_canvas_rgb_u8).  src: contiguous u8 [H, W, 3] on the
         device; mask_l: None or a contiguous u8 [H, W]; margins: (left, top, right, bottom), integers in 0 .. 4096, not all 0.  -> (canvas u8
@@ -1378,6 +1425,16 @@ class Context:
             self.h, _p(eps), eps.shape[-1], nb, float(guidance), _p(latents), _p(noise), hw, float(sab_t), float(s1mab_t), float(c_skip),
             float(c_out), float(sab_p), float(s1mab_p), _p(model_in), model_in.shape[0] if model_in is not None else 0, float(inv_sf),
             _p(decode_in), _p(mask_lat), _p(z0), _p(noise_init)))
+
+    def lcm_step_levels(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
+                        inv_sf, decode_in, lvl_lat, z0, noise_init, steps, step):
+        """lcm_step_masked() of a soft mask: lvl_lat u8 [hw] holds levels 0 .. 255, `step` is this step's place among
+        the `steps` of the edit; a latent pixel of level v is inside iff v * steps > 255 * (steps - 1 - step)."""
+        self.sync_stream()
+        _chk((lib().fie_lcm_step_levels_f32 if self.f32 else lib().fie_lcm_step_levels)(
+            self.h, _p(eps), eps.shape[-1], nb, float(guidance), _p(latents), _p(noise), hw, float(sab_t), float(s1mab_t), float(c_skip),
+            float(c_out), float(sab_p), float(s1mab_p), _p(model_in), model_in.shape[0] if model_in is not None else 0, float(inv_sf),
+            _p(decode_in), _p(lvl_lat), _p(z0), _p(noise_init), int(steps), int(step)))
 
     def lcm_step(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
                  inv_sf, decode_in):

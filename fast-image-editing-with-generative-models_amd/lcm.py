@@ -43,7 +43,7 @@ class LCMSchedule:
             a_p = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
             s = t * self.timestep_scaling
             steps.append(dict(
-                t=t, last=(i == n - 1),
+                t=t, last=(i == n - 1), index=i - t_start, count=n - t_start,       # the step's place among the plan's: a soft mask's release schedule
                 sqrt_ab=float(np.sqrt(a_t)), sqrt_1mab=float(np.sqrt(1 - a_t)),
                 c_skip=float(self.sigma_data ** 2 / (s ** 2 + self.sigma_data ** 2)),
                 c_out=float(s / np.sqrt(s ** 2 + self.sigma_data ** 2)),

@@ -18,6 +18,8 @@ BLEND_MODES = ("alpha", "multiband")      # blend: the pa
 MAX_BLEND_LEVELS = 6                      # fie_multiband_blend_rgb_u8's bound
 MAX_GROW = 64                             # mask_grow: fie_mask_grow_u8's radius bound, the halo a block stages
 MAX_OUTPAINT = 4096                       # outpaint: fie_outpaint_canvas_rgb_u8's bound on each of the four margins
+MASK_MODES = ("binary", "levels")         # mask_mode: the mask switches the edit, or its greys are per-pixel strengths
+MAX_RAMP = 64                             # mask_ramp (section 21): fie_mask_ramp_u8's radius bound, the halo a block stages
 
 
 def to_l_array(mask, size=None):
@@ -93,6 +95,83 @@ def check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, m
     check_args(mask_blur, paste_back, have_mask)
     return (check_content(masked_content, have_mask), check_blend(blend, blend_levels, have_mask, paste_back or paste_later),
             check_grow(mask_grow, have_mask))
+
+
+def check_levels(mask_mode="binary", mask_ramp=0, mask_grow=0, have_mask=True):
+    """The argument rules of `mask_mode` / `mask_ramp` (soft masks: the mask's grey level as a per-pixel strength; DESIGN.md section 21);
+    returns (mask_mode, mask_ramp as an int).  Both need a mask (an outpaint counts as one).  "levels" reads the greys as passed, so neither
+    `mask_ramp` nor `mask_grow` goes with it: both work on the binarised outline and would discard them.  `mask_ramp` with `mask_grow` is fine:
+    grown first, ramped second."""
+    if not isinstance(mask_mode, str) or mask_mode not in MASK_MODES:
+        raise ValueError(f"mask_mode={mask_mode!r}: one of {', '.join(repr(m) for m in MASK_MODES)}")
+    if isinstance(mask_ramp, (bool, np.bool_)) or not isinstance(mask_ramp, (int, np.integer)) or not 0 <= mask_ramp <= MAX_RAMP:
+        raise ValueError(f"mask_ramp={mask_ramp!r}: an integer in 0..{MAX_RAMP}")
+    if mask_mode != "binary" and not have_mask:
+        raise ValueError(f"mask_mode={mask_mode!r} needs a mask")
+    if mask_ramp != 0 and not have_mask:
+        raise ValueError("mask_ramp needs a mask")
+    if mask_mode == "levels" and mask_ramp != 0:
+        raise ValueError("mask_mode='levels' with mask_ramp: the ramp is built from the mask's outline and would discard its greys")
+    if mask_mode == "levels" and mask_grow != 0:
+        raise ValueError("mask_mode='levels' with mask_grow: the grown mask is binary and would discard the greys")
+    return mask_mode, int(mask_ramp)
+
+
+def level_steps(v, K):
+    """n(v, K): how many of an edit's K steps a latent pixel of level v (0..255) is edited for -- the last n.  n(0) = 0, n(1) = 1, n(255) = K."""
+    return (int(v) * int(K) + 254) // 255
+
+
+def level_inside(v, K, j):
+    """Whether a latent pixel of level v is inside the edit in the blend after step j of K (what fie_lcm_step_levels compares): the same
+    statement as level_steps(v, K) >= K - j."""
+    return int(v) * int(K) > 255 * (int(K) - 1 - int(j))
+
+
+def support_numpy(levels):
+    """S = 255 (V > 0): the binary mask every reader but the latent step takes in a level map's place (fie_mask_support_u8)."""
+    return (np.asarray(levels) > 0).astype(np.uint8) * 255
+
+
+def levels_lat_numpy(levels_e, mask_lat):
+    """fie_mask_levels_u8 restated: levels_e uint8 [H, W] (the level map at the edit size), mask_lat [H/8, W/8] or flat (fie_mask_prep's, of
+    the support) -> uint8 [H/8, W/8]: mask_lat ? max(levels_e[8y, 8x], 1) : 0."""
+    v = np.asarray(levels_e)[::8, ::8]
+    m = np.asarray(mask_lat).reshape(v.shape) != 0
+    return np.where(m, np.maximum(v, 1), 0).astype(np.uint8)
+
+
+def _isqrt(n):
+    """floor(sqrt(n)) of a non-negative int64 array: the float root is a first guess, the integers decide."""
+    n = np.asarray(n, np.int64)
+    s = np.sqrt(n.astype(np.float64)).astype(np.int64)
+    s = np.where(s * s > n, s - 1, s)
+    return np.where((s + 1) * (s + 1) <= n, s + 1, s)
+
+
+def ramp_numpy(mask_l, r):
+    """fie_mask_ramp_u8 restated: uint8 [H, W] mask, r in 1..64 -> the level map.  m = mask_l >= 128; D2(p) the smallest
+    squared distance from p to a pixel q of the image with !m(q); V = 0 where !m, 255 where no such q lies within distance < r (a mask of all
+    ones: no q at all), else isqrt(65025 D2) // r.  Integers only: per row the distance to the row's nearest unset pixel (saturated at r), then
+    D2 = min over dy in -(r-1) .. r-1 of dy^2 + that distance^2 in row y + dy; rows outside the image hold no unset pixel."""
+    m = np.asarray(mask_l) >= 128
+    r = int(r)
+    if not 1 <= r <= MAX_RAMP:
+        raise ValueError(f"ramp radius {r!r}: an integer in 1..{MAX_RAMP}")
+    h, w = m.shape
+    far = r * r
+    if m.all():                                           # no unset pixel anywhere: nothing to measure a distance to
+        return np.full((h, w), 255, np.uint8)
+    idx = np.arange(w, dtype=np.int64)[None, :]
+    left = idx - np.maximum.accumulate(np.where(~m, idx, -4 * MAX_RAMP), axis=1)                          # to the nearest unset pixel at or left of x
+    right = np.minimum.accumulate(np.where(~m, idx, w + 4 * MAX_RAMP)[:, ::-1], axis=1)[:, ::-1] - idx    # at or right of x
+    hx = np.full((h + 2 * r, w), r, np.int64)             # rows above and below the image: nothing unset
+    hx[r:r + h] = np.minimum(np.minimum(left, right), r)
+    d2 = np.full((h, w), far, np.int64)
+    for dy in range(-r + 1, r):
+        d2 = np.minimum(d2, dy * dy + hx[r + dy:r + dy + h] ** 2)
+    v = np.where(d2 >= far, 255, np.minimum(255, _isqrt(65025 * d2) // r))
+    return np.where(m, v, 0).astype(np.uint8)
 
 
 def check_outpaint(outpaint):

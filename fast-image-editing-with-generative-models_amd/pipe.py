@@ -33,6 +33,16 @@ class DeviceOutput:
         self.out, self.extra = out, extra
 
 
+class MaskLevels:
+    """A soft mask at the edit size as the pair its readers take: `levels` u8 [H, W], what the latent step reads through
+    fie_mask_levels_u8, and `support` u8 [H, W], what every other reader of a mask reads by its own rule.  A caller that resizes a level map
+    resizes the two separately (FastEditor); passed as `mask_image` with mask_mode="levels"."""
+    __slots__ = ("support", "levels")
+
+    def __init__(self, support, levels):
+        self.support, self.levels = support, levels
+
+
 class HipImg2ImgPipeline:
     def __init__(self, ctx, cfgs, sds, tokenizers=None, sched_cfg=None, noise_dtype=None, weight_dtype="f16"):
         """cfgs / sds: dicts with keys unet, controlnet, vae, clip_l, clip_g (configs / diffusers-named state dicts).
@@ -139,7 +149,7 @@ class HipImg2ImgPipeline:
     def prepare(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                 num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
                 mask_image=None, mask_blur=0, paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False,
-                mask_grow=0):
+                mask_grow=0, mask_mode="binary", mask_ramp=0):
         """`image` / `control_image`: PIL images, or u8 [H, W, 3] tensors already on the device (FastEditor.edit keeps the
         resized source and its device-side Canny map in HBM instead of bouncing them through PIL).  `mask_image` (additive, diffusers'
         name): restricts the edit to its white region -- a PIL image, a uint8 / bool [H, W] array, or a u8 [H, W]
@@ -152,20 +162,40 @@ class HipImg2ImgPipeline:
         (FastEditor's source-size back end): a "multiband" job with paste_back=False then returns the blended image B uncomposited.
         `mask_grow` (additive; a non-zero value needs a mask): the mask grown (> 0) or shrunk (< 0) by the exact Euclidean disk of that many of its
         pixels, -64 .. 64, on the device before anything else reads it: the call equals the one with the grown mask passed in (DESIGN.md section
-        16).  0 launches nothing and passes the mask on as it is."""
+        16).  0 launches nothing and passes the mask on as it is.
+        `mask_mode` / `mask_ramp` (additive; both need a mask): a soft mask.  "levels" reads the mask's greys as a
+        per-pixel strength V: a latent pixel of level v is held on the source's trajectory and released into the edit for the last
+        (v K + 254) // 255 of the edit's K steps -- 255 is edited as a binary mask's white, 0 never; everything else that reads a mask (the
+        paste-back and its feather, `masked_content`, `blend`) reads the support 255 (V > 0) in its place.  `mask_ramp` = r in 1..64 builds V
+        from the binary mask's outline on the device (after `mask_grow`): 0 outside, floor(255 d / r) up to 255 inside, d the distance to the
+        nearest pixel outside the mask, in pixels of the mask as passed.  The two do not combine, nor does "levels" with `mask_grow`.  A
+        `MaskLevels(support, levels)` pair of u8 [H, W] device tensors is taken as it is (FastEditor resizes the two separately)."""
+        grow = hmask.check_grow(mask_grow, mask_image is not None)
         return self._prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                              controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content,
-                             hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later),
-                             hmask.check_grow(mask_grow, mask_image is not None))
+                             hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later), grow,
+                             hmask.check_levels(mask_mode, mask_ramp, grow, mask_image is not None))
 
-    def _mask_job(self, mask_image, mask_blur, paste_back, h, w, grow=0):
+    def _mask_job(self, mask_image, mask_blur, paste_back, h, w, grow=0, levels=("binary", 0)):
         """Mask tensors of one image: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back, the edit-size L mask
-        u8 [1, h, w]).  The mask is binarised / downsampled / feathered on the device (fie_mask_prep) on the current stream, in front of the job;
-        with `grow` != 0 it is grown or shrunk by that radius first (fie_mask_grow_u8, same place), and the L mask returned is the grown one."""
+        u8 [1, h, w], lvl_lat u8 [1, h/8 * w/8] or None).  The mask is binarised / downsampled / feathered on the device (fie_mask_prep) on the
+        current stream, in front of the job; with `grow` != 0 it is grown or shrunk by that radius first (fie_mask_grow_u8, same place), and the L
+        mask returned is the grown one.  `levels` = check_levels()'s (mask_mode, mask_ramp), a soft mask: the level map V is
+        the mask itself ("levels"), fie_mask_ramp_u8 of the (grown) mask (mask_ramp > 0) or a MaskLevels pair's; the L mask returned and prepared
+        is its support, and lvl_lat holds the latent levels (fie_mask_levels_u8), which the latent step alone reads."""
         r = hmask.check_args(mask_blur, paste_back, mask_image is not None)
         if mask_image is None:
-            return None, None, None
-        if torch.is_tensor(mask_image):
+            return None, None, None, None
+        mode, ramp = levels
+        pair = isinstance(mask_image, MaskLevels)         # support and levels as the caller resized them: nothing to grow, ramp or derive
+        if pair:
+            if mode != "levels":
+                raise ValueError("a MaskLevels pair is a level map: it needs mask_mode='levels'")
+            for t in (mask_image.support, mask_image.levels):
+                if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != (h, w):
+                    raise ValueError(f"a MaskLevels pair holds two u8 [{h}, {w}] tensors")
+            lm, lv = (t.to(self.ctx.device).contiguous() for t in (mask_image.support, mask_image.levels))
+        elif torch.is_tensor(mask_image):
             if mask_image.dim() != 2 or mask_image.dtype != torch.uint8:
                 raise ValueError("a mask tensor must be u8 [H, W]")
             if tuple(mask_image.shape) != (h, w):
@@ -176,12 +206,17 @@ class HipImg2ImgPipeline:
         with self.eager_lock:                             # the context's stream binding is shared by the threads of in-flight edits
             if grow:
                 lm = self.ctx.mask_grow(lm, grow)
+            if not pair:
+                lv = self.ctx.mask_ramp(lm, ramp) if ramp else lm if mode == "levels" else None
+                if lv is not None:
+                    lm = self.ctx.mask_support(lv)
             m_px, m_lat = self.ctx.mask_prep(lm, r)
-        return m_lat[None], (m_px[None] if paste_back else None), lm[None]
+            lvl = self.ctx.mask_levels(lv, m_lat) if lv is not None else None
+        return m_lat[None], (m_px[None] if paste_back else None), lm[None], None if lvl is None else lvl[None]
 
     def _prepare(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                  controlnet_conditioning_scale, generator, mask_image=None, mask_blur=0, paste_back=True, masked_content="original",
-                 blend=("alpha", 4), grow=0):
+                 blend=("alpha", 4), grow=0, levels=("binary", 0)):
         """Host side of one call: argument checks, tokenisation, RNG draws (in upstream order: posterior sample, init
         noise, one per non-final step) and the H2D copies.  Returns the device-resident job for run_device()."""
         ctx = self.ctx
@@ -196,7 +231,7 @@ class HipImg2ImgPipeline:
         if h % 8 or w % 8:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {h} and {w}.")
         content = hmask.check_content(masked_content, mask_image is not None)
-        mask_lat, mask_px, mask_l = self._mask_job(mask_image, mask_blur, paste_back, h, w, grow)
+        mask_lat, mask_px, mask_l, lvl_lat = self._mask_job(mask_image, mask_blur, paste_back, h, w, grow, levels)
         steps = self.scheduler.plan(num_inference_steps, strength)
         if not steps:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of "
@@ -231,6 +266,7 @@ class HipImg2ImgPipeline:
             time_ids=const[0], t_dev=const[1],
             noises=[self._randn((1, 4, lh, lw), generator) for _ in range(n_noise)],
             mask_lat=mask_lat, mask_px=mask_px, mask_cfg=None if mask_lat is None else (float(mask_blur), bool(paste_back)),
+            **({} if lvl_lat is None else dict(lvl_lat=lvl_lat)),         # a soft mask's latent levels; none: the job is what it was
             **self._content_job(content, mask_l, mask_lat), **self._blend_job(blend, mask_l))
 
     @staticmethod
@@ -254,14 +290,16 @@ class HipImg2ImgPipeline:
 
     def prepare_batch(self, prompts, negative_prompts, images, control_images, strength=0.8, num_inference_steps=4,
                       guidance_scale=1.5, controlnet_conditioning_scale=0.5, generators=None, mask_image=None, mask_blur=0,
-                      paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0):
+                      paste_back=True, *, masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0,
+                      mask_mode="binary", mask_ramp=0):
         """[additive] n independent edits as ONE device job (BASELINE config "batch=8"): the UNet / ControlNet / CLIP run
         at batch n * nb, the VAE per image.  Rows are image-major ([img0 uncond, img0 cond, img1 uncond, ...]); each
         image keeps its own generator, so image i of a batch draws exactly the noise a single call with that generator
         draws (upstream: a list of generators, one per prompt).  `mask_image`: None, or one mask per image (None in the
         list = edit everywhere).  `masked_content`: one mode for the call (prepare()); an image without a mask is edited as ever.  `blend` / `blend_levels` /
         `paste_later`: prepare()'s, one value for the call; an image without a mask comes out as without the keyword.  `mask_grow`: prepare()'s, one
-        radius for the call; an image without a mask is untouched."""
+        radius for the call; an image without a mask is untouched.  `mask_mode` / `mask_ramp`: prepare()'s, one value for the call; an image without a
+        mask is untouched (its latent levels are 255 everywhere)."""
         n = len(prompts)
         if not (n == len(images) == len(control_images)) or n == 0:
             raise ValueError("prompts, images and control_images must be non-empty lists of one length")
@@ -273,6 +311,7 @@ class HipImg2ImgPipeline:
         content = hmask.check_content(masked_content, masked)
         blend = hmask.check_blend(blend, blend_levels, masked, paste_back or paste_later)
         grow = hmask.check_grow(mask_grow, masked)
+        levels = hmask.check_levels(mask_mode, mask_ramp, grow, masked)
         negative_prompts = negative_prompts or [""] * n
         generators = generators or [None] * n
         jobs = [self._prepare(prompts[i], negative_prompts[i], images[i], control_images[i], strength, num_inference_steps,
@@ -280,7 +319,8 @@ class HipImg2ImgPipeline:
                               mask_blur if masks[i] is not None else 0, paste_back,
                               content if masks[i] is not None else "original",
                               blend if masks[i] is not None else ("alpha", 4),
-                              grow if masks[i] is not None else 0) for i in range(n)]
+                              grow if masks[i] is not None else 0,
+                              levels if masks[i] is not None else ("binary", 0)) for i in range(n)]
         if any(j["hw"] != jobs[0]["hw"] for j in jobs):
             raise ValueError("all images of a batch must have one size")
         if masked:                                        # an image without a mask edits everywhere: an all-ones mask
@@ -290,6 +330,8 @@ class HipImg2ImgPipeline:
                     j["mask_lat"] = torch.ones((1, (h // 8) * (w // 8)), device=self.ctx.device, dtype=torch.uint8)
                     j["mask_px"] = torch.ones((1, h, w), device=self.ctx.device, dtype=torch.float32) if paste_back else None
                     j["mask_cfg"] = (float(mask_blur), bool(paste_back))
+                    if levels != ("binary", 0):
+                        j["lvl_lat"] = torch.full((1, (h // 8) * (w // 8)), 255, device=self.ctx.device, dtype=torch.uint8)
                     # no mask of its own: an empty hole -- nothing filled, no edge cleared, no latent replaced
                     j.update(self._content_job(content, torch.zeros((1, h, w), device=self.ctx.device, dtype=torch.uint8),
                                                torch.zeros((1, (h // 8) * (w // 8)), device=self.ctx.device, dtype=torch.uint8)))
@@ -313,19 +355,21 @@ class HipImg2ImgPipeline:
 
     def prepare_sweep(self, prompt, negative_prompt="", image=None, control_image=None, strengths="all", num_inference_steps=4,
                       guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None, mask_image=None, mask_blur=0, paste_back=True, *,
-                      masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0):
+                      masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0, mask_mode="binary", mask_ramp=0):
         """[additive] A strength sweep as ONE device job: one image, one prompt pair, and the k variants of
         fie_amd/sweep.py: variants(num_inference_steps, strengths) as the k "images" of the job, strongest first.  Everything that does not depend
         on the strength runs once (tokenisation, both text encoders, the mask preparation, the fill, the VAE encode, the edge-map embedding); the
         UNet and the ControlNet run each loop step on the rows of the variants that have joined the loop by then -- a leading slice, rows being
         image-major as in prepare_batch().  One generator: variant i consumes the noise a single call with that generator and strength draws (its
-        stream is a prefix of the longest variant's).  The other arguments are prepare()'s.  A sweep of ONE variant is the single-image job."""
+        stream is a prefix of the longest variant's).  A soft mask's level map is shared: its support does not depend on the step count, and every
+        variant releases a level by its own K.  The other arguments are prepare()'s.  A sweep of ONE variant is the single-image job."""
         from . import sweep as hsweep
         vs = hsweep.variants(num_inference_steps, strengths)
+        grow = hmask.check_grow(mask_grow, mask_image is not None)
         job = self._prepare(prompt, negative_prompt, image, control_image, vs[0][1][0], num_inference_steps, guidance_scale,
                             controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content,
-                            hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later),
-                            hmask.check_grow(mask_grow, mask_image is not None))
+                            hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later), grow,
+                            hmask.check_levels(mask_mode, mask_ramp, grow, mask_image is not None))
         if len(vs) == 1:
             return job                                    # the single-image job (and its graph)
         plans = [self.scheduler.plan(num_inference_steps, v[1][0]) for v in vs]
@@ -406,6 +450,7 @@ class HipImg2ImgPipeline:
         # 1024^2 VAE tensors of a batch would cross the 2 GiB operand limit of the buffer-load kernels, and gain nothing)
         per = len(job["noises"]) // n                     # noise tensors per image
         mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")     # a masked edit
+        lvl_lat = job.get("lvl_lat")                      # a soft mask's latent levels: the masked step's twin reads them
         latents = torch.empty((n, hw, 4), device=dev, dtype=torch.float32)
         z0 = torch.empty((n, hw, 4), device=dev, dtype=torch.float32) if mask_lat is not None else None
         model_in = torch.empty((n * nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
@@ -448,10 +493,14 @@ class HipImg2ImgPipeline:
                     ctx.lcm_step(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
                                  st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
                                  1.0 / sf, decode_in[i:i + 1])
-                else:
+                elif lvl_lat is None:
                     ctx.lcm_step_masked(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
                                         st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
                                         1.0 / sf, decode_in[i:i + 1], mask_lat[i], z0[i], job["noises"][i * per + 1])
+                else:
+                    ctx.lcm_step_levels(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
+                                        st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
+                                        1.0 / sf, decode_in[i:i + 1], lvl_lat[i], z0[i], job["noises"][i * per + 1], st["count"], st["index"])
             next_noise += 1
             self._mark("lcm_step")
         # 8-9. decode + postprocess
@@ -512,7 +561,7 @@ class HipImg2ImgPipeline:
             cond_emb = self.controlnet.cond_embedding(ctx.pixels_in(ctl, False)).repeat_interleave(k * nb, dim=0)
             tb0 = (self.unet.time_rowbias(job["t_dev"][0]), self.controlnet.time_rowbias(job["t_dev"][0]))
         text_len = text.shape[0] // (k * nb)
-        mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")
+        mask_lat, mask_px, lvl_lat = job.get("mask_lat"), job.get("mask_px"), job.get("lvl_lat")
         latents = torch.empty((k, hw, 4), device=dev, dtype=torch.float32)
         z0 = torch.empty((hw, 4), device=dev, dtype=torch.float32) if mask_lat is not None else None
         model_in = torch.empty((k * nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
@@ -552,10 +601,14 @@ class HipImg2ImgPipeline:
                     ctx.lcm_step(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
                                  st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
                                  1.0 / sf, decode_in[i:i + 1])
-                else:
+                elif lvl_lat is None:
                     ctx.lcm_step_masked(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
                                         st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
                                         1.0 / sf, decode_in[i:i + 1], mask_lat[0], z0, noises[1])
+                else:                                     # the variant's own K and j: it releases a level by its own step count
+                    ctx.lcm_step_levels(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
+                                        st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
+                                        1.0 / sf, decode_in[i:i + 1], lvl_lat[0], z0, noises[1], st["count"], st["index"])
             self._mark("lcm_step")
         dec = (lambda z: cabi.vae_decode(self.vae, z)) if self.cpp_walks else self.vae.decode
         if job.get("blend"):
@@ -649,7 +702,8 @@ class HipImg2ImgPipeline:
 
     _TENSOR_KEYS = ("ids_l", "ids_g", "eos_rows", "img_u8", "ctl_u8", "time_ids")
     # mask_l, content_lat: a masked-content mode's; blend_l: the multi-band blend's (section 15)
-    _MASK_KEYS = ("mask_lat", "mask_px", "mask_l", "content_lat", "blend_l")
+    # lvl_lat: a soft mask's latent levels (section 21)
+    _MASK_KEYS = ("mask_lat", "mask_px", "mask_l", "content_lat", "blend_l", "lvl_lat")
 
     def run_device_graphed(self, job, slot=0):
         """run_device() replayed from a hipGraph: the ~2 500 launches of one edit are captured once per
@@ -659,8 +713,9 @@ class HipImg2ImgPipeline:
         flight on different streams of one GPU."""
         base = (job["hw"], job["nb"], tuple(st["t"] for st in job["steps"]), job["guidance"], job["cn_scale"], slot, job.get("n", 1))
         if job.get("mask_lat") is not None:              # masked: (masked, mask_blur, paste_back); an unmasked key is what it was
-            # + the masked-content mode, unless "original"; + ("multiband", levels), unless the blend is "alpha"
-            base = base + ((True,) + job["mask_cfg"] + ((job["content"],) if job.get("content") else ()) + ((job["blend"],) if job.get("blend") else ()),)
+            # + the masked-content mode, unless "original"; + ("multiband", levels), unless the blend is "alpha"; + "levels" for a soft mask
+            base = base + ((True,) + job["mask_cfg"] + ((job["content"],) if job.get("content") else ()) + ((job["blend"],) if job.get("blend") else ())
+                           + (("levels",) if job.get("lvl_lat") is not None else ()),)
         if job.get("sweep"):                             # a strength sweep: + the step counts of its variants
             base = base + (("sweep", job["sweep"]),)
         # A forked graph owns extra runtime streams; past ~8 such graphs in one process new ones start sharing hardware queues
@@ -793,7 +848,8 @@ class HipImg2ImgPipeline:
     def __call__(self, prompt, negative_prompt="", image=None, control_image=None, strength=0.8,
                  num_inference_steps=4, guidance_scale=1.5, controlnet_conditioning_scale=0.5, generator=None,
                  output_type="pil", slot=0, post_check=None, mask_image=None, mask_blur=0, paste_back=True, after_device=None, *,
-                 masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0, **unused):
+                 masked_content="original", blend="alpha", blend_levels=4, paste_later=False, mask_grow=0, mask_mode="binary", mask_ramp=0,
+                 **unused):
         """`slot` (additive): independent hipGraph instance + stream, so that several calls may be in flight from different
         host threads on one GPU (graph mode only).  `post_check` (additive): a callable run after the result has reached the host
         (the stream is idle then); when it returns True the device-resident inputs have changed meanwhile and the device job is run
@@ -802,7 +858,8 @@ class HipImg2ImgPipeline:
         no host wait in front of the edit, a repeated job in the rare case that they had not.  `mask_image` / `mask_blur` / `paste_back`
         (additive): a mask-restricted edit (prepare(); a list of masks for a batch call); `masked_content`: what it starts from inside the mask
         (prepare()); `blend` / `blend_levels` / `paste_later`: how the paste-back meets the source (prepare()); `mask_grow`: the mask grown or
-        shrunk by an exact disk before anything reads it (prepare()).  `after_device` (additive): a callable given the u8 result
+        shrunk by an exact disk before anything reads it (prepare()); `mask_mode` / `mask_ramp`: a soft mask, the greys as per-pixel strength
+        (prepare()).  `after_device` (additive): a callable given the u8 result
         while it is still on the device, on the slot's stream behind the device job and outside its graph; it may queue more work there (FastEditor
         scores the edit) and whatever it returns comes back as `.extra`, complete once the image has reached the host.  A hook that returns a
         `DeviceOutput` replaces the image: its tensor(s) take the final device-to-host copy (FastEditor's full-resolution back end).
@@ -815,7 +872,8 @@ class HipImg2ImgPipeline:
         with torch.cuda.stream(st):
             out = self._call(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                              controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back), after_device,
-                             masked_content, dict(blend=blend, blend_levels=blend_levels, paste_later=paste_later, mask_grow=mask_grow))
+                             masked_content, dict(blend=blend, blend_levels=blend_levels, paste_later=paste_later, mask_grow=mask_grow,
+                                                  mask_mode=mask_mode, mask_ramp=mask_ramp))
         caller.wait_stream(st)
         return out
 

@@ -617,6 +617,38 @@ int fie_multiband_blend_rgb_u8(fie_ctx* ctx, const uint8_t* edit, const uint8_t*
  *      workspace, no atomics, no block waits for another. */
 int fie_mask_grow_u8(fie_ctx* ctx, const uint8_t* mask_l, int H, int W, int radius, uint8_t* out);
 
+/* ---- Soft masks: the mask's grey level as a per-pixel strength.  A level map V is u8, 0 = never edited, 255 = edited as
+ * a binary mask's white; its support S = 255 (V > 0) is what every other reader of a mask takes in the mask's place.
+ *   fie_lcm_step_levels[_f32]   fie_lcm_step_masked with lvl_lat u8 [H*W] (latent pixels, levels 0 .. 255) in place of mask_lat and the step's place:
+ *      steps = K in 1 .. 255, the number of steps of the edit, and step = j in 0 .. K - 1.  After step j a latent pixel of level v is inside
+ *      iff v K > 255 (K - 1 - j): it is edited for the last (v K + 254) / 255 of the K steps -- 0 for v = 0, 1 for v = 1, K for v = 255.  An
+ *      inside pixel keeps the bits fie_lcm_step writes, an outside one takes what fie_lcm_step_masked gives it.  fie_lcm_step_masked is the
+ *      case of levels 0 / 1 with K = 1, j = 0; a 0 / 255 map is the binary masked edit at every K.
+ *   fie_mask_levels_u8   levels_e u8 [H, W] (the level map at the edit size), mask_lat u8 [H/8 * W/8] (fie_mask_prep's, of the support); H, W
+ *      positive multiples of 8.  lvl_lat[y][x] = mask_lat[y][x] ? max(levels_e[8y][8x], 1) : 0: the latent support is mask_lat's bit for bit.
+ *      One launch.
+ *   fie_mask_support_u8  levels u8 [n], n >= 1 -> out u8 [n] = 255 where levels > 0, else 0 (out may be levels).  One launch.
+ *   fie_mask_ramp_u8     a level map from a binary mask's outline.  mask_l u8 [H, W], any H, W >= 1 with H * W < 2^31, radius r in 1 .. 64;
+ *      out_levels u8 [H, W], every byte written; it overlaps no byte of mask_l (blocks read each other's halo).  With m(q) = (mask_l(q) >= 128)
+ *      and D2(p) the smallest (px - qx)^2 + (py - qy)^2 over the pixels q of the image with !m(q):
+ *        out(p) = 0 where !m(p); 255 where no such q lies within distance < r (a mask of all ones included);
+ *        else isqrt(65025 D2(p)) / r = floor(255 sqrt(D2(p)) / r).
+ *      The image border is not an edge (fie_mask_grow_u8's rule for the erosion); every set pixel gets at least 255 / r >= 3, so the map's support
+ *      is the binarised mask.  Integers only, exact (fie_amd/mask.py: ramp_numpy restates it).  FIE_EINVAL for anything else.  One launch of one
+ *      block per 64 x 64 tile, staged and scanned as fie_mask_grow_u8's ((64 + 2r)^2 bytes of LDS); the row pass takes the minimum of
+ *      g^2 + dx^2 over the column distances g.  Asynchronous on the ctx stream; no workspace, no atomics, no block waits for another. */
+int fie_lcm_step_levels(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents,
+                        const float* noise, int64_t HW, float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out,
+                        float sqrt_ab_prev, float sqrt_1mab_prev, void* model_in, int copies, float inv_scaling,
+                        void* decode_in, const uint8_t* lvl_lat, const float* z0, const float* noise_init, int steps, int step);
+int fie_lcm_step_levels_f32(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents,
+                            const float* noise, int64_t HW, float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out,
+                            float sqrt_ab_prev, float sqrt_1mab_prev, void* model_in, int copies, float inv_scaling,
+                            void* decode_in, const uint8_t* lvl_lat, const float* z0, const float* noise_init, int steps, int step);
+int fie_mask_levels_u8(fie_ctx* ctx, const uint8_t* levels_e, const uint8_t* mask_lat, int H, int W, uint8_t* lvl_lat);
+int fie_mask_support_u8(fie_ctx* ctx, const uint8_t* levels, int64_t n, uint8_t* out);
+int fie_mask_ramp_u8(fie_ctx* ctx, const uint8_t* mask_l, int H, int W, int radius, uint8_t* out_levels);
+
 /* ---- The canvas of an outpainting edit: the source made larger by four margins, and the mask that selects what is new.
  *   fie_outpaint_canvas_rgb_u8   src u8 [H, W, 3], mask_l u8 [H, W] or NULL, H, W >= 1; left, top, right, bottom in 0 .. 4096, not all 0.  With
  *      Hc = top + H + bottom, Wc = left + W + right and Hc * Wc < 2^31:

@@ -107,6 +107,17 @@ def add_grow_args(p):
     return p
 
 
+def add_levels_args(p):
+    """[additive] soft masks.  Kept apart from build_parser() for the same reason as add_mask_args."""
+    p.add_argument("--mask_mode", type=str, default="binary", choices=["binary", "levels"],
+                   help="[additive] with --use_mask: 'levels' reads each mask's greys as a per-pixel strength (255 edited as white, lower levels "
+                        "released into the edit for the last steps only, 0 never); not with --mask_ramp or --mask_grow")
+    p.add_argument("--mask_ramp", type=int, default=0, choices=range(0, 65), metavar="N",
+                   help="[additive] with --use_mask: a soft mask from each binary mask's outline: the strength ramps up over N pixels of the mask "
+                        "(the 512x512 benchmark image) inward from its outline, 0..64; --mask_grow N in front moves the ramp outward")
+    return p
+
+
 def outpaint_arg(text):
     """argparse type of --outpaint: 'L,T,R,B' -> (left, top, right, bottom) (fie_amd/mask.py: parse_outpaint)."""
     import fie_amd  # noqa: F401
@@ -285,7 +296,7 @@ def sweep_kwargs(args):
 def full_parser():
     """The parser main() reads: build_parser() and every additive group."""
     return add_sweep_args(add_tile_args(add_lpips_args(add_dino_args(add_clip_args(add_metrics_args(add_region_args(add_resolution_args(add_outpaint_args(
-        add_grow_args(add_blend_args(add_mask_args(build_parser()))))))))))))
+        add_levels_args(add_grow_args(add_blend_args(add_mask_args(build_parser())))))))))))))
 
 
 METRIC_KEYS = ("ssim", "psnr", "mse", "bg_ssim", "bg_psnr", "bg_mse", "clip_score", "clip_score_edited", "dino_distance", "lpips", "bg_lpips")
@@ -395,6 +406,11 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
         if not masked:
             raise ValueError("--mask_grow needs --use_mask")
         extra = dict(extra, mask_grow=mask_grow)
+    mask_mode, mask_ramp = getattr(args, "mask_mode", "binary"), getattr(args, "mask_ramp", 0)
+    if mask_mode != "binary" or mask_ramp:
+        if not masked:
+            raise ValueError("--mask_mode levels and --mask_ramp need --use_mask")
+        extra = dict(extra, mask_mode=mask_mode, mask_ramp=mask_ramp)
     sweep = sweep_kwargs(args)                     # --auto_strength: one edit_sweep() per image in place of edit()
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
@@ -529,6 +545,10 @@ def main(argv=None):
         parser.error("--blend multiband needs --use_mask")
     if args.mask_grow and not masked:
         parser.error("--mask_grow needs --use_mask")
+    if (args.mask_mode != "binary" or args.mask_ramp) and not masked:
+        parser.error("--mask_mode levels and --mask_ramp need --use_mask")
+    if args.mask_mode == "levels" and (args.mask_ramp or args.mask_grow):
+        parser.error("--mask_mode levels does not go with --mask_ramp or --mask_grow: both work on the outline and would discard the greys")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets

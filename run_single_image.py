@@ -69,6 +69,12 @@ def build_parser():
     a("--mask_grow", type=int, default=0, choices=range(-64, 65), metavar="N",
       help="[additive] with --mask: grow (N > 0) or shrink (N < 0) the mask by an exact disk of N pixels of the mask (the input image's pixels), "
            "-64..64, before anything else reads it")
+    a("--mask_mode", type=str, default="binary", choices=["binary", "levels"],
+      help="[additive] with --mask: 'levels' reads the mask's greys as a per-pixel strength (255 edited as white, lower levels released into the "
+           "edit for the last steps only, 0 never); not with --mask_ramp or --mask_grow")
+    a("--mask_ramp", type=int, default=0, choices=range(0, 65), metavar="N",
+      help="[additive] with --mask: a soft mask from the binary mask's outline: the strength ramps up over N pixels of the mask (the input image's "
+           "pixels) inward from its outline, 0..64; --mask_grow N in front moves the ramp outward")
     a("--outpaint", type=outpaint_arg, default=None, metavar="L,T,R,B",
       help="[additive] outpainting: make the picture larger by L, T, R, B pixels (left, top, right, bottom; each 0..4096, not all 0) and let the "
            "model invent the new border.  The border is the mask (a --mask is carried into it), so --mask_grow, --mask_blur, --masked_content, "
@@ -201,6 +207,10 @@ def main(argv=None):
         parser.error("--blend multiband needs --mask and the paste-back")
     if args.mask_grow and not masked:
         parser.error("--mask_grow needs --mask")
+    if (args.mask_mode != "binary" or args.mask_ramp) and not masked:
+        parser.error("--mask_mode levels and --mask_ramp need --mask")
+    if args.mask_mode == "levels" and (args.mask_ramp or args.mask_grow):
+        parser.error("--mask_mode levels does not go with --mask_ramp or --mask_grow: both work on the outline and would discard the greys")
     if args.resolution != "square":
         import fie_amd  # noqa: F401
         from fie_amd import buckets
@@ -253,6 +263,9 @@ def main(argv=None):
         if args.mask_grow:
             extra.update(mask_grow=args.mask_grow)
             print(f"      Mask grown by: {args.mask_grow} px")
+        if args.mask_mode != "binary" or args.mask_ramp:
+            extra.update(mask_mode=args.mask_mode, mask_ramp=args.mask_ramp)
+            print(f"      Soft mask: {'the greys as levels' if args.mask_mode == 'levels' else f'ramp over {args.mask_ramp} px'}")
     if args.resolution != "square":
         extra.update(resolution=args.resolution)
     if args.region == "mask":

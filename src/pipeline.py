@@ -24,7 +24,7 @@ from fie_amd import mask as hmask
 from fie_amd import metrics as hmetrics
 from fie_amd import region as hregion
 from fie_amd import tiles as htiles
-from fie_amd.pipe import DeviceOutput, HipImg2ImgPipeline
+from fie_amd.pipe import DeviceOutput, HipImg2ImgPipeline, MaskLevels
 
 
 class FastEditor:
@@ -181,7 +181,8 @@ class FastEditor:
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
              paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
-             blend="alpha", blend_levels=4, mask_grow=0, outpaint=None, tiles=None, tile_overlap=128, tile_batch=4):
+             blend="alpha", blend_levels=4, mask_grow=0, outpaint=None, tiles=None, tile_overlap=128, tile_batch=4, mask_mode="binary",
+             mask_ramp=0):
         """Edit `image` (PIL RGB) following `prompt`, structure preserved through Canny edges (reference :212-274).
         [additive] `mask` (a PIL image or a uint8 / bool [H, W] array of the image's size, white = edit): only that region changes -- the
         latents outside it follow the source's trajectory and, with `paste_back` (default), the output outside it is the resized source byte
@@ -248,7 +249,20 @@ class FastEditor:
         a mask and `paste_back` every byte outside the mask is the source's.  `metrics=True` scores (source, output).  Source and mask are
         uploaded once, the tiles are device slices, the blend is one HIP op behind the last job (csrc/tile_blend.hip) and the only image that
         crosses to the host is the result.  `resolution`, `region`, `outpaint` and output_size="edit" with tiles are a
-        ValueError; None (default) changes nothing."""
+        ValueError; None (default) changes nothing.
+        [additive] `mask_mode` ("binary" / "levels") and `mask_ramp` (an integer in 0..64); both need a mask: a soft mask, the mask's grey level
+        as a per-pixel strength.  With "levels" the mask's greys V are read as they are: 255 is edited as a binary mask's
+        white, 0 never, and a pixel of level v between is held on the source's trajectory and released into the edit for the last
+        (v K + 254) // 255 of the edit's K steps only -- a face and its background, or an object and its shadow, get different strengths inside
+        one image, and the seam of the edit stops being a step in latent space.  Only the latent steps read the levels; the paste-back and its
+        feather, `masked_content`, `blend`, output_size="source", the box of region="mask", `bg_*` / `clip_score_edited` / `bg_lpips` read the
+        support 255 (V > 0) where they read the mask, each by its own rule.  `mask_ramp` = r >= 1 builds V from a binary mask's outline on the
+        device: 0 outside the mask, floor(255 d / r) clipped to 255 inside, d the distance to the nearest pixel outside the mask -- the ramp runs
+        inward, the image border is not an edge, and `mask_grow=r` in front of it (grown first, ramped second) moves it outward.  r counts pixels
+        of the mask as passed, that is of the source image, as `mask_grow` does: on a large source the edit runs at a fraction of that size and the
+        recipe is region="mask", so that the ramp spans more than a latent pixel or two.  "levels" with `mask_ramp` or with `mask_grow` is a
+        ValueError (both work on the outline and would discard the greys).  A region and tiles ramp the whole mask first and crop second.  The
+        defaults launch nothing and change nothing."""
         tiles, tile_overlap, tile_batch = htiles.check(tiles, tile_overlap, tile_batch)
         kw = dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                   controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
@@ -258,27 +272,33 @@ class FastEditor:
             self._check_tiled(resolution, region, outpaint, output_size)
             masked = mask is not None
             grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, masked)[2]
+            kw["levels"] = hmask.check_levels(mask_mode, mask_ramp, grow, masked)
             return self._edit_tiled(image, prompt, negative_prompt, htiles.plan(image.size, tiles, tile_overlap), tile_batch,
                                     hmask.to_l_array(mask, image.size) if masked else None, grow, metrics, kw)
         full = hregion.check_output(output_size, region)
         margins = hmask.check_outpaint(outpaint)
         masked = mask is not None or margins is not None          # the new border is a mask of its own
         grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, masked)[2]
+        kw["levels"] = levels = hmask.check_levels(mask_mode, mask_ramp, grow, masked)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
         if region is not None and margins is not None:            # a region crops on the host: the canvas comes back once, the rest is the call on it
             canvas, canvas_mask = self._outpaint_host(image, mask_l, margins)
             return self.edit(Image.fromarray(canvas), prompt, negative_prompt, strength, num_inference_steps, guidance_scale,
                              controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold, seed, canvas_mask, mask_blur, paste_back,
                              resolution=resolution, metrics=metrics, output_size=output_size, region=region, region_padding=region_padding,
-                             masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow)
+                             masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow, mask_mode=levels[0],
+                             mask_ramp=levels[1])
         if region is not None:
             if grow:        # grown first, cropped second: the box of "mask" is the grown mask's, and pixels outside an explicit box reach into it
                 mask_l = self._grow_host(mask_l, grow)
-            box = hregion.resolve(region, image.size, mask_l, region_padding, resolution)
+            if levels[1]:   # ramped whole, cropped second: the crop carries its levels, and the box of "mask" comes from their support
+                mask_l = self._ramp_host(mask_l, levels[1])
+            soft = levels != ("binary", 0)
+            box = hregion.resolve(region, image.size, hmask.support_numpy(mask_l) if soft else mask_l, region_padding, resolution)
             res = self.edit(image.crop(box), prompt, negative_prompt, strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
                             canny_low_threshold, canny_high_threshold, seed, None if mask_l is None else mask_l[box[1]:box[3], box[0]:box[2]],
                             mask_blur, paste_back, resolution=resolution, metrics=metrics, output_size="source", masked_content=masked_content,
-                            blend=blend, blend_levels=blend_levels)
+                            blend=blend, blend_levels=blend_levels, mask_mode="levels" if soft else "binary")
             if metrics:
                 return hregion.paste(image, res[0], box), res[1]
             return hregion.paste(image, res, box)
@@ -311,7 +331,7 @@ class FastEditor:
                 image, mask_l = self._outpaint_device(image, mask_l, margins)
             source_dev, control_dev, finish = self._canny_device(image, kw["canny_low_threshold"], kw["canny_high_threshold"], size=size, wait=False,
                                                                  original=origs)
-            mask_dev = self._mask_device(mask_l, size, original=omasks, grow=grow)
+            mask_dev = self._mask_device(mask_l, size, original=omasks, grow=grow, levels=kw["levels"])
         hook = None
         if metrics:
             keep = {} if select is not None else None
@@ -324,7 +344,8 @@ class FastEditor:
                          strength=kw["strength"], num_inference_steps=kw["num_inference_steps"], guidance_scale=kw["guidance_scale"],
                          controlnet_conditioning_scale=kw["controlnet_conditioning_scale"], generator=generator, post_check=finish,
                          mask_image=mask_dev, mask_blur=0 if full else kw["mask_blur"], paste_back=kw["paste_back"] and not full,
-                         after_device=hook, masked_content=kw["masked_content"], blend=kw["blend"], blend_levels=kw["blend_levels"], paste_later=full)
+                         after_device=hook, masked_content=kw["masked_content"], blend=kw["blend"], blend_levels=kw["blend_levels"], paste_later=full,
+                         mask_mode="levels" if isinstance(mask_dev, MaskLevels) else "binary")
 
     def _fullres(self, slot, origs, omasks, blur, then=None):
         """The `after_device` hook of an edit with output_size="source": queues, on the edit's stream behind its result and outside its graph, the
@@ -375,14 +396,15 @@ class FastEditor:
     def edit_sweep(self, image, prompt, negative_prompt="", strengths="all", num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
                    paste_back=True, *, resolution=None, output_size=None, region=None, tiles=None, masked_content="original", blend="alpha",
-                   blend_levels=4, mask_grow=0, outpaint=None, select=None, min_ssim=None):
+                   blend_levels=4, mask_grow=0, outpaint=None, select=None, min_ssim=None, mask_mode="binary", mask_ramp=0):
         """[additive] edit() at several strengths as ONE device job, scored on the device, optionally with the winner picked there (DESIGN.md
         section 20).  `strength` only decides how many of the `num_inference_steps` LCM steps an edit runs, so the distinct edits are those of the
         distinct step counts m = min(int(N * s), N): `strengths` is "all" (one variant per m = 1 .. N) or a list of floats in [0, 1]; strengths with
         the same m are one variant (fie_amd/sweep.py: variants; at most 16).  Variants are ordered strongest first.  Upload, resize, Canny map, text
         encoders, mask preparation, fill, VAE encode and edge-map embedding run once; the UNet and the ControlNet run each loop step on the
         variants that have joined by then; with `seed`, variant i is what edit(..., strength=s_i, seed=seed) returns up to fp16 tiling effects
-        (the bound of edit_batch against serial edits).  The other keywords are edit()'s (`metrics` is always on; `region` and `tiles` are a
+        (the bound of edit_batch against serial edits).  A soft mask (`mask_mode` / `mask_ramp`) is prepared once: its support does not depend
+        on the step count, and every variant releases a level by its own number of steps.  The other keywords are edit()'s (`metrics` is always on; `region` and `tiles` are a
         ValueError).
         select=None: returns (images, variants): variants[i] = {"strength": [the requested strengths of the variant], "steps": m, and the
         metrics dict edit(..., strength=s_i, metrics=True) reports}.
@@ -419,7 +441,8 @@ class FastEditor:
         kw = dict(strength=[v[1][0] for v in vs], num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                   controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
                   canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
-                  masked_content=masked_content, blend=blend, blend_levels=blend_levels)
+                  masked_content=masked_content, blend=blend, blend_levels=blend_levels,
+                  levels=hmask.check_levels(mask_mode, mask_ramp, grow, masked))
         rule = None if select is None else (select, hsweep.ssim_floor(min_ssim, hmetrics.TARGET[1], hmetrics.TARGET[0]), masked)
         res = self._single_job(image, prompt, negative_prompt, k, resolution, mask_l, margins, grow, True, full, kw, select=rule)
         extra, ihost = res.extra if select is not None else (res.extra, None)
@@ -557,6 +580,11 @@ class FastEditor:
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(getattr(self._tls, "slot", 0))):
             return self.pipe.ctx.mask_grow(torch.from_numpy(mask_l).to(self.pipe.ctx.device), grow).cpu().numpy()
 
+    def _ramp_host(self, mask_l, ramp):
+        """uint8 [H, W] mask -> its level map under `mask_ramp` (fie_mask_ramp_u8), back on the host: what a region edit crops.  As _grow_host()."""
+        with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(getattr(self._tls, "slot", 0))):
+            return self.pipe.ctx.mask_ramp(torch.from_numpy(mask_l).to(self.pipe.ctx.device), ramp).cpu().numpy()
+
     def _outpaint_device(self, image, mask_l, margins):
         """PIL image, uint8 [H, W] mask or None, check_outpaint()'s margins -> (canvas u8 [Hc, Wc, 3], canvas mask u8 [Hc, Wc]) on the device:
         source and mask are uploaded at their own size, the canvas is one launch (fie_outpaint_canvas_rgb_u8) on the current stream.  An image of
@@ -581,11 +609,14 @@ class FastEditor:
         canvas, canvas_mask = self._outpaint_host(image, hmask.to_l_array(mask, image.size) if mask is not None else None, margins)
         return Image.fromarray(canvas), Image.fromarray(canvas_mask)
 
-    def _mask_device(self, mask_l, size, original=None, grow=0):
+    def _mask_device(self, mask_l, size, original=None, grow=0, levels=("binary", 0)):
         """uint8 [H, W] mode-L mask (or None) -> u8 [size[1], size[0]] on the device: LANCZOS-resized as the source is (fie_resize_l_u8,
         bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`).  `original`: a list that receives the mask as uploaded (or None).
         `grow` != 0: the uploaded mask is grown by that radius first (fie_mask_grow_u8), and it is the grown one that `original` receives.
-        `mask_l` may also be a u8 [H, W] tensor already on the device (an outpainting canvas's mask): it is taken as the upload."""
+        `mask_l` may also be a u8 [H, W] tensor already on the device (an outpainting canvas's mask): it is taken as the upload.
+        `levels`: check_levels()'s (mask_mode, mask_ramp); a soft mask comes back as MaskLevels(support, levels): the level
+        map V is the (grown) mask ramped on the device (fie_mask_ramp_u8) or, with "levels", the upload itself; `original` receives its support
+        S = 255 (V > 0), and S and V are resized separately."""
         if mask_l is None:
             if original is not None:
                 original.append(None)
@@ -593,16 +624,22 @@ class FastEditor:
         m = mask_l if torch.is_tensor(mask_l) else torch.from_numpy(mask_l).to(self.pipe.ctx.device)
         if grow:
             m = self.pipe.ctx.mask_grow(m, grow)
+        v = self.pipe.ctx.mask_ramp(m.contiguous(), levels[1]) if levels[1] else m.contiguous() if levels[0] == "levels" else None
+        if v is not None:
+            m = self.pipe.ctx.mask_support(v)
         if original is not None:
             original.append(m)
         if (m.shape[1], m.shape[0]) != tuple(size):
             m = self.pipe.ctx.resize_lanczos(m, size[1], size[0])
-        return m
+            if v is not None:
+                v = self.pipe.ctx.resize_lanczos(v, size[1], size[0])
+        return m if v is None else MaskLevels(m, v)
 
     def edit_batch(self, images, prompts, negative_prompts=None, strength=0.80, num_inference_steps=4, guidance_scale=1.5,
                    controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, masks=None, mask_blur=0,
                    paste_back=True, *, resolution=None, metrics=False, output_size=None, region=None, region_padding=32, masked_content="original",
-                   blend="alpha", blend_levels=4, mask_grow=0, outpaint=None, tiles=None, tile_overlap=128, tile_batch=4):
+                   blend="alpha", blend_levels=4, mask_grow=0, outpaint=None, tiles=None, tile_overlap=128, tile_batch=4, mask_mode="binary",
+                   mask_ramp=0):
         """[additive] edit() for a list of images in ONE device job (UNet / ControlNet / CLIP at batch n x CFG; the
         BASELINE "batch=8" configuration).  Every image gets its own generator seeded with `seed`, exactly as n serial
         edit(..., seed=seed) calls would, so image i of the batch equals the serial result up to fp16 tiling effects.
@@ -616,6 +653,7 @@ class FastEditor:
         `masked_content`: as edit()'s, one value for the whole call; an image whose mask is None is edited as without it.
         `blend` / `blend_levels`: as edit()'s, one value for the whole call; an image whose mask is None comes out as without them.
         `mask_grow`: as edit()'s, one radius for the whole call; an image whose mask is None is untouched.
+        `mask_mode` / `mask_ramp`: as edit()'s, one value for the whole call; an image whose mask is None is untouched.
         `outpaint`: as edit()'s -- one (left, top, right, bottom) tuple for the whole call, or a LIST with one entry (a tuple or None) per image; an
         image whose entry is None is treated as without the keyword, one with margins counts as masked.  Images group by the target size of their
         canvases.
@@ -628,14 +666,15 @@ class FastEditor:
         if htiles.check(tiles, tile_overlap, tile_batch)[0] is not None:
             self._check_tiled(resolution, region, outpaint, output_size)
             has_mask = [masks is not None and m is not None for m in (masks or [None] * len(images))]
-            hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, any(has_mask))
+            hmask.check_levels(mask_mode, mask_ramp, hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow,
+                                                                          any(has_mask))[2], any(has_mask))
             negs = list(negative_prompts) if isinstance(negative_prompts, (list, tuple)) else [negative_prompts or ""] * len(images)
             if len(negs) != len(images):
                 raise ValueError(f"{len(negs)} negative prompts for {len(images)} images")
             res = []
             for i, (im, p) in enumerate(zip(images, prompts)):         # an image whose mask is None is edited as without the mask keywords
                 mk = dict(mask=masks[i], mask_blur=mask_blur, masked_content=masked_content, blend=blend, blend_levels=blend_levels,
-                          mask_grow=mask_grow) if has_mask[i] else {}
+                          mask_grow=mask_grow, mask_mode=mask_mode, mask_ramp=mask_ramp) if has_mask[i] else {}
                 res.append(self.edit(im, p, negs[i], strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
                                      canny_low_threshold, canny_high_threshold, seed, paste_back=paste_back, metrics=metrics, output_size=output_size,
                                      tiles=tiles, tile_overlap=tile_overlap, tile_batch=tile_batch, **mk))
@@ -646,6 +685,8 @@ class FastEditor:
         outpainted = any(o is not None for o in margins)
         has_mask = [(masks is not None and masks[i] is not None) or o is not None for i, o in enumerate(margins)]
         grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, any(has_mask))[2]
+        levels = hmask.check_levels(mask_mode, mask_ramp, grow, any(has_mask))
+        soft = levels != ("binary", 0)
         regions = list(region) if isinstance(region, list) else [region] * len(images)
         if len(regions) != len(images):
             raise ValueError(f"{len(regions)} regions for {len(images)} images: one region (or None) per image")
@@ -660,18 +701,22 @@ class FastEditor:
             return self.edit_batch(canvases, prompts, negative_prompts, strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
                                    canny_low_threshold, canny_high_threshold, seed, cmasks, mask_blur, paste_back, resolution=resolution,
                                    metrics=metrics, output_size=output_size, region=region, region_padding=region_padding,
-                                   masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow)
+                                   masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow, mask_mode=levels[0],
+                                   mask_ramp=levels[1])
         if has_region:
             mls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks or [None] * len(images), images)]
             if grow:        # grown first, cropped second (edit())
                 mls = [m if m is None else self._grow_host(m, grow) for m in mls]
-            boxes = [hregion.resolve(r, im.size, m, region_padding, resolution) for r, im, m in zip(regions, images, mls)]
+            if levels[1]:   # ramped whole, cropped second (edit())
+                mls = [m if m is None else self._ramp_host(m, levels[1]) for m in mls]
+            boxes = [hregion.resolve(r, im.size, hmask.support_numpy(m) if soft and m is not None else m, region_padding, resolution)
+                     for r, im, m in zip(regions, images, mls)]
             cut = lambda a, b: a if a is None or b is None else a[b[1]:b[3], b[0]:b[2]]
             res = self.edit_batch([im if b is None else im.crop(b) for im, b in zip(images, boxes)], prompts, negative_prompts, strength,
                                   num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold,
                                   seed, None if masks is None else [cut(m, b) for m, b in zip(mls, boxes)], mask_blur, paste_back,
                                   resolution=resolution, metrics=metrics, output_size="source", masked_content=masked_content,
-                                  blend=blend, blend_levels=blend_levels)
+                                  blend=blend, blend_levels=blend_levels, mask_mode="levels" if soft and masks is not None else "binary")
             outs = [o if b is None else hregion.paste(im, o, b) for im, o, b in zip(images, res[0] if metrics else res, boxes)]
             return (outs, res[1]) if metrics else outs
         sizes = [buckets.target_size(resolution, hmask.canvas_size(im.size, o)) for im, o in zip(images, margins)]
@@ -691,6 +736,8 @@ class FastEditor:
                                       blend=blend if any(has_mask[i] for i in idx) else "alpha",
                                       blend_levels=blend_levels,
                                       mask_grow=grow if any(has_mask[i] for i in idx) else 0,
+                                      mask_mode=levels[0] if any(has_mask[i] for i in idx) else "binary",
+                                      mask_ramp=levels[1] if any(has_mask[i] for i in idx) else 0,
                                       outpaint=[margins[i] for i in idx] if outpainted else None)
                 res, ms = res if metrics else (res, [None] * len(idx))
                 for i, r, m in zip(idx, res, ms):
@@ -703,7 +750,7 @@ class FastEditor:
                                       dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                            controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
                                            canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
-                                           masked_content=masked_content, blend=blend, blend_levels=blend_levels))
+                                           masked_content=masked_content, blend=blend, blend_levels=blend_levels, levels=levels))
         if not metrics:
             return res.images
         return res.images, self._scores(res.extra, [m is not None for m in omasks])
@@ -733,7 +780,7 @@ class FastEditor:
                 ctls.append(c_dev)
                 if one is not None:
                     origs.append(one[0])
-            mask_devs = [self._mask_device(m, size, original=omasks, grow=grow) for m in mask_ls] if mask_ls is not None else None
+            mask_devs = [self._mask_device(m, size, original=omasks, grow=grow, levels=kw["levels"]) for m in mask_ls] if mask_ls is not None else None
         if (metrics or full) and mask_ls is None:
             omasks = [None] * len(images)
         hook = after
@@ -745,7 +792,8 @@ class FastEditor:
                         strength=kw["strength"], num_inference_steps=kw["num_inference_steps"], guidance_scale=kw["guidance_scale"],
                         controlnet_conditioning_scale=kw["controlnet_conditioning_scale"], generator=gens, mask_image=mask_devs,
                         mask_blur=0 if full else kw["mask_blur"], paste_back=kw["paste_back"] and not full, after_device=hook,
-                        masked_content=kw["masked_content"], blend=kw["blend"], blend_levels=kw["blend_levels"], paste_later=full)
+                        masked_content=kw["masked_content"], blend=kw["blend"], blend_levels=kw["blend_levels"], paste_later=full,
+                        mask_mode="levels" if any(isinstance(m, MaskLevels) for m in mask_devs or ()) else "binary")
         return res, omasks
 
     def _check_tiled(self, resolution, region, outpaint, output_size):
@@ -763,7 +811,7 @@ class FastEditor:
     def _edit_tiled(self, image, prompt, negative_prompt, plan, tile_batch, mask_l, grow, metrics, kw):
         """edit(..., tiles=...) behind its argument checks (the docstring of edit() defines the result).  plan: tiles.plan()'s (tw, th, xs, ys);
         mask_l: None or the uint8 [H, W] mask; grow: check_grow()'s radius; kw: the scalar keywords of edit().  Source and mask go up once and the
-        mask grows there, whole; the tiles of a device job are contiguous copies of their boxes; each job's `after_device` hook copies its u8
+        mask grows there, whole, and so does a soft mask's ramp (kw["levels"]); the tiles of a device job are contiguous copies of their boxes; each job's `after_device` hook copies its u8
         results into their rows of the slot's [n, th, tw, 3] buffer and keeps them off the host; the hook of the last job queues the blend (and,
         with metrics, the scorer behind it) and hands the H x W x 3 image to the pipeline's device-to-host copy."""
         tw, th, xs, ys = plan
@@ -772,11 +820,14 @@ class FastEditor:
         n = len(xs) * len(ys)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             src = torch.from_numpy(np.array(image if image.mode == "RGB" else image.convert("RGB"))).to(ctx.device)
-            mask_dev = None
+            mask_dev = levels_dev = None
             if mask_l is not None:
                 mask_dev = torch.from_numpy(mask_l).to(ctx.device)
                 if grow:
                     mask_dev = ctx.mask_grow(mask_dev, grow)
+                if kw["levels"] != ("binary", 0):         # a soft mask: ramped whole, once; the tiles carry crops of the levels, the scorer reads the support
+                    levels_dev = ctx.mask_ramp(mask_dev, kw["levels"][1]) if kw["levels"][1] else mask_dev
+                    mask_dev, kw = ctx.mask_support(levels_dev), dict(kw, levels=("levels", 0))
             key = (slot, n, th, tw)
             if key not in self._tile_bufs:
                 self._tile_bufs = {k: v for k, v in self._tile_bufs.items() if k[0] != slot}          # one plan's buffer per slot
@@ -801,7 +852,7 @@ class FastEditor:
                 return DeviceOutput([out], scorer(out) if scorer is not None else None)
             with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
                 crops = [cut(src, boxes[j]) for j in c]
-                mcrops = [cut(mask_dev, boxes[j]) for j in c] if mask_dev is not None else None
+                mcrops = [cut(levels_dev if levels_dev is not None else mask_dev, boxes[j]) for j in c] if mask_dev is not None else None
             res, _ = self._batch_job(crops, [prompt] * len(c), [negative_prompt or ""] * len(c), (tw, th), mcrops, None, 0, False, False, kw,
                                      after=collect)
         if not metrics:
