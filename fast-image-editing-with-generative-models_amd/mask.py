@@ -3,6 +3,7 @@ PIE-Bench run-length code.  Device-free, so all of it runs (and is tested) on th
 
 A mask marks the region to edit in white.  Accepted forms: a PIL image of any mode (taken through `.convert("L")`), or a uint8 / bool
 [H, W] numpy array (bool True = 255)."""
+import dataclasses
 import math
 
 import numpy as np
@@ -89,14 +90,6 @@ def check_grow(mask_grow, have_mask=True):
     return int(mask_grow)
 
 
-def check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, have_mask=True, paste_later=False):
-    """The four rule sets above in the one order every entry point runs them: args, content, blend, grow.  `paste_later`: the caller composites
-    behind the job, which counts as a paste-back for `blend`.  Returns the normalised (content, (blend, levels), grow)."""
-    check_args(mask_blur, paste_back, have_mask)
-    return (check_content(masked_content, have_mask), check_blend(blend, blend_levels, have_mask, paste_back or paste_later),
-            check_grow(mask_grow, have_mask))
-
-
 def check_levels(mask_mode="binary", mask_ramp=0, mask_grow=0, have_mask=True):
     """The argument rules of `mask_mode` / `mask_ramp` (soft masks: the mask's grey level as a per-pixel strength; DESIGN.md section 21);
     returns (mask_mode, mask_ramp as an int).  Both need a mask (an outpaint counts as one).  "levels" reads the greys as passed, so neither
@@ -115,6 +108,82 @@ def check_levels(mask_mode="binary", mask_ramp=0, mask_grow=0, have_mask=True):
     if mask_mode == "levels" and mask_grow != 0:
         raise ValueError("mask_mode='levels' with mask_grow: the grown mask is binary and would discard the greys")
     return mask_mode, int(mask_ramp)
+
+
+@dataclasses.dataclass(frozen=True)
+class MaskSpec:
+    """The mask keywords of one call, normalised: what every entry point builds once, with check(), and hands inward in place of the keywords.
+    A new mask keyword is a field here, its rule in check() and its public name in keywords()."""
+    blur: float = 0.0
+    paste_back: bool = True
+    content: str = "original"
+    blend: str = "alpha"
+    blend_levels: int = 4
+    grow: int = 0
+    mode: str = "binary"
+    ramp: int = 0
+    paste_later: bool = False      # the caller composites behind the job, which counts as a paste-back for `blend`
+
+    @classmethod
+    def check(cls, mask_blur=0, paste_back=True, masked_content="original", blend="alpha", blend_levels=4, mask_grow=0, mask_mode="binary",
+              mask_ramp=0, *, have_mask, paste_later=False):
+        """The rule sets above in the one order every entry point runs them: args, content, blend, grow, levels."""
+        blur = check_args(mask_blur, paste_back, have_mask)
+        content = check_content(masked_content, have_mask)
+        blend, blend_levels = check_blend(blend, blend_levels, have_mask, paste_back or paste_later)
+        grow = check_grow(mask_grow, have_mask)
+        mode, ramp = check_levels(mask_mode, mask_ramp, grow, have_mask)
+        return cls(blur, bool(paste_back), content, blend, blend_levels, grow, mode, ramp, bool(paste_later))
+
+    @property
+    def soft(self):
+        """A soft mask: its readers take a MaskLevels pair."""
+        return self.mode != "binary" or self.ramp != 0
+
+    def keywords(self):
+        """The spec under the public keyword names, for re-entering a public method: check(**s.keywords(), have_mask=True) == s.  `paste_later`
+        is the pipeline's alone (FastEditor's methods have no such keyword) and is named only where it is set."""
+        return dict(mask_blur=self.blur, paste_back=self.paste_back, masked_content=self.content, blend=self.blend, blend_levels=self.blend_levels,
+                    mask_grow=self.grow, mask_mode=self.mode, mask_ramp=self.ramp, **(dict(paste_later=True) if self.paste_later else {}))
+
+    def unmasked(self):
+        """What an image without a mask of its own runs with: as without the keywords."""
+        return MaskSpec(paste_back=self.paste_back, paste_later=self.paste_later)
+
+    def behind_fullres(self):
+        """The job in front of the source-size back end (output_size="source"): feather and paste-back happen there, behind it."""
+        return dataclasses.replace(self, blur=0.0, paste_back=False, paste_later=True)
+
+    def prepared(self):
+        """What goes with a mask that has been grown and ramped already: a soft one is a level map, read as it is."""
+        return dataclasses.replace(self, grow=0, ramp=0, mode="levels" if self.soft else "binary")
+
+
+def cli_keywords(args, masked, flag):
+    """The command lines' mask flags behind the parser: `args` the parsed namespace (a flag its parser lacks counts as its default), `masked`
+    whether the run has a mask, `flag` the option that gives one ("--use_mask" / "--mask").  Refuses what needs a mask without one, and "levels"
+    with a ramp or a grow, as a ValueError; returns edit()'s keywords for the flags that differ from their defaults."""
+    get = lambda name, default: getattr(args, name, default)
+    out = {}
+    if get("masked_content", "original") != "original":
+        if not masked:
+            raise ValueError(f"--masked_content needs {flag}")
+        out.update(masked_content=args.masked_content)
+    if get("blend", "alpha") != "alpha":
+        if not masked or get("no_paste_back", False):
+            raise ValueError(f"--blend multiband needs {flag}" + (" and the paste-back" if hasattr(args, "no_paste_back") else ""))
+        out.update(blend=args.blend, blend_levels=get("blend_levels", 4))
+    if get("mask_grow", 0):
+        if not masked:
+            raise ValueError(f"--mask_grow needs {flag}")
+        out.update(mask_grow=args.mask_grow)
+    if get("mask_mode", "binary") != "binary" or get("mask_ramp", 0):
+        if not masked:
+            raise ValueError(f"--mask_mode levels and --mask_ramp need {flag}")
+        if get("mask_mode", "binary") == "levels" and (get("mask_ramp", 0) or get("mask_grow", 0)):
+            raise ValueError("--mask_mode levels does not go with --mask_ramp or --mask_grow: both work on the outline and would discard the greys")
+        out.update(mask_mode=get("mask_mode", "binary"), mask_ramp=get("mask_ramp", 0))
+    return out
 
 
 def level_steps(v, K):

@@ -170,26 +170,22 @@ class HipImg2ImgPipeline:
         from the binary mask's outline on the device (after `mask_grow`): 0 outside, floor(255 d / r) up to 255 inside, d the distance to the
         nearest pixel outside the mask, in pixels of the mask as passed.  The two do not combine, nor does "levels" with `mask_grow`.  A
         `MaskLevels(support, levels)` pair of u8 [H, W] device tensors is taken as it is (FastEditor resizes the two separately)."""
-        grow = hmask.check_grow(mask_grow, mask_image is not None)
+        spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp,
+                                    have_mask=mask_image is not None, paste_later=paste_later)
         return self._prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content,
-                             hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later), grow,
-                             hmask.check_levels(mask_mode, mask_ramp, grow, mask_image is not None))
+                             controlnet_conditioning_scale, generator, mask_image, spec)
 
-    def _mask_job(self, mask_image, mask_blur, paste_back, h, w, grow=0, levels=("binary", 0)):
-        """Mask tensors of one image: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back, the edit-size L mask
-        u8 [1, h, w], lvl_lat u8 [1, h/8 * w/8] or None).  The mask is binarised / downsampled / feathered on the device (fie_mask_prep) on the
-        current stream, in front of the job; with `grow` != 0 it is grown or shrunk by that radius first (fie_mask_grow_u8, same place), and the L
-        mask returned is the grown one.  `levels` = check_levels()'s (mask_mode, mask_ramp), a soft mask: the level map V is
-        the mask itself ("levels"), fie_mask_ramp_u8 of the (grown) mask (mask_ramp > 0) or a MaskLevels pair's; the L mask returned and prepared
-        is its support, and lvl_lat holds the latent levels (fie_mask_levels_u8), which the latent step alone reads."""
-        r = hmask.check_args(mask_blur, paste_back, mask_image is not None)
+    def _mask_job(self, mask_image, spec, h, w):
+        """Mask tensors of one image under its MaskSpec: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back, the
+        edit-size L mask u8 [1, h, w], lvl_lat u8 [1, h/8 * w/8] or None), made on the device on the current stream, in front of the job:
+        the optional grow (fie_mask_grow_u8), a soft mask's level map V -- the mask itself ("levels"), fie_mask_ramp_u8 of the grown mask, or a
+        MaskLevels pair's -- and its support, which is the L mask returned, then fie_mask_prep on that; lvl_lat holds V's latent levels
+        (fie_mask_levels_u8), which the latent step alone reads (DESIGN.md sections 8, 16, 21)."""
         if mask_image is None:
             return None, None, None, None
-        mode, ramp = levels
         pair = isinstance(mask_image, MaskLevels)         # support and levels as the caller resized them: nothing to grow, ramp or derive
         if pair:
-            if mode != "levels":
+            if spec.mode != "levels":
                 raise ValueError("a MaskLevels pair is a level map: it needs mask_mode='levels'")
             for t in (mask_image.support, mask_image.levels):
                 if not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != (h, w):
@@ -204,21 +200,21 @@ class HipImg2ImgPipeline:
         else:
             lm = torch.from_numpy(hmask.to_l_array(mask_image, (w, h))).to(self.ctx.device)
         with self.eager_lock:                             # the context's stream binding is shared by the threads of in-flight edits
-            if grow:
-                lm = self.ctx.mask_grow(lm, grow)
+            if spec.grow:
+                lm = self.ctx.mask_grow(lm, spec.grow)
             if not pair:
-                lv = self.ctx.mask_ramp(lm, ramp) if ramp else lm if mode == "levels" else None
+                lv = self.ctx.mask_ramp(lm, spec.ramp) if spec.ramp else lm if spec.mode == "levels" else None
                 if lv is not None:
                     lm = self.ctx.mask_support(lv)
-            m_px, m_lat = self.ctx.mask_prep(lm, r)
+            m_px, m_lat = self.ctx.mask_prep(lm, spec.blur)
             lvl = self.ctx.mask_levels(lv, m_lat) if lv is not None else None
-        return m_lat[None], (m_px[None] if paste_back else None), lm[None], None if lvl is None else lvl[None]
+        return m_lat[None], (m_px[None] if spec.paste_back else None), lm[None], None if lvl is None else lvl[None]
 
     def _prepare(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                 controlnet_conditioning_scale, generator, mask_image=None, mask_blur=0, paste_back=True, masked_content="original",
-                 blend=("alpha", 4), grow=0, levels=("binary", 0)):
-        """Host side of one call: argument checks, tokenisation, RNG draws (in upstream order: posterior sample, init
-        noise, one per non-final step) and the H2D copies.  Returns the device-resident job for run_device()."""
+                 controlnet_conditioning_scale, generator, mask_image, spec):
+        """Host side of one call: image and size checks, tokenisation, RNG draws (in upstream order: posterior sample, init
+        noise, one per non-final step) and the H2D copies.  `spec`: the call's checked MaskSpec.  Returns the device-resident job for
+        run_device()."""
         ctx = self.ctx
         if image is None or control_image is None:
             raise ValueError("`image` and `control_image` are both required")
@@ -230,8 +226,7 @@ class HipImg2ImgPipeline:
         w, h = size_of(image)
         if h % 8 or w % 8:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {h} and {w}.")
-        content = hmask.check_content(masked_content, mask_image is not None)
-        mask_lat, mask_px, mask_l, lvl_lat = self._mask_job(mask_image, mask_blur, paste_back, h, w, grow, levels)
+        mask_lat, mask_px, mask_l, lvl_lat = self._mask_job(mask_image, spec, h, w)
         steps = self.scheduler.plan(num_inference_steps, strength)
         if not steps:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of "
@@ -265,22 +260,23 @@ class HipImg2ImgPipeline:
             guidance=float(guidance_scale), cn_scale=float(controlnet_conditioning_scale),
             time_ids=const[0], t_dev=const[1],
             noises=[self._randn((1, 4, lh, lw), generator) for _ in range(n_noise)],
-            mask_lat=mask_lat, mask_px=mask_px, mask_cfg=None if mask_lat is None else (float(mask_blur), bool(paste_back)),
+            mask_lat=mask_lat, mask_px=mask_px, mask_cfg=None if mask_lat is None else (spec.blur, spec.paste_back),
             **({} if lvl_lat is None else dict(lvl_lat=lvl_lat)),         # a soft mask's latent levels; none: the job is what it was
-            **self._content_job(content, mask_l, mask_lat), **self._blend_job(blend, mask_l))
+            **self._content_job(spec, mask_l, mask_lat), **self._blend_job(spec, mask_l))
 
     @staticmethod
-    def _blend_job(blend, blend_l):
+    def _blend_job(spec, blend_l):
         """The job entries of blend="multiband" (DESIGN.md section 15); none with "alpha", whose job is what it was.  `blend_l`: the edit-size L
         mask u8 [1, h, w] that the blend reads inside the device job -- the image's own mask, or all 255 for an image of a batch that has none
         (everything is inside: the blend returns the decoded bytes)."""
-        return {} if blend[0] == "alpha" else dict(blend=(blend[0], int(blend[1])), blend_l=blend_l)
+        return {} if spec.blend == "alpha" else dict(blend=(spec.blend, spec.blend_levels), blend_l=blend_l)
 
     @staticmethod
-    def _content_job(content, mask_l, content_lat):
+    def _content_job(spec, mask_l, content_lat):
         """The job entries of a masked-content mode; none with "original", whose job is what it was.  `mask_l`: the edit-size
         L mask u8 [1, h, w], read inside the device job by the fill and the edge-map clear; `content_lat`: u8 [1, h/8 * w/8], where the latent
         modes replace the initial latents -- the image's mask_lat, or zeros for an image of a batch that has no mask of its own."""
+        content = spec.content
         if content == "original":
             return {}
         out = dict(content=content, mask_l=mask_l)
@@ -301,26 +297,19 @@ class HipImg2ImgPipeline:
         radius for the call; an image without a mask is untouched.  `mask_mode` / `mask_ramp`: prepare()'s, one value for the call; an image without a
         mask is untouched (its latent levels are 255 everywhere)."""
         n = len(prompts)
+        masks = list(mask_image) if mask_image is not None else [None] * n
+        masked = any(m is not None for m in masks)
+        spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp,
+                                    have_mask=masked, paste_later=paste_later)
         if not (n == len(images) == len(control_images)) or n == 0:
             raise ValueError("prompts, images and control_images must be non-empty lists of one length")
-        masks = list(mask_image) if mask_image is not None else [None] * n
         if len(masks) != n:
             raise ValueError(f"{len(masks)} masks for {n} images: one mask (or None) per image")
-        masked = any(m is not None for m in masks)
-        hmask.check_args(mask_blur, paste_back, masked)
-        content = hmask.check_content(masked_content, masked)
-        blend = hmask.check_blend(blend, blend_levels, masked, paste_back or paste_later)
-        grow = hmask.check_grow(mask_grow, masked)
-        levels = hmask.check_levels(mask_mode, mask_ramp, grow, masked)
         negative_prompts = negative_prompts or [""] * n
         generators = generators or [None] * n
         jobs = [self._prepare(prompts[i], negative_prompts[i], images[i], control_images[i], strength, num_inference_steps,
                               guidance_scale, controlnet_conditioning_scale, generators[i], masks[i],
-                              mask_blur if masks[i] is not None else 0, paste_back,
-                              content if masks[i] is not None else "original",
-                              blend if masks[i] is not None else ("alpha", 4),
-                              grow if masks[i] is not None else 0,
-                              levels if masks[i] is not None else ("binary", 0)) for i in range(n)]
+                              spec if masks[i] is not None else spec.unmasked()) for i in range(n)]
         if any(j["hw"] != jobs[0]["hw"] for j in jobs):
             raise ValueError("all images of a batch must have one size")
         if masked:                                        # an image without a mask edits everywhere: an all-ones mask
@@ -328,14 +317,14 @@ class HipImg2ImgPipeline:
             for j in jobs:
                 if j["mask_lat"] is None:
                     j["mask_lat"] = torch.ones((1, (h // 8) * (w // 8)), device=self.ctx.device, dtype=torch.uint8)
-                    j["mask_px"] = torch.ones((1, h, w), device=self.ctx.device, dtype=torch.float32) if paste_back else None
-                    j["mask_cfg"] = (float(mask_blur), bool(paste_back))
-                    if levels != ("binary", 0):
+                    j["mask_px"] = torch.ones((1, h, w), device=self.ctx.device, dtype=torch.float32) if spec.paste_back else None
+                    j["mask_cfg"] = (spec.blur, spec.paste_back)
+                    if spec.soft:
                         j["lvl_lat"] = torch.full((1, (h // 8) * (w // 8)), 255, device=self.ctx.device, dtype=torch.uint8)
                     # no mask of its own: an empty hole -- nothing filled, no edge cleared, no latent replaced
-                    j.update(self._content_job(content, torch.zeros((1, h, w), device=self.ctx.device, dtype=torch.uint8),
+                    j.update(self._content_job(spec, torch.zeros((1, h, w), device=self.ctx.device, dtype=torch.uint8),
                                                torch.zeros((1, (h // 8) * (w // 8)), device=self.ctx.device, dtype=torch.uint8)))
-                    j.update(self._blend_job(blend, torch.full((1, h, w), 255, device=self.ctx.device, dtype=torch.uint8)))
+                    j.update(self._blend_job(spec, torch.full((1, h, w), 255, device=self.ctx.device, dtype=torch.uint8)))
         if n == 1:
             return jobs[0]                                # the single-image job (and its graph)
         nb, t77 = jobs[0]["nb"], jobs[0]["ids_g"].shape[1]
@@ -363,13 +352,12 @@ class HipImg2ImgPipeline:
         image-major as in prepare_batch().  One generator: variant i consumes the noise a single call with that generator and strength draws (its
         stream is a prefix of the longest variant's).  A soft mask's level map is shared: its support does not depend on the step count, and every
         variant releases a level by its own K.  The other arguments are prepare()'s.  A sweep of ONE variant is the single-image job."""
+        spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp,
+                                    have_mask=mask_image is not None, paste_later=paste_later)
         from . import sweep as hsweep
         vs = hsweep.variants(num_inference_steps, strengths)
-        grow = hmask.check_grow(mask_grow, mask_image is not None)
         job = self._prepare(prompt, negative_prompt, image, control_image, vs[0][1][0], num_inference_steps, guidance_scale,
-                            controlnet_conditioning_scale, generator, mask_image, mask_blur, paste_back, masked_content,
-                            hmask.check_blend(blend, blend_levels, mask_image is not None, paste_back or paste_later), grow,
-                            hmask.check_levels(mask_mode, mask_ramp, grow, mask_image is not None))
+                            controlnet_conditioning_scale, generator, mask_image, spec)
         if len(vs) == 1:
             return job                                    # the single-image job (and its graph)
         plans = [self.scheduler.plan(num_inference_steps, v[1][0]) for v in vs]
@@ -705,12 +693,9 @@ class HipImg2ImgPipeline:
     # lvl_lat: a soft mask's latent levels (section 21)
     _MASK_KEYS = ("mask_lat", "mask_px", "mask_l", "content_lat", "blend_l", "lvl_lat")
 
-    def run_device_graphed(self, job, slot=0):
-        """run_device() replayed from a hipGraph: the ~2 500 launches of one edit are captured once per
-        (size, CFG batch, step plan, scales) and replayed with the job's inputs copied into the graph's static buffers.
-        The returned u8 image is the graph's static output buffer (consume it before the next replay).
-        `slot` selects an independent graph instance (own static buffers / scratch) so that several edits can be in
-        flight on different streams of one GPU."""
+    @staticmethod
+    def _graph_base(job, slot):
+        """What of a job decides which graph replays it: the graph key without the fork flag."""
         base = (job["hw"], job["nb"], tuple(st["t"] for st in job["steps"]), job["guidance"], job["cn_scale"], slot, job.get("n", 1))
         if job.get("mask_lat") is not None:              # masked: (masked, mask_blur, paste_back); an unmasked key is what it was
             # + the masked-content mode, unless "original"; + ("multiband", levels), unless the blend is "alpha"; + "levels" for a soft mask
@@ -718,6 +703,15 @@ class HipImg2ImgPipeline:
                            + (("levels",) if job.get("lvl_lat") is not None else ()),)
         if job.get("sweep"):                             # a strength sweep: + the step counts of its variants
             base = base + (("sweep", job["sweep"]),)
+        return base
+
+    def run_device_graphed(self, job, slot=0):
+        """run_device() replayed from a hipGraph: the ~2 500 launches of one edit are captured once per
+        (size, CFG batch, step plan, scales) and replayed with the job's inputs copied into the graph's static buffers.
+        The returned u8 image is the graph's static output buffer (consume it before the next replay).
+        `slot` selects an independent graph instance (own static buffers / scratch) so that several edits can be in
+        flight on different streams of one GPU."""
+        base = self._graph_base(job, slot)
         # A forked graph owns extra runtime streams; past ~8 such graphs in one process new ones start sharing hardware queues
         # with their own launch stream and replay 50 % slower (measured: 82 -> 125 ms, tools/edit_ab.py).  Beyond the budget a
         # new key is captured on one stream instead (87 ms): slower than a healthy forked graph, never pathological.
@@ -865,15 +859,16 @@ class HipImg2ImgPipeline:
         `DeviceOutput` replaces the image: its tensor(s) take the final device-to-host copy (FastEditor's full-resolution back end).
         `strength` (additive): a list of strengths or "all" makes the call a strength sweep (prepare_sweep): `.images` holds one image per distinct
         step count, strongest first, and the hooks see u8 [k, h, w, 3] as they do for a batch."""
+        have_mask = any(m is not None for m in mask_image) if isinstance(mask_image, (list, tuple)) else mask_image is not None
+        spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp,
+                                    have_mask=have_mask, paste_later=paste_later)
         if slot and not self.use_graph:
             raise ValueError("slots > 0 need hipGraph replay (the eager path shares per-image state)")
         caller, st = torch.cuda.current_stream(self.ctx.device), self.slot_stream(slot)
         st.wait_stream(caller)                           # device-resident inputs may still be in flight on the caller's stream
         with torch.cuda.stream(st):
             out = self._call(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, generator, output_type, slot, post_check, (mask_image, mask_blur, paste_back), after_device,
-                             masked_content, dict(blend=blend, blend_levels=blend_levels, paste_later=paste_later, mask_grow=mask_grow,
-                                                  mask_mode=mask_mode, mask_ramp=mask_ramp))
+                             controlnet_conditioning_scale, generator, output_type, slot, post_check, mask_image, spec, after_device)
         caller.wait_stream(st)
         return out
 
@@ -906,9 +901,7 @@ class HipImg2ImgPipeline:
         return hosts[0].numpy().copy()
 
     def _call(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-              controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_args=(None, 0, True), after_device=None,
-              masked_content="original", blend_kw=None):
-        blend_kw = blend_kw or {}
+              controlnet_conditioning_scale, generator, output_type, slot, post_check=None, mask_image=None, spec=hmask.MaskSpec(), after_device=None):
 
         def run(job):
             """One device job, the caller's after_device hook behind it, then the result on the host: -> (u8 array, hook's return)."""
@@ -922,7 +915,7 @@ class HipImg2ImgPipeline:
             if isinstance(prompt, (list, tuple)):
                 raise ValueError("a strength sweep runs on one image: `strength` is a list and `prompt` is one too")
             job = self.prepare_sweep(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
-                                     controlnet_conditioning_scale, generator, *mask_args, masked_content=masked_content, **blend_kw)
+                                     controlnet_conditioning_scale, generator, mask_image, **spec.keywords())
             arr, extra = run(job)
             if post_check is not None and post_check():
                 self.repeated_jobs += 1
@@ -933,8 +926,8 @@ class HipImg2ImgPipeline:
         if isinstance(prompt, (list, tuple)):            # [additive] a batch: lists of prompts / images / generators
             job = self.prepare_batch(list(prompt), negative_prompt if isinstance(negative_prompt, (list, tuple)) else None,
                                      list(image), list(control_image), strength, num_inference_steps, guidance_scale,
-                                     controlnet_conditioning_scale, generator if isinstance(generator, (list, tuple)) else None, *mask_args,
-                                     masked_content=masked_content, **blend_kw)
+                                     controlnet_conditioning_scale, generator if isinstance(generator, (list, tuple)) else None, mask_image,
+                                     **spec.keywords())
             arr, extra = run(job)
             if post_check is not None and post_check():
                 arr, extra = run(job)
@@ -944,7 +937,7 @@ class HipImg2ImgPipeline:
                 return types.SimpleNamespace(images=list(arr), extra=extra)
             return types.SimpleNamespace(images=[Image.fromarray(a) for a in arr], extra=extra)
         job = self.prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps,
-                           guidance_scale, controlnet_conditioning_scale, generator, *mask_args, masked_content=masked_content, **blend_kw)
+                           guidance_scale, controlnet_conditioning_scale, generator, mask_image, **spec.keywords())
         if output_type == "latent":
             self.run_device_graphed(job, slot) if self.use_graph else self._run_eager(job)
             res = job["_result"]

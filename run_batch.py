@@ -376,6 +376,8 @@ def process_shard(editor, entries, args, edited_dir, comparisons_dir, progress=N
 
 
 def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progress=None):
+    import fie_amd  # noqa: F401
+    from fie_amd import mask as hmask
     res = dict(processed=0, skipped=0, failed=0, total_time=0.0, rows=[])
     extra = {} if args.strength is None else {"strength": args.strength}
     bs = max(1, getattr(args, "batch_size", 1))
@@ -390,27 +392,7 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     masked = use_mask or outpaint is not None      # --outpaint: the new border is a mask
     if outpaint is not None:
         extra = dict(extra, outpaint=tuple(outpaint))
-    extra = dict(extra, **region_kwargs(args, masked), **tile_kwargs(args))
-    masked_content = getattr(args, "masked_content", "original")
-    if masked_content != "original":
-        if not masked:
-            raise ValueError("--masked_content needs --use_mask")
-        extra = dict(extra, masked_content=masked_content)
-    blend = getattr(args, "blend", "alpha")
-    if blend != "alpha":
-        if not masked:
-            raise ValueError("--blend multiband needs --use_mask")
-        extra = dict(extra, blend=blend, blend_levels=getattr(args, "blend_levels", 4))
-    mask_grow = getattr(args, "mask_grow", 0)
-    if mask_grow:
-        if not masked:
-            raise ValueError("--mask_grow needs --use_mask")
-        extra = dict(extra, mask_grow=mask_grow)
-    mask_mode, mask_ramp = getattr(args, "mask_mode", "binary"), getattr(args, "mask_ramp", 0)
-    if mask_mode != "binary" or mask_ramp:
-        if not masked:
-            raise ValueError("--mask_mode levels and --mask_ramp need --use_mask")
-        extra = dict(extra, mask_mode=mask_mode, mask_ramp=mask_ramp)
+    extra = dict(extra, **region_kwargs(args, masked), **tile_kwargs(args), **hmask.cli_keywords(args, masked, "--use_mask"))
     sweep = sweep_kwargs(args)                     # --auto_strength: one edit_sweep() per image in place of edit()
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
@@ -476,7 +458,6 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
                     print(f"\n      Error processing {image_id}: --use_mask but the entry has no `mask`")
                     res["failed"] += 1
                     continue
-                from fie_amd import mask as hmask
                 mask = hmask.rle_decode(entry["mask"], (source_img.height, source_img.width))
             pending.append((index, image_id, rel, output_path, source_img, prompt, mask))
             if len(pending) == bs:
@@ -531,29 +512,19 @@ def print_summary(tot, args, edited_dir, comparisons_dir, world, wall):
 def main(argv=None):
     parser = full_parser()
     args = parser.parse_args(argv)
+    import fie_amd  # noqa: F401
+    from fie_amd import buckets, mask as hmask
+    masked = args.use_mask or args.outpaint is not None                # --outpaint: the new border is a mask
     try:
         tile_kwargs(args)
         sweep_kwargs(args)
+        if args.region == "mask" and not masked:
+            raise ValueError("--region mask needs --use_mask")
+        hmask.cli_keywords(args, masked, "--use_mask")
     except ValueError as e:
         parser.error(str(e))
-    masked = args.use_mask or args.outpaint is not None                # --outpaint: the new border is a mask
-    if args.region == "mask" and not masked:
-        parser.error("--region mask needs --use_mask")
-    if args.masked_content != "original" and not masked:
-        parser.error("--masked_content needs --use_mask")
-    if args.blend != "alpha" and not masked:
-        parser.error("--blend multiband needs --use_mask")
-    if args.mask_grow and not masked:
-        parser.error("--mask_grow needs --use_mask")
-    if (args.mask_mode != "binary" or args.mask_ramp) and not masked:
-        parser.error("--mask_mode levels and --mask_ramp need --use_mask")
-    if args.mask_mode == "levels" and (args.mask_ramp or args.mask_grow):
-        parser.error("--mask_mode levels does not go with --mask_ramp or --mask_grow: both work on the outline and would discard the greys")
     if args.resolution != "square":
-        import fie_amd  # noqa: F401
-        from fie_amd import buckets
         args.resolution = buckets.parse(args.resolution)
-    import fie_amd  # noqa: F401
     from fie_amd import dist as fdist
     rank, local, world = fdist.init()
     say = print if rank == 0 else (lambda *a, **k: None)

@@ -201,19 +201,13 @@ def main(argv=None):
                      "input's size")
     if args.region == "mask" and not masked:
         parser.error("--region mask needs --mask")
-    if args.masked_content != "original" and not masked:
-        parser.error("--masked_content needs --mask")
-    if args.blend != "alpha" and (not masked or args.no_paste_back):
-        parser.error("--blend multiband needs --mask and the paste-back")
-    if args.mask_grow and not masked:
-        parser.error("--mask_grow needs --mask")
-    if (args.mask_mode != "binary" or args.mask_ramp) and not masked:
-        parser.error("--mask_mode levels and --mask_ramp need --mask")
-    if args.mask_mode == "levels" and (args.mask_ramp or args.mask_grow):
-        parser.error("--mask_mode levels does not go with --mask_ramp or --mask_grow: both work on the outline and would discard the greys")
+    import fie_amd  # noqa: F401
+    from fie_amd import buckets, mask as hmask
+    try:
+        mask_kw = hmask.cli_keywords(args, masked, "--mask")
+    except ValueError as e:
+        parser.error(str(e))
     if args.resolution != "square":
-        import fie_amd  # noqa: F401
-        from fie_amd import buckets
         args.resolution = buckets.parse(args.resolution)
     if args.quality_mode:
         args.full_precision = args.full_controlnet = args.no_cpu_offload = True
@@ -254,17 +248,14 @@ def main(argv=None):
             extra.update(mask=Image.open(args.mask))
         extra.update(mask_blur=args.mask_blur, paste_back=not args.no_paste_back)
         print(f"      Mask: {args.mask or 'the new border'} (blur {args.mask_blur}, paste-back {'off' if args.no_paste_back else 'on'})")
-        if args.masked_content != "original":
-            extra.update(masked_content=args.masked_content)
+        extra.update(mask_kw)
+        if "masked_content" in mask_kw:
             print(f"      Masked content: {args.masked_content}")
-        if args.blend != "alpha":
-            extra.update(blend=args.blend, blend_levels=args.blend_levels)
+        if "blend" in mask_kw:
             print(f"      Blend: {args.blend}, {args.blend_levels} levels")
-        if args.mask_grow:
-            extra.update(mask_grow=args.mask_grow)
+        if "mask_grow" in mask_kw:
             print(f"      Mask grown by: {args.mask_grow} px")
-        if args.mask_mode != "binary" or args.mask_ramp:
-            extra.update(mask_mode=args.mask_mode, mask_ramp=args.mask_ramp)
+        if "mask_mode" in mask_kw:
             print(f"      Soft mask: {'the greys as levels' if args.mask_mode == 'levels' else f'ramp over {args.mask_ramp} px'}")
     if args.resolution != "square":
         extra.update(resolution=args.resolution)

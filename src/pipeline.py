@@ -264,53 +264,49 @@ class FastEditor:
         ValueError (both work on the outline and would discard the greys).  A region and tiles ramp the whole mask first and crop second.  The
         defaults launch nothing and change nothing."""
         tiles, tile_overlap, tile_batch = htiles.check(tiles, tile_overlap, tile_batch)
-        kw = dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                  controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
-                  canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
-                  masked_content=masked_content, blend=blend, blend_levels=blend_levels)
+        scalars = self._scalars(strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold,
+                                canny_high_threshold, seed)
         if tiles is not None:
             self._check_tiled(resolution, region, outpaint, output_size)
-            masked = mask is not None
-            grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, masked)[2]
-            kw["levels"] = hmask.check_levels(mask_mode, mask_ramp, grow, masked)
-            return self._edit_tiled(image, prompt, negative_prompt, htiles.plan(image.size, tiles, tile_overlap), tile_batch,
-                                    hmask.to_l_array(mask, image.size) if masked else None, grow, metrics, kw)
         full = hregion.check_output(output_size, region)
         margins = hmask.check_outpaint(outpaint)
         masked = mask is not None or margins is not None          # the new border is a mask of its own
-        grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, masked)[2]
-        kw["levels"] = levels = hmask.check_levels(mask_mode, mask_ramp, grow, masked)
+        spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp, have_mask=masked)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
+        if tiles is not None:
+            return self._edit_tiled(image, prompt, negative_prompt, htiles.plan(image.size, tiles, tile_overlap), tile_batch, mask_l, spec, metrics,
+                                    scalars)
         if region is not None and margins is not None:            # a region crops on the host: the canvas comes back once, the rest is the call on it
             canvas, canvas_mask = self._outpaint_host(image, mask_l, margins)
-            return self.edit(Image.fromarray(canvas), prompt, negative_prompt, strength, num_inference_steps, guidance_scale,
-                             controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold, seed, canvas_mask, mask_blur, paste_back,
-                             resolution=resolution, metrics=metrics, output_size=output_size, region=region, region_padding=region_padding,
-                             masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow, mask_mode=levels[0],
-                             mask_ramp=levels[1])
+            return self.edit(Image.fromarray(canvas), prompt, negative_prompt, **scalars, mask=canvas_mask, **spec.keywords(),
+                             resolution=resolution, metrics=metrics, output_size=output_size, region=region, region_padding=region_padding)
         if region is not None:
-            if grow:        # grown first, cropped second: the box of "mask" is the grown mask's, and pixels outside an explicit box reach into it
-                mask_l = self._grow_host(mask_l, grow)
-            if levels[1]:   # ramped whole, cropped second: the crop carries its levels, and the box of "mask" comes from their support
-                mask_l = self._ramp_host(mask_l, levels[1])
-            soft = levels != ("binary", 0)
-            box = hregion.resolve(region, image.size, hmask.support_numpy(mask_l) if soft else mask_l, region_padding, resolution)
-            res = self.edit(image.crop(box), prompt, negative_prompt, strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
-                            canny_low_threshold, canny_high_threshold, seed, None if mask_l is None else mask_l[box[1]:box[3], box[0]:box[2]],
-                            mask_blur, paste_back, resolution=resolution, metrics=metrics, output_size="source", masked_content=masked_content,
-                            blend=blend, blend_levels=blend_levels, mask_mode="levels" if soft else "binary")
+            if spec.grow:   # grown first, cropped second: the box of "mask" is the grown mask's, and pixels outside an explicit box reach into it
+                mask_l = self._grow_host(mask_l, spec.grow)
+            if spec.ramp:   # ramped whole, cropped second: the crop carries its levels, and the box of "mask" comes from their support
+                mask_l = self._ramp_host(mask_l, spec.ramp)
+            box = hregion.resolve(region, image.size, hmask.support_numpy(mask_l) if spec.soft else mask_l, region_padding, resolution)
+            res = self.edit(image.crop(box), prompt, negative_prompt, **scalars, mask=None if mask_l is None else mask_l[box[1]:box[3], box[0]:box[2]],
+                            **spec.prepared().keywords(), resolution=resolution, metrics=metrics, output_size="source")
             if metrics:
                 return hregion.paste(image, res[0], box), res[1]
             return hregion.paste(image, res, box)
-        res = self._single_job(image, prompt, negative_prompt, 1, resolution, mask_l, margins, grow, metrics, full, kw)
+        res = self._single_job(image, prompt, negative_prompt, 1, resolution, mask_l, margins, spec, metrics, full, scalars)
         if not metrics:
             return res.images[0]
         return res.images[0], self._scores(res.extra, [masked])[0]
 
-    def _single_job(self, image, prompt, negative_prompt, k, resolution, mask_l, margins, grow, metrics, full, kw, select=None):
+    @staticmethod
+    def _scalars(strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold, seed):
+        """The scalar keywords of edit() under their own names: what its tails read and its re-entries pass on."""
+        return dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                    controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
+                    canny_high_threshold=canny_high_threshold, seed=seed)
+
+    def _single_job(self, image, prompt, negative_prompt, k, resolution, mask_l, margins, spec, metrics, full, kw, select=None):
         """The tail of edit() and edit_sweep() behind their argument checks: ONE device job on one image with k rows -- edit(): 1 and
         kw["strength"] a float; edit_sweep(): its variants and kw["strength"] their list of strengths.  mask_l: None or the uint8 [H, W] mask;
-        margins: check_outpaint()'s tuple or None; grow: check_grow()'s radius; kw: the scalar keywords of edit().  `select`: None, or
+        margins: check_outpaint()'s tuple or None; spec: the call's MaskSpec; kw: the scalar keywords of edit() (_scalars).  `select`: None, or
         (rule, floor, bg) of the selector that wraps the scorer (_selector).  Hooks, outermost first: _fullres, _selector, _scorer.
         -> the pipeline's result."""
         size = buckets.target_size(resolution, hmask.canvas_size(image.size, margins))
@@ -331,7 +327,7 @@ class FastEditor:
                 image, mask_l = self._outpaint_device(image, mask_l, margins)
             source_dev, control_dev, finish = self._canny_device(image, kw["canny_low_threshold"], kw["canny_high_threshold"], size=size, wait=False,
                                                                  original=origs)
-            mask_dev = self._mask_device(mask_l, size, original=omasks, grow=grow, levels=kw["levels"])
+            mask_dev = self._mask_device(mask_l, size, spec, original=omasks)
         hook = None
         if metrics:
             keep = {} if select is not None else None
@@ -339,13 +335,16 @@ class FastEditor:
             if select is not None:
                 hook = self._selector(slot, hook, keep, *select)
         if full:        # the edit-size job runs with its own paste-back off: the composite happens at the source's size, behind it, for all k rows
-            hook = self._fullres(slot, origs * k, (omasks if kw["paste_back"] else [None]) * k, kw["mask_blur"], hook)
+            hook = self._fullres(slot, origs * k, (omasks if spec.paste_back else [None]) * k, spec.blur, hook)
         return self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev, control_image=control_dev,
-                         strength=kw["strength"], num_inference_steps=kw["num_inference_steps"], guidance_scale=kw["guidance_scale"],
-                         controlnet_conditioning_scale=kw["controlnet_conditioning_scale"], generator=generator, post_check=finish,
-                         mask_image=mask_dev, mask_blur=0 if full else kw["mask_blur"], paste_back=kw["paste_back"] and not full,
-                         after_device=hook, masked_content=kw["masked_content"], blend=kw["blend"], blend_levels=kw["blend_levels"], paste_later=full,
-                         mask_mode="levels" if isinstance(mask_dev, MaskLevels) else "binary")
+                         generator=generator, post_check=finish, mask_image=mask_dev, after_device=hook, **self._job_keywords(kw, spec, full))
+
+    @staticmethod
+    def _job_keywords(kw, spec, full):
+        """The pipeline's keywords of a device job: the scalars it reads, and the spec of a mask that _mask_device has grown and ramped already,
+        with `full` in front of the source-size back end."""
+        spec = (spec.behind_fullres() if full else spec).prepared()
+        return dict({k: kw[k] for k in ("strength", "num_inference_steps", "guidance_scale", "controlnet_conditioning_scale")}, **spec.keywords())
 
     def _fullres(self, slot, origs, omasks, blur, then=None):
         """The `after_device` hook of an edit with output_size="source": queues, on the edit's stream behind its result and outside its graph, the
@@ -435,16 +434,13 @@ class FastEditor:
         full = hregion.check_output(output_size, None)
         margins = hmask.check_outpaint(outpaint)
         masked = mask is not None or margins is not None
-        grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, masked)[2]
+        spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp, have_mask=masked)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
         k = len(vs)
-        kw = dict(strength=[v[1][0] for v in vs], num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                  controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
-                  canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
-                  masked_content=masked_content, blend=blend, blend_levels=blend_levels,
-                  levels=hmask.check_levels(mask_mode, mask_ramp, grow, masked))
+        scalars = self._scalars([v[1][0] for v in vs], num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold,
+                                canny_high_threshold, seed)
         rule = None if select is None else (select, hsweep.ssim_floor(min_ssim, hmetrics.TARGET[1], hmetrics.TARGET[0]), masked)
-        res = self._single_job(image, prompt, negative_prompt, k, resolution, mask_l, margins, grow, True, full, kw, select=rule)
+        res = self._single_job(image, prompt, negative_prompt, k, resolution, mask_l, margins, spec, True, full, scalars, select=rule)
         extra, ihost = res.extra if select is not None else (res.extra, None)
         variants = [{"strength": list(v[1]), "steps": v[0], **d} for v, d in zip(vs, self._scores(extra, [masked] * k))]
         if select is None:
@@ -609,22 +605,21 @@ class FastEditor:
         canvas, canvas_mask = self._outpaint_host(image, hmask.to_l_array(mask, image.size) if mask is not None else None, margins)
         return Image.fromarray(canvas), Image.fromarray(canvas_mask)
 
-    def _mask_device(self, mask_l, size, original=None, grow=0, levels=("binary", 0)):
+    def _mask_device(self, mask_l, size, spec=hmask.MaskSpec(), original=None):
         """uint8 [H, W] mode-L mask (or None) -> u8 [size[1], size[0]] on the device: LANCZOS-resized as the source is (fie_resize_l_u8,
-        bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`).  `original`: a list that receives the mask as uploaded (or None).
-        `grow` != 0: the uploaded mask is grown by that radius first (fie_mask_grow_u8), and it is the grown one that `original` receives.
-        `mask_l` may also be a u8 [H, W] tensor already on the device (an outpainting canvas's mask): it is taken as the upload.
-        `levels`: check_levels()'s (mask_mode, mask_ramp); a soft mask comes back as MaskLevels(support, levels): the level
-        map V is the (grown) mask ramped on the device (fie_mask_ramp_u8) or, with "levels", the upload itself; `original` receives its support
-        S = 255 (V > 0), and S and V are resized separately."""
+        bit-exact with `mask.convert("L").resize(size, Image.LANCZOS)`).  `mask_l` may also be a u8 [H, W] tensor already on the device (an
+        outpainting canvas's mask): it is taken as the upload.  Under `spec` the upload is grown first (fie_mask_grow_u8), and a soft mask
+         comes back as MaskLevels(support, levels): the level map V is the grown mask ramped (fie_mask_ramp_u8) or, with
+        "levels", the upload itself, and its support S and V are resized separately.  `original`: a list that receives the mask every later
+        reader takes as the uploaded one, the grown mask or S (or None)."""
         if mask_l is None:
             if original is not None:
                 original.append(None)
             return None
         m = mask_l if torch.is_tensor(mask_l) else torch.from_numpy(mask_l).to(self.pipe.ctx.device)
-        if grow:
-            m = self.pipe.ctx.mask_grow(m, grow)
-        v = self.pipe.ctx.mask_ramp(m.contiguous(), levels[1]) if levels[1] else m.contiguous() if levels[0] == "levels" else None
+        if spec.grow:
+            m = self.pipe.ctx.mask_grow(m, spec.grow)
+        v = self.pipe.ctx.mask_ramp(m.contiguous(), spec.ramp) if spec.ramp else m.contiguous() if spec.mode == "levels" else None
         if v is not None:
             m = self.pipe.ctx.mask_support(v)
         if original is not None:
@@ -663,30 +658,26 @@ class FastEditor:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
             raise ValueError(f"{len(masks)} masks for {len(images)} images: one mask (or None) per image")
-        if htiles.check(tiles, tile_overlap, tile_batch)[0] is not None:
+        tiled = htiles.check(tiles, tile_overlap, tile_batch)[0] is not None
+        if tiled:
             self._check_tiled(resolution, region, outpaint, output_size)
-            has_mask = [masks is not None and m is not None for m in (masks or [None] * len(images))]
-            hmask.check_levels(mask_mode, mask_ramp, hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow,
-                                                                          any(has_mask))[2], any(has_mask))
-            negs = list(negative_prompts) if isinstance(negative_prompts, (list, tuple)) else [negative_prompts or ""] * len(images)
-            if len(negs) != len(images):
-                raise ValueError(f"{len(negs)} negative prompts for {len(images)} images")
-            res = []
-            for i, (im, p) in enumerate(zip(images, prompts)):         # an image whose mask is None is edited as without the mask keywords
-                mk = dict(mask=masks[i], mask_blur=mask_blur, masked_content=masked_content, blend=blend, blend_levels=blend_levels,
-                          mask_grow=mask_grow, mask_mode=mask_mode, mask_ramp=mask_ramp) if has_mask[i] else {}
-                res.append(self.edit(im, p, negs[i], strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
-                                     canny_low_threshold, canny_high_threshold, seed, paste_back=paste_back, metrics=metrics, output_size=output_size,
-                                     tiles=tiles, tile_overlap=tile_overlap, tile_batch=tile_batch, **mk))
-            return ([r[0] for r in res], [r[1] for r in res]) if metrics else res
         if isinstance(outpaint, list) and len(outpaint) != len(images):
             raise ValueError(f"{len(outpaint)} outpaint entries for {len(images)} images: one (left, top, right, bottom) or None per image")
         margins = [hmask.check_outpaint(o) for o in outpaint] if isinstance(outpaint, list) else [hmask.check_outpaint(outpaint)] * len(images)
         outpainted = any(o is not None for o in margins)
         has_mask = [(masks is not None and masks[i] is not None) or o is not None for i, o in enumerate(margins)]
-        grow = hmask.check_keywords(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, any(has_mask))[2]
-        levels = hmask.check_levels(mask_mode, mask_ramp, grow, any(has_mask))
-        soft = levels != ("binary", 0)
+        spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp,
+                                    have_mask=any(has_mask))
+        scalars = self._scalars(strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold,
+                                canny_high_threshold, seed)
+        if tiled:
+            negs = list(negative_prompts) if isinstance(negative_prompts, (list, tuple)) else [negative_prompts or ""] * len(images)
+            if len(negs) != len(images):
+                raise ValueError(f"{len(negs)} negative prompts for {len(images)} images")
+            res = [self.edit(im, p, neg, **scalars, mask=masks[i] if masked else None, **(spec if masked else spec.unmasked()).keywords(),
+                             metrics=metrics, output_size=output_size, tiles=tiles, tile_overlap=tile_overlap, tile_batch=tile_batch)
+                   for i, (im, p, neg, masked) in enumerate(zip(images, prompts, negs, has_mask))]
+            return ([r[0] for r in res], [r[1] for r in res]) if metrics else res
         regions = list(region) if isinstance(region, list) else [region] * len(images)
         if len(regions) != len(images):
             raise ValueError(f"{len(regions)} regions for {len(images)} images: one region (or None) per image")
@@ -698,25 +689,20 @@ class FastEditor:
                 if o is not None:
                     c, m = self._outpaint_host(images[i], hmask.to_l_array(cmasks[i], images[i].size) if cmasks[i] is not None else None, o)
                     canvases[i], cmasks[i] = Image.fromarray(c), m
-            return self.edit_batch(canvases, prompts, negative_prompts, strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale,
-                                   canny_low_threshold, canny_high_threshold, seed, cmasks, mask_blur, paste_back, resolution=resolution,
-                                   metrics=metrics, output_size=output_size, region=region, region_padding=region_padding,
-                                   masked_content=masked_content, blend=blend, blend_levels=blend_levels, mask_grow=grow, mask_mode=levels[0],
-                                   mask_ramp=levels[1])
+            return self.edit_batch(canvases, prompts, negative_prompts, **scalars, masks=cmasks, **spec.keywords(), resolution=resolution,
+                                   metrics=metrics, output_size=output_size, region=region, region_padding=region_padding)
         if has_region:
             mls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks or [None] * len(images), images)]
-            if grow:        # grown first, cropped second (edit())
-                mls = [m if m is None else self._grow_host(m, grow) for m in mls]
-            if levels[1]:   # ramped whole, cropped second (edit())
-                mls = [m if m is None else self._ramp_host(m, levels[1]) for m in mls]
-            boxes = [hregion.resolve(r, im.size, hmask.support_numpy(m) if soft and m is not None else m, region_padding, resolution)
+            if spec.grow:   # grown first, cropped second (edit())
+                mls = [m if m is None else self._grow_host(m, spec.grow) for m in mls]
+            if spec.ramp:   # ramped whole, cropped second (edit())
+                mls = [m if m is None else self._ramp_host(m, spec.ramp) for m in mls]
+            boxes = [hregion.resolve(r, im.size, hmask.support_numpy(m) if spec.soft and m is not None else m, region_padding, resolution)
                      for r, im, m in zip(regions, images, mls)]
             cut = lambda a, b: a if a is None or b is None else a[b[1]:b[3], b[0]:b[2]]
-            res = self.edit_batch([im if b is None else im.crop(b) for im, b in zip(images, boxes)], prompts, negative_prompts, strength,
-                                  num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold,
-                                  seed, None if masks is None else [cut(m, b) for m, b in zip(mls, boxes)], mask_blur, paste_back,
-                                  resolution=resolution, metrics=metrics, output_size="source", masked_content=masked_content,
-                                  blend=blend, blend_levels=blend_levels, mask_mode="levels" if soft and masks is not None else "binary")
+            res = self.edit_batch([im if b is None else im.crop(b) for im, b in zip(images, boxes)], prompts, negative_prompts, **scalars,
+                                  masks=None if masks is None else [cut(m, b) for m, b in zip(mls, boxes)], **spec.prepared().keywords(),
+                                  resolution=resolution, metrics=metrics, output_size="source")
             outs = [o if b is None else hregion.paste(im, o, b) for im, o, b in zip(images, res[0] if metrics else res, boxes)]
             return (outs, res[1]) if metrics else outs
         sizes = [buckets.target_size(resolution, hmask.canvas_size(im.size, o)) for im, o in zip(images, margins)]
@@ -727,17 +713,9 @@ class FastEditor:
             out, mets = [None] * len(images), [None] * len(images)
             pick = lambda seq, idx: None if seq is None else seq if isinstance(seq, str) else [seq[i] for i in idx]
             for sz, idx in groups.items():
-                res = self.edit_batch([images[i] for i in idx], [prompts[i] for i in idx], pick(negative_prompts, idx), strength=strength,
-                                      num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                                      controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
-                                      canny_high_threshold=canny_high_threshold, seed=seed, masks=pick(masks, idx), mask_blur=mask_blur,
-                                      paste_back=paste_back, resolution=sz, metrics=metrics, output_size=output_size,
-                                      masked_content=masked_content if any(has_mask[i] for i in idx) else "original",
-                                      blend=blend if any(has_mask[i] for i in idx) else "alpha",
-                                      blend_levels=blend_levels,
-                                      mask_grow=grow if any(has_mask[i] for i in idx) else 0,
-                                      mask_mode=levels[0] if any(has_mask[i] for i in idx) else "binary",
-                                      mask_ramp=levels[1] if any(has_mask[i] for i in idx) else 0,
+                res = self.edit_batch([images[i] for i in idx], [prompts[i] for i in idx], pick(negative_prompts, idx), **scalars,
+                                      masks=pick(masks, idx), **(spec if any(has_mask[i] for i in idx) else spec.unmasked()).keywords(),
+                                      resolution=sz, metrics=metrics, output_size=output_size,
                                       outpaint=[margins[i] for i in idx] if outpainted else None)
                 res, ms = res if metrics else (res, [None] * len(idx))
                 for i, r, m in zip(idx, res, ms):
@@ -746,19 +724,16 @@ class FastEditor:
         mask_ls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks, images)] if masks is not None else None
         if outpainted and mask_ls is None:
             mask_ls = [None] * len(images)
-        res, omasks = self._batch_job(images, prompts, negative_prompts, sizes[0], mask_ls, margins if outpainted else None, grow, metrics, full,
-                                      dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                                           controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
-                                           canny_high_threshold=canny_high_threshold, seed=seed, mask_blur=mask_blur, paste_back=paste_back,
-                                           masked_content=masked_content, blend=blend, blend_levels=blend_levels, levels=levels))
+        res, omasks = self._batch_job(images, prompts, negative_prompts, sizes[0], mask_ls, margins if outpainted else None, spec, metrics, full,
+                                      scalars)
         if not metrics:
             return res.images
         return res.images, self._scores(res.extra, [m is not None for m in omasks])
 
-    def _batch_job(self, images, prompts, negative_prompts, size, mask_ls, margins, grow, metrics, full, kw, after=None):
+    def _batch_job(self, images, prompts, negative_prompts, size, mask_ls, margins, spec, metrics, full, kw, after=None):
         """The single-size tail of edit_batch(): ONE device job for images that share the target `size`.  images: PIL images, or u8 [H, W, 3] tensors
         already on the device (the tiles of a tiled edit: slices of one upload); mask_ls: None, or one uint8 [H, W] array / device tensor / None per
-        image; margins: None, or check_outpaint()'s tuple / None per image; kw: the scalar keywords of edit().  `after`: an `after_device` hook that
+        image; margins: None, or check_outpaint()'s tuple / None per image; spec: the call's MaskSpec; kw: the scalar keywords of edit().  `after`: an `after_device` hook that
         stands in place of the scorer and the full-resolution back end (metrics and full are then False).  -> (the pipeline's result, the masks as
         uploaded)."""
         gens = None
@@ -780,20 +755,16 @@ class FastEditor:
                 ctls.append(c_dev)
                 if one is not None:
                     origs.append(one[0])
-            mask_devs = [self._mask_device(m, size, original=omasks, grow=grow, levels=kw["levels"]) for m in mask_ls] if mask_ls is not None else None
+            mask_devs = [self._mask_device(m, size, spec, original=omasks) for m in mask_ls] if mask_ls is not None else None
         if (metrics or full) and mask_ls is None:
             omasks = [None] * len(images)
         hook = after
         if metrics:
             hook = self._scorer(slot, origs, omasks, list(prompts))
         if full:
-            hook = self._fullres(slot, origs, omasks if kw["paste_back"] else [None] * len(images), kw["mask_blur"], hook)
-        res = self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls,
-                        strength=kw["strength"], num_inference_steps=kw["num_inference_steps"], guidance_scale=kw["guidance_scale"],
-                        controlnet_conditioning_scale=kw["controlnet_conditioning_scale"], generator=gens, mask_image=mask_devs,
-                        mask_blur=0 if full else kw["mask_blur"], paste_back=kw["paste_back"] and not full, after_device=hook,
-                        masked_content=kw["masked_content"], blend=kw["blend"], blend_levels=kw["blend_levels"], paste_later=full,
-                        mask_mode="levels" if any(isinstance(m, MaskLevels) for m in mask_devs or ()) else "binary")
+            hook = self._fullres(slot, origs, omasks if spec.paste_back else [None] * len(images), spec.blur, hook)
+        res = self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls, generator=gens,
+                        mask_image=mask_devs, after_device=hook, **self._job_keywords(kw, spec, full))
         return res, omasks
 
     def _check_tiled(self, resolution, region, outpaint, output_size):
@@ -808,10 +779,10 @@ class FastEditor:
         if output_size == "edit":
             raise ValueError("tiles with output_size='edit': a tiled edit returns the source-size image (output_size='source')")
 
-    def _edit_tiled(self, image, prompt, negative_prompt, plan, tile_batch, mask_l, grow, metrics, kw):
+    def _edit_tiled(self, image, prompt, negative_prompt, plan, tile_batch, mask_l, spec, metrics, kw):
         """edit(..., tiles=...) behind its argument checks (the docstring of edit() defines the result).  plan: tiles.plan()'s (tw, th, xs, ys);
-        mask_l: None or the uint8 [H, W] mask; grow: check_grow()'s radius; kw: the scalar keywords of edit().  Source and mask go up once and the
-        mask grows there, whole, and so does a soft mask's ramp (kw["levels"]); the tiles of a device job are contiguous copies of their boxes; each job's `after_device` hook copies its u8
+        mask_l: None or the uint8 [H, W] mask; spec: the call's MaskSpec; kw: the scalar keywords of edit().  Source and mask go up once and the
+        mask is grown and ramped there, whole; the tiles of a device job are contiguous copies of their boxes; each job's `after_device` hook copies its u8
         results into their rows of the slot's [n, th, tw, 3] buffer and keeps them off the host; the hook of the last job queues the blend (and,
         with metrics, the scorer behind it) and hands the H x W x 3 image to the pipeline's device-to-host copy."""
         tw, th, xs, ys = plan
@@ -823,11 +794,11 @@ class FastEditor:
             mask_dev = levels_dev = None
             if mask_l is not None:
                 mask_dev = torch.from_numpy(mask_l).to(ctx.device)
-                if grow:
-                    mask_dev = ctx.mask_grow(mask_dev, grow)
-                if kw["levels"] != ("binary", 0):         # a soft mask: ramped whole, once; the tiles carry crops of the levels, the scorer reads the support
-                    levels_dev = ctx.mask_ramp(mask_dev, kw["levels"][1]) if kw["levels"][1] else mask_dev
-                    mask_dev, kw = ctx.mask_support(levels_dev), dict(kw, levels=("levels", 0))
+                if spec.grow:
+                    mask_dev = ctx.mask_grow(mask_dev, spec.grow)
+                if spec.soft:                             # ramped whole, once; the tiles carry crops of the levels, the scorer reads the support
+                    levels_dev = ctx.mask_ramp(mask_dev, spec.ramp) if spec.ramp else mask_dev
+                    mask_dev = ctx.mask_support(levels_dev)
             key = (slot, n, th, tw)
             if key not in self._tile_bufs:
                 self._tile_bufs = {k: v for k, v in self._tile_bufs.items() if k[0] != slot}          # one plan's buffer per slot
@@ -853,8 +824,8 @@ class FastEditor:
             with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
                 crops = [cut(src, boxes[j]) for j in c]
                 mcrops = [cut(levels_dev if levels_dev is not None else mask_dev, boxes[j]) for j in c] if mask_dev is not None else None
-            res, _ = self._batch_job(crops, [prompt] * len(c), [negative_prompt or ""] * len(c), (tw, th), mcrops, None, 0, False, False, kw,
-                                     after=collect)
+            res, _ = self._batch_job(crops, [prompt] * len(c), [negative_prompt or ""] * len(c), (tw, th), mcrops, None, spec.prepared(), False, False,
+                                     kw, after=collect)
         if not metrics:
             return res.images[0]
         return res.images[0], self._scores(res.extra, [mask_dev is not None])[0]

@@ -2,6 +2,7 @@
 composite), a masked edit against the masked oracle, and the product surfaces (graph replay, batches, the C-ABI edit, run_batch
 --use_mask, FastEditor.edit at full size)."""
 import json
+import pprint
 
 import numpy as np
 import pytest
@@ -243,6 +244,156 @@ def test_cabi_run_edit_masked_matches_product_path(rig):
     assert np.abs(out.astype(int) - prod.astype(int)).max() <= 3
     outside = mask == 0
     assert np.array_equal(out[outside], np.asarray(img)[outside])
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the prepared jobs
+def prepared_jobs(pipe):
+    """Six prepare*() calls at 64 x 64 that between them set every mask keyword -> {name: job}.  Nothing runs on the jobs."""
+    img, img2 = synth_image(21, 64), synth_image(22, 64)
+    ctrl, ctrl2 = _ctrl(img), _ctrl(img2)
+    m = box_mask(64, 12, 8, 52, 44)
+    gen = lambda seed: torch.Generator("cpu").manual_seed(seed)
+    one = lambda **kw: pipe.prepare("a [red] circle", "", img, ctrl, generator=gen(1), **KW, **kw)
+    return dict(unmasked=one(), blur=one(mask_image=m, mask_blur=2),
+                content_blend_grow=one(mask_image=m, masked_content="fill", blend="multiband", blend_levels=3, mask_grow=4),
+                ramp=one(mask_image=m, mask_ramp=8),
+                batch=pipe.prepare_batch(["a [red] circle", "a dog"], None, [img, img2], [ctrl, ctrl2], generators=[gen(1), gen(2)],
+                                         mask_image=[m, None], masked_content="latent_noise", **KW),
+                sweep=pipe.prepare_sweep("a [red] circle", "", img, ctrl, strengths="all", generator=gen(1), mask_image=m,
+                                         **{k: v for k, v in KW.items() if k != "strength"}))
+
+
+def describe_job(job, base):
+    """What of a prepared job the graph key and the C ABI read, as plain Python values: its keys, the mask entries that are not tensors, the
+    shape and dtype of every tensor (and of every list of tensors), and the graph key's `base`."""
+    plain = lambda v: tuple(plain(x) for x in v) if isinstance(v, (tuple, list)) else v.item() if isinstance(v, np.generic) else v
+    shape = lambda t: (tuple(t.shape), str(t.dtype).replace("torch.", ""))
+    return dict(keys=sorted(job), mask_cfg=job.get("mask_cfg"), content=job.get("content"), blend=job.get("blend"), sweep=job.get("sweep"),
+                tensors={k: shape(v) for k, v in sorted(job.items()) if torch.is_tensor(v)},
+                lists={k: [shape(t) for t in v] for k, v in sorted(job.items()) if isinstance(v, list) and v and torch.is_tensor(v[0])},
+                base=plain(base))
+
+
+# recorded by running prepared_jobs() / describe_job() on the commit before MaskSpec, with `base` as run_device_graphed computed it inline
+PREPARED_JOBS = {'batch': {'base': ((64, 64), 2, (759, 499, 259), 1.5, 0.5, 0, 2, (True, 0.0, True, 'latent_noise')),
+           'blend': None,
+           'content': 'latent_noise',
+           'keys': ['cn_scale', 'content', 'content_lat', 'ctl_u8', 'eos_rows', 'guidance', 'hw', 'ids_g', 'ids_l', 'img_u8', 'mask_cfg', 'mask_l', 'mask_lat',
+                    'mask_px', 'n', 'nb', 'noises', 'steps', 't_dev', 'time_ids'],
+           'lists': {'noises': [((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'),
+                                ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32')],
+                     't_dev': [((4, 1), 'float32'), ((4, 1), 'float32'), ((4, 1), 'float32')]},
+           'mask_cfg': (0.0, True),
+           'sweep': None,
+           'tensors': {'content_lat': ((2, 64), 'uint8'),
+                       'ctl_u8': ((2, 64, 64, 3), 'uint8'),
+                       'eos_rows': ((4,), 'int32'),
+                       'ids_g': ((4, 77), 'int32'),
+                       'ids_l': ((4, 77), 'int32'),
+                       'img_u8': ((2, 64, 64, 3), 'uint8'),
+                       'mask_l': ((2, 64, 64), 'uint8'),
+                       'mask_lat': ((2, 64), 'uint8'),
+                       'mask_px': ((2, 64, 64), 'float32'),
+                       'time_ids': ((4, 6), 'float32')}},
+ 'blur': {'base': ((64, 64), 2, (759, 499, 259), 1.5, 0.5, 0, 1, (True, 2.0, True)),
+          'blend': None,
+          'content': None,
+          'keys': ['cn_scale', 'ctl_u8', 'eos_rows', 'guidance', 'hw', 'ids_g', 'ids_l', 'img_u8', 'mask_cfg', 'mask_lat', 'mask_px', 'nb', 'noises', 'steps',
+                   't_dev', 'time_ids'],
+          'lists': {'noises': [((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32')],
+                    't_dev': [((2, 1), 'float32'), ((2, 1), 'float32'), ((2, 1), 'float32')]},
+          'mask_cfg': (2.0, True),
+          'sweep': None,
+          'tensors': {'ctl_u8': ((64, 64, 3), 'uint8'),
+                      'eos_rows': ((2,), 'int32'),
+                      'ids_g': ((2, 77), 'int32'),
+                      'ids_l': ((2, 77), 'int32'),
+                      'img_u8': ((64, 64, 3), 'uint8'),
+                      'mask_lat': ((1, 64), 'uint8'),
+                      'mask_px': ((1, 64, 64), 'float32'),
+                      'time_ids': ((2, 6), 'float32')}},
+ 'content_blend_grow': {'base': ((64, 64), 2, (759, 499, 259), 1.5, 0.5, 0, 1, (True, 0.0, True, 'fill', ('multiband', 3))),
+                        'blend': ('multiband', 3),
+                        'content': 'fill',
+                        'keys': ['blend', 'blend_l', 'cn_scale', 'content', 'ctl_u8', 'eos_rows', 'guidance', 'hw', 'ids_g', 'ids_l', 'img_u8', 'mask_cfg', 'mask_l',
+                                 'mask_lat', 'mask_px', 'nb', 'noises', 'steps', 't_dev', 'time_ids'],
+                        'lists': {'noises': [((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32')],
+                                  't_dev': [((2, 1), 'float32'), ((2, 1), 'float32'), ((2, 1), 'float32')]},
+                        'mask_cfg': (0.0, True),
+                        'sweep': None,
+                        'tensors': {'blend_l': ((1, 64, 64), 'uint8'),
+                                    'ctl_u8': ((64, 64, 3), 'uint8'),
+                                    'eos_rows': ((2,), 'int32'),
+                                    'ids_g': ((2, 77), 'int32'),
+                                    'ids_l': ((2, 77), 'int32'),
+                                    'img_u8': ((64, 64, 3), 'uint8'),
+                                    'mask_l': ((1, 64, 64), 'uint8'),
+                                    'mask_lat': ((1, 64), 'uint8'),
+                                    'mask_px': ((1, 64, 64), 'float32'),
+                                    'time_ids': ((2, 6), 'float32')}},
+ 'ramp': {'base': ((64, 64), 2, (759, 499, 259), 1.5, 0.5, 0, 1, (True, 0.0, True, 'levels')),
+          'blend': None,
+          'content': None,
+          'keys': ['cn_scale', 'ctl_u8', 'eos_rows', 'guidance', 'hw', 'ids_g', 'ids_l', 'img_u8', 'lvl_lat', 'mask_cfg', 'mask_lat', 'mask_px', 'nb', 'noises',
+                   'steps', 't_dev', 'time_ids'],
+          'lists': {'noises': [((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32')],
+                    't_dev': [((2, 1), 'float32'), ((2, 1), 'float32'), ((2, 1), 'float32')]},
+          'mask_cfg': (0.0, True),
+          'sweep': None,
+          'tensors': {'ctl_u8': ((64, 64, 3), 'uint8'),
+                      'eos_rows': ((2,), 'int32'),
+                      'ids_g': ((2, 77), 'int32'),
+                      'ids_l': ((2, 77), 'int32'),
+                      'img_u8': ((64, 64, 3), 'uint8'),
+                      'lvl_lat': ((1, 64), 'uint8'),
+                      'mask_lat': ((1, 64), 'uint8'),
+                      'mask_px': ((1, 64, 64), 'float32'),
+                      'time_ids': ((2, 6), 'float32')}},
+ 'sweep': {'base': ((64, 64), 2, (999, 759, 499, 259), 1.5, 0.5, 0, 1, (True, 0.0, True), ('sweep', (4, 3, 2, 1))),
+           'blend': None,
+           'content': None,
+           'keys': ['cn_scale', 'ctl_u8', 'eos_rows', 'guidance', 'hw', 'ids_g', 'ids_l', 'img_u8', 'mask_cfg', 'mask_lat', 'mask_px', 'nb', 'noises', 'plans',
+                    'sched', 'steps', 'sweep', 't_dev', 'time_ids'],
+           'lists': {'noises': [((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'),
+                                ((1, 4, 8, 8), 'float32')],
+                     't_dev': [((2, 1), 'float32'), ((4, 1), 'float32'), ((6, 1), 'float32'), ((8, 1), 'float32')]},
+           'mask_cfg': (0.0, True),
+           'sweep': (4, 3, 2, 1),
+           'tensors': {'ctl_u8': ((64, 64, 3), 'uint8'),
+                       'eos_rows': ((2,), 'int32'),
+                       'ids_g': ((2, 77), 'int32'),
+                       'ids_l': ((2, 77), 'int32'),
+                       'img_u8': ((64, 64, 3), 'uint8'),
+                       'mask_lat': ((1, 64), 'uint8'),
+                       'mask_px': ((1, 64, 64), 'float32'),
+                       'time_ids': ((2, 6), 'float32')}},
+ 'unmasked': {'base': ((64, 64), 2, (759, 499, 259), 1.5, 0.5, 0, 1),
+              'blend': None,
+              'content': None,
+              'keys': ['cn_scale', 'ctl_u8', 'eos_rows', 'guidance', 'hw', 'ids_g', 'ids_l', 'img_u8', 'mask_cfg', 'mask_lat', 'mask_px', 'nb', 'noises', 'steps',
+                       't_dev', 'time_ids'],
+              'lists': {'noises': [((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32'), ((1, 4, 8, 8), 'float32')],
+                        't_dev': [((2, 1), 'float32'), ((2, 1), 'float32'), ((2, 1), 'float32')]},
+              'mask_cfg': None,
+              'sweep': None,
+              'tensors': {'ctl_u8': ((64, 64, 3), 'uint8'),
+                          'eos_rows': ((2,), 'int32'),
+                          'ids_g': ((2, 77), 'int32'),
+                          'ids_l': ((2, 77), 'int32'),
+                          'img_u8': ((64, 64, 3), 'uint8'),
+                          'time_ids': ((2, 6), 'float32')}}}
+
+
+def test_prepared_jobs_are_what_they_were_before_the_spec(rig):
+    """The prepare family behind MaskSpec builds the jobs it built from the loose keywords: same keys, same mask_cfg / content / blend / sweep
+    values, same tensor shapes and dtypes, and the same graph key."""
+    _, _, pipe = rig
+    jobs = prepared_jobs(pipe)
+    assert set(jobs) == set(PREPARED_JOBS)
+    for name, job in jobs.items():
+        got = describe_job(job, pipe._graph_base(job, 0))
+        assert got == PREPARED_JOBS[name], name
+        assert pprint.pformat(got) == pprint.pformat(PREPARED_JOBS[name]), name              # and of the same types: 0.0 is not 0, True is not 1
 
 
 # ------------------------------------------------------------------------------------------------------------------------ product surfaces

@@ -45,6 +45,7 @@ def main():
     import torch
     from PIL import Image
     import fie_amd  # noqa: F401
+    from fie_amd.mask import MaskSpec
     from bench import synth_item_image
     from src.pipeline import FastEditor
 
@@ -145,7 +146,7 @@ def main():
     with torch.cuda.stream(st):
         src = ctx.resize_lanczos(torch.from_numpy(np.array(img)).to(ctx.device), 1024, 1024)
         ctl = ctx.canny_device(src)
-        mdev = {"binary": ed._mask_device(m, (1024, 1024)), "levels": ed._mask_device(m, (1024, 1024), levels=("binary", args.ramp))}
+        mdev = {"binary": ed._mask_device(m, (1024, 1024)), "levels": ed._mask_device(m, (1024, 1024), MaskSpec(ramp=args.ramp))}
         gen = lambda: torch.Generator("cpu").manual_seed(42)
         jobs = {"binary": pipe.prepare(kw["prompt"], "", src, ctl, 0.8, 4, 1.5, 0.5, gen(), mdev["binary"], 0, True),
                 "levels": pipe.prepare(kw["prompt"], "", src, ctl, 0.8, 4, 1.5, 0.5, gen(), mdev["levels"], 0, True, mask_mode="levels")}
