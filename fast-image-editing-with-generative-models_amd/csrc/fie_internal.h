@@ -147,6 +147,17 @@ __device__ __forceinline__ float fie_sat448(float x) {
     const float c = fminf(fmaxf(x, -448.f), 448.f);
     return fabsf(x) <= 3.402823466e38f ? c : __builtin_nanf("");
 }
+// exp(x) for finite x (the callers clamp theirs), as accurate as the hardware's exp2 at every argument.  Under -ffp-contract=fast the compiler's inline
+// expansion of expf -- a = (x c - E) + pl with c = log2(e), E = rint(x c) and pl the rounding residue of the product x c -- has its first term
+// fused into fma(x, c, -E), which already holds the residue, and then adds pl again: the result is off by ln2 ulp(x c) / 2, up to 6 ulp at
+// |x| = 8 .. 15 (tests/test_pointwise_gpu.py measured it on the VAE posterior; a pragma does not reach the expansion).  Here the reduced
+// argument is that one fused multiply-add, written as such, plus the tail of log2(e): right whether or not anything else is contracted.
+__device__ __forceinline__ float fie_expf(float x) {
+    const float c = 0x1.715476p+0f, cc = 0x1.4ae0bep-26f;      // log2(e) = c + cc
+    const float e = rintf(x * c);
+    const float a = __builtin_fmaf(x, cc, __builtin_fmaf(x, c, -e));
+    return ldexpf(__builtin_amdgcn_exp2f(a), (int)e);
+}
 __device__ __forceinline__ float fie_silu(float x) { return x / (1.0f + __expf(-x)); }
 // exact-erf GELU.  erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, three orders below fp16 resolution): one rcp, one
 // exp and five FMAs instead of libm's branchy erff -- the GEGLU epilogue evaluates it for every FF1 output element.

@@ -53,7 +53,7 @@ __global__ void latent_prep_src_kernel(const T* moments, const float* eps_post, 
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float logvar = fminf(fmaxf(m[4 + c], -30.f), 20.f);
-            const float z0 = (m[c] + expf(0.5f * logvar) * eps_post[c * HW + i]) * sf;
+            const float z0 = (m[c] + fie_expf(0.5f * logvar) * eps_post[c * HW + i]) * sf;
             const float x = sqrt_ab * z0 + sqrt_1mab * noise[c * HW + i];
             lp[c] = x;
             zp[c] = z0;

@@ -271,7 +271,10 @@ int fie_clip_embed_f16(fie_ctx* ctx, const int32_t* ids, int B, int T, int C, co
 
 /* ---- K10 pixels.  Replaces image_processor.py::VaeImageProcessor.preprocess / postprocess.
  *   in : u8 HWC (3 ch) -> f16 NHWC padded to 8 ch; normalize != 0: x/255*2-1, else x/255; `copies` batch copies.
- *   out: f16 NHWC (ld_in channels, first 3 used) -> u8 HWC: round(clamp(x/2+0.5, 0, 1) * 255). */
+ *   out: f16 NHWC (ld_in channels, first 3 used) -> u8 HWC: round(clamp(x/2+0.5, 0, 1) * 255), evaluated in fp32 as written (x/2+0.5, the
+ *        clamp, the product, each rounded once) and rounded half to even.  +Inf -> 255, -Inf -> 0, NaN -> 0 (the clamp's max takes the 0).
+ *        For every finite f16 x this is the byte exact arithmetic gives; an fp32 x (fie_pixels_out_f32_u8) within 2^-22 of a rounding
+ *        tie (k + 0.5) / 255 * 2 - 1 gets the byte of the fp32 evaluation (tests/pointwise_check.py: pixels_out_expect). */
 int fie_pixels_in_u8_f16(fie_ctx* ctx, const uint8_t* src, int H, int W, int normalize, void* dst, int copies);
 int fie_pixels_out_f16_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, uint8_t* dst);
 
