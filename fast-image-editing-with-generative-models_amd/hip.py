@@ -1355,8 +1355,13 @@ class Context:
         _chk(lib().fie_lpips_layer_f32(self.h, _p(fa), _p(fb), p, hw, c, _p(w), _p(ws), _p(out), out.stride(0)))
         return out
 
-    def canny_device(self, rgb_u8, low=100, high=200, out=None):
-        """u8 [H, W, 3] device tensor -> u8 [H, W, 3] edge map on the device (integer exact; synchronises the stream)."""
+    def canny_device(self, rgb_u8, low=100, high=200, out=None, budget=None, workspace=None):
+        """u8 [H, W, 3] device tensor -> u8 [H, W, 3] edge map on the device (integer exact; synchronises the stream).  `budget`: None, or the
+        number of strong seeds an edge-budget Canny may keep (fie_amd/canny_auto.py: budget): the thresholds are picked on the device, (low, high)
+        give their ratio, and `self.canny_pair` holds the pair that was used; `workspace`: as canny_begin()'s."""
+        if budget is not None:
+            edges, state = self.canny_begin(rgb_u8, low, high, rounds=1, budget=budget, out=out, workspace=workspace)
+            return self.canny_finish(state)
         self.sync_stream()
         h, w, _ = rgb_u8.shape
         assert rgb_u8.is_contiguous() and rgb_u8.dtype == torch.uint8
@@ -1369,31 +1374,70 @@ class Context:
         self.canny_passes = it.value
         return out
 
-    def canny_begin(self, rgb_u8, low=100, high=200, rounds=1):
+    def _canny_words(self):
+        """The pinned words of the Canny on the current stream: 4 hysteresis flags, then the pair of an edge-budget Canny.  One set per stream
+        (edits in flight run on their own)."""
+        cache = self.__dict__.setdefault("_canny_flags", {})
+        words = cache.get(self._stream)
+        if words is None:
+            words = cache[self._stream] = torch.zeros(6, dtype=torch.int32).pin_memory()
+        return words
+
+    def canny_begin(self, rgb_u8, low=100, high=200, rounds=1, budget=None, out=None, workspace=None):
         """First half of canny_device() (include/fie.h: fie_canny_rgb_device_begin_u8): launches NMS + `rounds` rounds of four hysteresis passes + the
-        edge map and returns (edge map tensor, state) without waiting; canny_finish(state) waits and tells whether that map was final."""
+        edge map and returns (edge map tensor, state) without waiting; canny_finish(state) waits and tells whether that map was final.
+        `budget`: as canny_device()'s (fie_canny_rgb_device_begin_auto_u8: ridge + histogram, select and classify kernels in place of the NMS
+        kernel; still no wait).  `workspace`: a u8 tensor of fie_canny_auto_workspace_bytes to use (edge-budget form only)."""
         self.sync_stream()
         h, w, _ = rgb_u8.shape
         assert rgb_u8.is_contiguous() and rgb_u8.dtype == torch.uint8
-        ws = torch.empty(lib().fie_canny_workspace_bytes(h, w), device=self.device, dtype=torch.uint8)
-        out = torch.empty((h, w, 3), device=self.device, dtype=torch.uint8)
-        cache = self.__dict__.setdefault("_canny_flags", {})           # pinned flag words, one set per stream (edits in flight run on their own)
-        flags = cache.get(self._stream)
-        if flags is None:
-            flags = cache[self._stream] = torch.zeros(4, dtype=torch.int32).pin_memory()
-        _chk(lib().fie_canny_rgb_device_begin_u8(self.h, _p(rgb_u8), h, w, int(low), int(high), int(rounds), _p(ws), _p(out), flags.data_ptr()))
-        return out, (h, w, ws, out, flags, rgb_u8, int(rounds))
+        if out is None:
+            out = torch.empty((h, w, 3), device=self.device, dtype=torch.uint8)
+        assert out.is_contiguous()
+        flags = self._canny_words()
+        if budget is None:
+            ws = torch.empty(lib().fie_canny_workspace_bytes(h, w), device=self.device, dtype=torch.uint8)
+            _chk(lib().fie_canny_rgb_device_begin_u8(self.h, _p(rgb_u8), h, w, int(low), int(high), int(rounds), _p(ws), _p(out), flags.data_ptr()))
+        else:
+            ws = self._canny_auto_workspace(h, w, workspace)
+            _chk(lib().fie_canny_rgb_device_begin_auto_u8(self.h, _p(rgb_u8), h, w, int(budget), int(low), int(high), int(rounds), _p(ws), _p(out),
+                                                          flags.data_ptr()))
+        return out, (h, w, ws, out, flags, rgb_u8, int(rounds), budget is not None)
+
+    def _canny_auto_workspace(self, h, w, workspace=None):
+        need = lib().fie_canny_auto_workspace_bytes(h, w)
+        if need < 0:
+            raise ValueError(f"edge-budget Canny: no workspace for an image of {h} x {w}")
+        if workspace is None:
+            return torch.empty(need, device=self.device, dtype=torch.uint8)
+        assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= need
+        return workspace
 
     def canny_finish(self, state):
         """Waits for canny_begin's work; runs the further hysteresis rounds if its last pass had still changed something (the edge map tensor is then
-        rewritten).  Returns the tensor; `self.canny_more` = passes launched here (0: the map was final when begin's kernels ended)."""
-        h, w, ws, out, flags, _src, rounds = state
+        rewritten).  Returns the tensor; `self.canny_more` = passes launched here (0: the map was final when begin's kernels ended).  After an
+        edge-budget begin, `self.canny_pair` = the (low, high) the device used, read from the pinned words."""
+        h, w, ws, out, flags, _src, rounds, auto = state
         self.sync_stream()
         it = _I(0)
         _chk(lib().fie_canny_rgb_device_finish_u8(self.h, h, w, _p(ws), _p(out), flags.data_ptr(), ctypes.byref(it)))
         self.canny_more = it.value
         self.canny_passes = 4 * rounds + it.value
+        if auto:
+            self.canny_pair = (int(flags[4]), int(flags[5]))
         return out
+
+    def canny_thresholds(self, rgb_u8, budget, lo=100, hi=200, workspace=None):
+        """The (low, high) an edge-budget Canny of the u8 [H, W, 3] device tensor uses under `budget` and the ratio lo / hi, as Python ints
+        (fie_canny_thresholds_device_u8: ridge + histogram and select; SYNCHRONISES: the 8 bytes are read back)."""
+        self.sync_stream()
+        h, w, _ = rgb_u8.shape
+        assert rgb_u8.is_contiguous() and rgb_u8.dtype == torch.uint8
+        ws = self._canny_auto_workspace(h, w, workspace)
+        pair = torch.empty(2, device=self.device, dtype=torch.int32)
+        _chk(lib().fie_canny_thresholds_device_u8(self.h, _p(rgb_u8), h, w, int(budget), int(lo), int(hi), _p(ws), _p(pair)))
+        low, high = pair.cpu().tolist()
+        return low, high
 
     def latent_prep(self, moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in):
         self.sync_stream()
@@ -1452,6 +1496,15 @@ def canny_rgb(rgb_u8, low=100, high=200):
     out = np.empty_like(a)
     _chk(lib().fie_canny_rgb_u8(a.ctypes.data, a.shape[0], a.shape[1], int(low), int(high), out.ctypes.data))
     return out
+
+
+def canny_auto_thresholds(rgb_u8, budget, lo=100, hi=200):
+    """The (low, high) of an edge-budget Canny through the host C ABI entry (numpy uint8 HxWx3 in, two Python ints out; no device)."""
+    import numpy as np
+    a = np.ascontiguousarray(rgb_u8, dtype=np.uint8)
+    pair = (ctypes.c_int * 2)()
+    _chk(lib().fie_canny_auto_thresholds_u8(a.ctypes.data, a.shape[0], a.shape[1], int(budget), int(lo), int(hi), pair))
+    return pair[0], pair[1]
 
 
 _ctx = {}

@@ -512,6 +512,24 @@ int fie_canny_rgb_device_begin_u8(fie_ctx* ctx, const uint8_t* rgb, int H, int W
                                   int* host_flags);
 int fie_canny_rgb_device_finish_u8(fie_ctx* ctx, int H, int W, void* workspace, uint8_t* edges_rgb, int* host_flags, int* iterations);
 
+/* ---- Edge-budget Canny: the thresholds are picked per image, on the device, so that at most `budget` pixels are strong
+ * edge seeds.  r[p] = the L1 magnitude of p where p passes the non-maximum-suppression direction test, else 0 (threshold free, 0 .. 2040);
+ * high = the smallest h in 16 .. 2040 with #{p : r[p] > h} <= budget; low = high * lo / hi with (lo, hi) the caller's thresholds, swapped when
+ * lo > hi: they give only the ratio.  The edge map is Canny(low, high).  Arguments: 1 <= budget <= H W < 2^31, 0 <= lo, hi, not both 0, workspace
+ * 16-byte aligned; anything else is FIE_EINVAL.
+ *   fie_canny_auto_workspace_bytes: label map and flag words where fie_canny_rgb_device_finish_u8 expects them (that entry finishes this form
+ *     too), the pair, the u16 ridge map and the 2048-bin histogram; -1 for a bad size.
+ *   fie_canny_rgb_device_begin_auto_u8: fie_canny_rgb_device_begin_u8 with ridge + histogram, select and classify kernels in place of the NMS
+ *     kernel.  Nothing is waited for and the pair reaches the classify kernel through device memory; host_words: 6 ints of PINNED host
+ *     memory, the 4 flag words, then low and high (valid once the stream has drained).
+ *   fie_canny_thresholds_device_u8: ridge + select alone, {low, high} into pair_dev (2 ints of device memory); does not synchronise.
+ *   fie_canny_auto_thresholds_u8: the same pair on the host (rgb: host memory; out: 2 ints). */
+int64_t fie_canny_auto_workspace_bytes(int H, int W);
+int fie_canny_rgb_device_begin_auto_u8(fie_ctx* ctx, const uint8_t* rgb, int H, int W, int64_t budget, int lo, int hi, int rounds, void* workspace,
+                                       uint8_t* edges_rgb, int* host_words);
+int fie_canny_thresholds_device_u8(fie_ctx* ctx, const uint8_t* rgb, int H, int W, int64_t budget, int lo, int hi, void* workspace, int* pair_dev);
+int fie_canny_auto_thresholds_u8(const uint8_t* rgb, int H, int W, int64_t budget, int lo, int hi, int* out);
+
 /* ---- K13 LANCZOS resize on the device, bit-exact with Pillow's 8-bit resample.  Replaces
  * `image.resize((1024, 1024), Image.LANCZOS)` at src/pipeline.py:251 (the PIL image is uploaded at its own size instead).
  *   src u8 [H, W, 3] -> dst u8 [OH, OW, 3] on the device; kx/ky: int32 [OW|OH, ks] 22-bit fixed-point taps, bx/by: int32

@@ -7,7 +7,8 @@ shards the selected entries image-parallel over N GPUs (fie_amd.dist) and rank 0
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run_batch.py --model ssd-1b
 
 Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir, --dino_dir, --lpips_dir,
---auto_strength, --min_ssim, --strengths.
+--auto_strength, --min_ssim, --strengths.  FIE_CANNY_DENSITY=d in the environment runs every edit with an edge-budget Canny (FastEditor.set_canny_density;
+DESIGN.md section 22): the pair picked for each image goes into --results_json as canny_low / canny_high.
 """
 import argparse
 import json
@@ -393,6 +394,7 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
     if outpaint is not None:
         extra = dict(extra, outpaint=tuple(outpaint))
     extra = dict(extra, **region_kwargs(args, masked), **tile_kwargs(args), **hmask.cli_keywords(args, masked, "--use_mask"))
+    picked = getattr(editor, "canny_density", None) is not None     # an edge-budget Canny: every row then says which thresholds its image got
     sweep = sweep_kwargs(args)                     # --auto_strength: one edit_sweep() per image in place of edit()
     pending = []                                   # (index, image_id, rel, output_path, source_img, prompt, mask) awaiting one device job
 
@@ -420,6 +422,8 @@ def _process_entries(editor, entries, args, edited_dir, comparisons_dir, progres
                                            negative_prompts=[args.negative_prompt] * len(pending), **kw, **mkw)
             dt = (time.time() - t0) / len(pending)
             edited, scores = edited if with_metrics or sweep else (edited, [{}] * len(pending))
+            if picked:
+                scores = [dict(s, canny_low=p[0], canny_high=p[1]) if p is not None else s for s, p in zip(scores, editor.last_canny_thresholds())]
             for (index, image_id, rel, output_path, source_img, prompt, _), out, score in zip(pending, edited, scores):
                 res["total_time"] += dt
                 out.save(output_path)
@@ -586,7 +590,11 @@ def main(argv=None):
     say(f"      Parameters: steps={args.steps}, guidance={args.guidance}, control_scale={args.control_scale}")
     if args.negative_prompt:
         say(f"      Negative prompt: {args.negative_prompt}")
-    say(f"      Canny thresholds: low={args.canny_low}, high={args.canny_high}")
+    if getattr(editor, "canny_density", None) is None:
+        say(f"      Canny thresholds: low={args.canny_low}, high={args.canny_high}")
+    else:
+        say(f"      Canny thresholds: picked per image at density {editor.canny_density:g} (FIE_CANNY_DENSITY), low / high = "
+            f"{min(args.canny_low, args.canny_high)} / {max(args.canny_low, args.canny_high)} (each image's pair: --results_json)")
 
     progress = None
     if rank == 0:

@@ -153,9 +153,18 @@ def add_sweep_args(p):
     return p
 
 
+def add_canny_args(p):
+    """[additive] edge-budget Canny, kept apart from build_parser() like add_tile_args."""
+    p.add_argument("--canny_density", type=float, default=None, metavar="D",
+                   help="[additive] pick the Canny thresholds for this image, on the device, so that about this fraction of the pixels (0.001..0.25; "
+                        "0.01..0.03 on the synthetic images this was tried on) are strong edge seeds: a hazy image still gets an edge map, a noisy "
+                        "one is not nailed to its noise.  --canny_low / --canny_high then give only the ratio low / high; the pair is printed")
+    return p
+
+
 def full_parser():
     """The parser main() reads: build_parser() and every additive group."""
-    return add_sweep_args(add_tile_args(build_parser()))
+    return add_canny_args(add_sweep_args(add_tile_args(build_parser())))
 
 
 def save_plot(path, source_img, edited_img, model, prompt):
@@ -202,9 +211,10 @@ def main(argv=None):
     if args.region == "mask" and not masked:
         parser.error("--region mask needs --mask")
     import fie_amd  # noqa: F401
-    from fie_amd import buckets, mask as hmask
+    from fie_amd import buckets, canny_auto as hcanny, mask as hmask
     try:
         mask_kw = hmask.cli_keywords(args, masked, "--mask")
+        hcanny.check(args.canny_density, args.canny_low, args.canny_high)
     except ValueError as e:
         parser.error(str(e))
     if args.resolution != "square":
@@ -268,6 +278,8 @@ def main(argv=None):
         extra.update(tiles=args.tiles, tile_overlap=args.tile_overlap, tile_batch=args.tile_batch)
         extra.pop("output_size", None)
         print(f"      Tiles: {args.tiles if args.tiles == 'auto' else '%dx%d' % args.tiles}, overlap {args.tile_overlap} px, {args.tile_batch} per device job")
+    if args.canny_density is not None:
+        editor.set_canny_density(args.canny_density)
     t0 = time.time()
     variants = None
     if args.sweep:
@@ -291,6 +303,9 @@ def main(argv=None):
                                  canny_high_threshold=args.canny_high, seed=args.seed, **extra)
     elapsed = time.time() - t0
     print(f"      Editing completed in {elapsed:.2f} seconds")
+    if args.canny_density is not None:
+        for low, high in filter(None, editor.last_canny_thresholds()):
+            print(f"      Canny thresholds picked at density {args.canny_density:g}: low={low}, high={high}")
     mem = editor.get_memory_usage()
     print(f"      GPU Memory: {mem['allocated_gb']:.2f}GB allocated, {mem['reserved_gb']:.2f}GB reserved")
 

@@ -20,6 +20,7 @@ from PIL import Image
 
 import fie_amd  # noqa: F401  (alias loader for the hyphenated package directory)
 from fie_amd import buckets, hip, stack
+from fie_amd import canny_auto as hcanny
 from fie_amd import mask as hmask
 from fie_amd import metrics as hmetrics
 from fie_amd import region as hregion
@@ -50,9 +51,15 @@ class FastEditor:
     def __init__(self, model_name="sdxl", device="cuda", dtype=torch.float16, enable_cpu_offload=True,
                  use_full_precision=False, use_full_controlnet=False, *, weights_dir=None, seed_weights=1234,
                  noise_dtype=None, broadcast_weights=True, weight_dtype="f16", clip_score_dir=None, dino_dir=None, dino_layer=11,
-                 lpips_dir=None):
+                 lpips_dir=None, canny_density=None):
         if model_name not in self.MODEL_CONFIGS and model_name not in self._EXTRA_STACKS:
             raise ValueError(f"Unknown model: {model_name}. Choose from {list(self.MODEL_CONFIGS.keys())}")
+        if canny_density is None and os.environ.get("FIE_CANNY_DENSITY"):     # [additive] set_canny_density() from the start; the switch serves run_batch.py
+            try:
+                canny_density = float(os.environ["FIE_CANNY_DENSITY"])
+            except ValueError:
+                raise ValueError(f"FIE_CANNY_DENSITY={os.environ['FIE_CANNY_DENSITY']!r}: a number in [0.001, 0.25]") from None
+        self.set_canny_density(canny_density)
         self.model_name = model_name
         self.device = device
         self.dtype = torch.float32 if use_full_precision else dtype
@@ -139,7 +146,7 @@ class FastEditor:
 
     CANNY_ROUNDS = 4            # hysteresis rounds (of four passes) edit() launches without looking at the flags: weak chains across <= 15 tiles of 32x32
 
-    def _canny_device(self, image, low_threshold, high_threshold, size=None, wait=True, original=None):
+    def _canny_device(self, image, low_threshold, high_threshold, size=None, wait=True, original=None, density=None):
         """PIL -> (u8 HWC source on the device, u8 HWC edge map on the device): gray, Sobel, NMS and hysteresis run in HIP
         kernels (csrc/canny_device.hip), integer exact.  `size` = (width, height): LANCZOS-resize first, as
         `image.resize(size, Image.LANCZOS)` does -- on the device for RGB images, through PIL for any other mode.
@@ -147,7 +154,10 @@ class FastEditor:
         -- called once the stream has drained -- returns True when those rounds had NOT reached the fixed point: it has then run the
         remaining ones and rewritten the edge map, and whatever was computed from the map must be computed again.
         `original`: a list that receives the source as uploaded, before the resize (what an inline metric scores against).
-        `image` may also be a u8 [H, W, 3] tensor already on the device (an outpainting canvas): it is taken as the upload."""
+        `image` may also be a u8 [H, W, 3] tensor already on the device (an outpainting canvas): it is taken as the upload.
+        `density`: None, or the `canny_density` of an edge-budget Canny: the thresholds are picked on the device from the
+        image the Canny sees -- behind the resize -- and the two given ones are their ratio; the pair that was used is `ctx.canny_pair` behind a
+        waiting call and `finish.pair` once finish() has run."""
         if torch.is_tensor(image):
             src = image
         else:
@@ -164,19 +174,73 @@ class FastEditor:
         if size is not None and (src.shape[1], src.shape[0]) != tuple(size):
             src = self.pipe.ctx.resize_lanczos(src, size[1], size[0])
         ctx = self.pipe.ctx
+        budget = None if density is None else hcanny.budget(src.shape[0] * src.shape[1], density)
         if not wait:
-            edges, state = ctx.canny_begin(src, low_threshold, high_threshold, rounds=self.CANNY_ROUNDS)
+            edges, state = ctx.canny_begin(src, low_threshold, high_threshold, rounds=self.CANNY_ROUNDS, budget=budget)
 
             def finish():
                 with self.pipe.eager_lock:                 # the context's stream binding is shared by the threads of in-flight edits
                     ctx.canny_finish(state)
+                    if budget is not None:
+                        finish.pair = ctx.canny_pair
                     return ctx.canny_more > 0
             return src, edges, finish
-        return src, ctx.canny_device(src, low_threshold, high_threshold)
+        return src, ctx.canny_device(src, low_threshold, high_threshold, budget=budget)
 
-    def preprocess_image(self, image, low_threshold=100, high_threshold=200):
-        """PIL RGB -> 3-channel PIL Canny edge map (reference :183-210)."""
-        return Image.fromarray(self._canny_device(image, low_threshold, high_threshold)[1].cpu().numpy())
+    canny_density = None        # set_canny_density(): None, or the fraction of the pixels that may be strong edge seeds
+
+    def set_canny_density(self, canny_density):
+        """[additive] An edge-budget Canny for every later edit(), edit_batch() and edit_sweep() of this editor; None (the
+        default) switches it off again.  `canny_density` is a float in [0.001, 0.25]: about that fraction of the pixels may be strong edge seeds,
+        and the two thresholds follow per image, on the device -- a hazy photograph whose gradients stay under 200 still gets an edge map, a noisy one
+        is not nailed to its noise.  Exactly: with r the gradient magnitude of every pixel that passes the Canny's non-maximum suppression (0
+        elsewhere), N the pixels of the image the Canny sees -- behind the resize and the outpaint canvas -- and budget = max(1, N * round(10^6 d) //
+        10^6), `high` is the smallest h in 16 .. 2040 with at most budget pixels of r > h and `low` = high * lo // hi, (lo, hi) = the call's
+        `canny_low_threshold`, `canny_high_threshold` (swapped when lo > hi; integers >= 0, not both 0: a ValueError of the call otherwise), which
+        give only the ratio; the edge map is that of the two.  A call returns what it returns without the setting for `canny_low_threshold=low,
+        canny_high_threshold=high` with (low, high) = `canny_thresholds(...)`.  A region takes the statistics of its crop; a tiled edit takes ONE
+        pair from the whole source at its own size in front of the first tile job (one read-back of 8 bytes), so that the edge density does not
+        jump at a tile seam; edit_batch gives every image its own pair, edit_sweep has one.  With `metrics=True` the dict gains `canny_low` and
+        `canny_high`.  Three more launches in front of the job, no additional host wait (except the tiled edit's).  The setting belongs to the
+        editor, not to a thread: set it before the worker threads of `set_in_flight` start.  Returns the value it replaces."""
+        before, self.canny_density = self.canny_density, hcanny.check_density(canny_density)
+        return before
+
+    def last_canny_thresholds(self):
+        """[additive] Per image of the calling thread's last edit(), edit_batch() or edit_sweep(): the (low, high) its edge-budget Canny picked, or
+        None where the editor had no `canny_density` set.  Costs nothing: the pairs came to the host with the edit's result."""
+        return list(getattr(self._tls, "canny_pairs", []))
+
+    def preprocess_image(self, image, low_threshold=100, high_threshold=200, canny_density=None):
+        """PIL RGB -> 3-channel PIL Canny edge map (reference :183-210).  [additive] `canny_density`: as edit()'s, on the image as passed."""
+        density = hcanny.check(canny_density, low_threshold, high_threshold)
+        return Image.fromarray(self._canny_device(image, low_threshold, high_threshold, density=density)[1].cpu().numpy())
+
+    def canny_thresholds(self, image, canny_density, canny_low_threshold=100, canny_high_threshold=200, resolution=None, outpaint=None, mask=None, *,
+                         tiles=None):
+        """[additive] The (low, high) that `edit(image, ...)` with these arguments hands its Canny after `set_canny_density(canny_density)` (DESIGN.md
+        section 22), as two Python ints.  The statistics are taken on the image the Canny sees: the outpaint canvas when there is one, LANCZOS-resized
+        to the edit size of `resolution`; with `tiles` (any value but None) the source at its own size, as a tiled edit takes them.  `mask` is
+        checked and otherwise unused (the mask's interior counts like the rest).  One upload, the ridge + histogram and select kernels and one
+        synchronising read-back of 8 bytes: for tests and tools, not for the hot path."""
+        density = hcanny.check(canny_density, canny_low_threshold, canny_high_threshold)
+        if density is None:
+            raise ValueError("canny_thresholds: canny_density=None: a number in [0.001, 0.25]")
+        margins = hmask.check_outpaint(outpaint)
+        if tiles is not None and (resolution is not None or margins is not None):
+            raise ValueError("canny_thresholds: tiles with resolution or outpaint (a tiled edit takes neither)")
+        mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
+        size = None if tiles is not None else buckets.target_size(resolution, hmask.canvas_size(image.size, margins))
+        ctx = self.pipe.ctx
+        with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(getattr(self._tls, "slot", 0))):
+            if margins is not None:
+                src = self._outpaint_device(image, mask_l, margins)[0]
+            else:
+                src = torch.from_numpy(np.array(image if image.mode == "RGB" else image.convert("RGB"))).to(ctx.device)
+            if size is not None and (src.shape[1], src.shape[0]) != tuple(size):
+                src = ctx.resize_lanczos(src, size[1], size[0])
+            return ctx.canny_thresholds(src.contiguous(), hcanny.budget(src.shape[0] * src.shape[1], density), canny_low_threshold,
+                                        canny_high_threshold)
 
     def edit(self, image, prompt, negative_prompt="", strength=0.80, num_inference_steps=4, guidance_scale=1.5,
              controlnet_conditioning_scale=0.5, canny_low_threshold=100, canny_high_threshold=200, seed=None, mask=None, mask_blur=0,
@@ -262,10 +326,13 @@ class FastEditor:
         of the mask as passed, that is of the source image, as `mask_grow` does: on a large source the edit runs at a fraction of that size and the
         recipe is region="mask", so that the ramp spans more than a latent pixel or two.  "levels" with `mask_ramp` or with `mask_grow` is a
         ValueError (both work on the outline and would discard the greys).  A region and tiles ramp the whole mask first and crop second.  The
-        defaults launch nothing and change nothing."""
+        defaults launch nothing and change nothing.
+        [additive] `set_canny_density(d)` in front of the call: an edge-budget Canny; the two thresholds are then picked per
+        image on the device and `canny_low_threshold` / `canny_high_threshold` give only their ratio.  Without it nothing changes."""
         tiles, tile_overlap, tile_batch = htiles.check(tiles, tile_overlap, tile_batch)
         scalars = self._scalars(strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold,
                                 canny_high_threshold, seed)
+        density = self._density(scalars)
         if tiles is not None:
             self._check_tiled(resolution, region, outpaint, output_size)
         full = hregion.check_output(output_size, region)
@@ -274,8 +341,16 @@ class FastEditor:
         spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp, have_mask=masked)
         mask_l = hmask.to_l_array(mask, image.size) if mask is not None else None
         if tiles is not None:
-            return self._edit_tiled(image, prompt, negative_prompt, htiles.plan(image.size, tiles, tile_overlap), tile_batch, mask_l, spec, metrics,
-                                    scalars)
+            pair = None
+            if density is not None:                       # one pair from the whole source, handed to every tile job as explicit thresholds
+                pair = self.canny_thresholds(image, density, canny_low_threshold, canny_high_threshold, tiles=tiles)
+                scalars = dict(scalars, canny_density=None, canny_low_threshold=pair[0], canny_high_threshold=pair[1])
+            res = self._edit_tiled(image, prompt, negative_prompt, htiles.plan(image.size, tiles, tile_overlap), tile_batch, mask_l, spec, metrics,
+                                   scalars)
+            if metrics and pair is not None:
+                res[1].update(canny_low=pair[0], canny_high=pair[1])
+            self._tls.canny_pairs = [pair]
+            return res
         if region is not None and margins is not None:            # a region crops on the host: the canvas comes back once, the rest is the call on it
             canvas, canvas_mask = self._outpaint_host(image, mask_l, margins)
             return self.edit(Image.fromarray(canvas), prompt, negative_prompt, **scalars, mask=canvas_mask, **spec.keywords(),
@@ -292,9 +367,10 @@ class FastEditor:
                 return hregion.paste(image, res[0], box), res[1]
             return hregion.paste(image, res, box)
         res = self._single_job(image, prompt, negative_prompt, 1, resolution, mask_l, margins, spec, metrics, full, scalars)
+        self._tls.canny_pairs = [res.canny_pair]
         if not metrics:
             return res.images[0]
-        return res.images[0], self._scores(res.extra, [masked])[0]
+        return res.images[0], self._with_pair(self._scores(res.extra, [masked]), [res.canny_pair])[0]
 
     @staticmethod
     def _scalars(strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold, seed):
@@ -302,6 +378,21 @@ class FastEditor:
         return dict(strength=strength, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                     controlnet_conditioning_scale=controlnet_conditioning_scale, canny_low_threshold=canny_low_threshold,
                     canny_high_threshold=canny_high_threshold, seed=seed)
+
+    def _density(self, kw):
+        """The density of a device job's Canny: the editor's setting (set_canny_density), checked with the call's pair, which is then its ratio.
+        The tile jobs of a tiled edit carry `canny_density=None` in kw: their thresholds are the pair picked from the whole source."""
+        if "canny_density" in kw:
+            return kw["canny_density"]
+        return hcanny.check(self.canny_density, kw["canny_low_threshold"], kw["canny_high_threshold"])
+
+    @staticmethod
+    def _with_pair(dicts, pairs):
+        """The metric dicts with `canny_low` / `canny_high` where an image's Canny picked its own thresholds (pairs[i] not None)."""
+        for d, pair in zip(dicts, pairs):
+            if pair is not None:
+                d.update(canny_low=pair[0], canny_high=pair[1])
+        return dicts
 
     def _single_job(self, image, prompt, negative_prompt, k, resolution, mask_l, margins, spec, metrics, full, kw, select=None):
         """The tail of edit() and edit_sweep() behind their argument checks: ONE device job on one image with k rows -- edit(): 1 and
@@ -326,7 +417,7 @@ class FastEditor:
             if margins is not None:         # from here on the canvas and its mask stand where the image and the mask stood, already on the device
                 image, mask_l = self._outpaint_device(image, mask_l, margins)
             source_dev, control_dev, finish = self._canny_device(image, kw["canny_low_threshold"], kw["canny_high_threshold"], size=size, wait=False,
-                                                                 original=origs)
+                                                                 original=origs, density=self._density(kw))
             mask_dev = self._mask_device(mask_l, size, spec, original=omasks)
         hook = None
         if metrics:
@@ -336,8 +427,10 @@ class FastEditor:
                 hook = self._selector(slot, hook, keep, *select)
         if full:        # the edit-size job runs with its own paste-back off: the composite happens at the source's size, behind it, for all k rows
             hook = self._fullres(slot, origs * k, (omasks if spec.paste_back else [None]) * k, spec.blur, hook)
-        return self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev, control_image=control_dev,
-                         generator=generator, post_check=finish, mask_image=mask_dev, after_device=hook, **self._job_keywords(kw, spec, full))
+        res = self.pipe(slot=slot, prompt=prompt, negative_prompt=negative_prompt, image=source_dev, control_image=control_dev,
+                        generator=generator, post_check=finish, mask_image=mask_dev, after_device=hook, **self._job_keywords(kw, spec, full))
+        res.canny_pair = getattr(finish, "pair", None)    # an edge-budget Canny's (low, high): they came to the host with the flags
+        return res
 
     @staticmethod
     def _job_keywords(kw, spec, full):
@@ -404,7 +497,7 @@ class FastEditor:
         variants that have joined by then; with `seed`, variant i is what edit(..., strength=s_i, seed=seed) returns up to fp16 tiling effects
         (the bound of edit_batch against serial edits).  A soft mask (`mask_mode` / `mask_ramp`) is prepared once: its support does not depend
         on the step count, and every variant releases a level by its own number of steps.  The other keywords are edit()'s (`metrics` is always on; `region` and `tiles` are a
-        ValueError).
+        ValueError).  With `set_canny_density(d)` the Canny map is shared, so the sweep has ONE pair and every variant's dict reports it.
         select=None: returns (images, variants): variants[i] = {"strength": [the requested strengths of the variant], "steps": m, and the
         metrics dict edit(..., strength=s_i, metrics=True) reports}.
         select="strongest" (needs `min_ssim`): the strongest variant whose SSIM against the source -- `bg_ssim` with a mask -- is at least
@@ -439,10 +532,13 @@ class FastEditor:
         k = len(vs)
         scalars = self._scalars([v[1][0] for v in vs], num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold,
                                 canny_high_threshold, seed)
+        self._density(scalars)
         rule = None if select is None else (select, hsweep.ssim_floor(min_ssim, hmetrics.TARGET[1], hmetrics.TARGET[0]), masked)
         res = self._single_job(image, prompt, negative_prompt, k, resolution, mask_l, margins, spec, True, full, scalars, select=rule)
+        self._tls.canny_pairs = [res.canny_pair]
         extra, ihost = res.extra if select is not None else (res.extra, None)
-        variants = [{"strength": list(v[1]), "steps": v[0], **d} for v, d in zip(vs, self._scores(extra, [masked] * k))]
+        variants = [{"strength": list(v[1]), "steps": v[0], **d}
+                    for v, d in zip(vs, self._with_pair(self._scores(extra, [masked] * k), [res.canny_pair] * k))]
         if select is None:
             return res.images, variants
         index = int(ihost[0])
@@ -653,7 +749,8 @@ class FastEditor:
         image whose entry is None is treated as without the keyword, one with margins counts as masked.  Images group by the target size of their
         canvases.
         `tiles` / `tile_overlap` / `tile_batch`: as edit()'s; every image is tiled on its own (its tiles alone fill its device jobs) and the results
-        come back in input order."""
+        come back in input order.
+        With `set_canny_density(d)` every image gets its own pair of thresholds from its own statistics."""
         if len(images) != len(prompts) or not images:
             raise ValueError("images and prompts must be non-empty lists of one length")
         if masks is not None and len(masks) != len(images):
@@ -670,13 +767,17 @@ class FastEditor:
                                     have_mask=any(has_mask))
         scalars = self._scalars(strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold,
                                 canny_high_threshold, seed)
+        self._density(scalars)
         if tiled:
             negs = list(negative_prompts) if isinstance(negative_prompts, (list, tuple)) else [negative_prompts or ""] * len(images)
             if len(negs) != len(images):
                 raise ValueError(f"{len(negs)} negative prompts for {len(images)} images")
-            res = [self.edit(im, p, neg, **scalars, mask=masks[i] if masked else None, **(spec if masked else spec.unmasked()).keywords(),
-                             metrics=metrics, output_size=output_size, tiles=tiles, tile_overlap=tile_overlap, tile_batch=tile_batch)
-                   for i, (im, p, neg, masked) in enumerate(zip(images, prompts, negs, has_mask))]
+            res, pairs = [], []
+            for i, (im, p, neg, masked) in enumerate(zip(images, prompts, negs, has_mask)):
+                res.append(self.edit(im, p, neg, **scalars, mask=masks[i] if masked else None, **(spec if masked else spec.unmasked()).keywords(),
+                                     metrics=metrics, output_size=output_size, tiles=tiles, tile_overlap=tile_overlap, tile_batch=tile_batch))
+                pairs += self._tls.canny_pairs
+            self._tls.canny_pairs = pairs
             return ([r[0] for r in res], [r[1] for r in res]) if metrics else res
         regions = list(region) if isinstance(region, list) else [region] * len(images)
         if len(regions) != len(images):
@@ -710,7 +811,7 @@ class FastEditor:
         for i, sz in enumerate(sizes):
             groups.setdefault(sz, []).append(i)
         if len(groups) > 1:
-            out, mets = [None] * len(images), [None] * len(images)
+            out, mets, pairs = [None] * len(images), [None] * len(images), [None] * len(images)
             pick = lambda seq, idx: None if seq is None else seq if isinstance(seq, str) else [seq[i] for i in idx]
             for sz, idx in groups.items():
                 res = self.edit_batch([images[i] for i in idx], [prompts[i] for i in idx], pick(negative_prompts, idx), **scalars,
@@ -718,17 +819,19 @@ class FastEditor:
                                       resolution=sz, metrics=metrics, output_size=output_size,
                                       outpaint=[margins[i] for i in idx] if outpainted else None)
                 res, ms = res if metrics else (res, [None] * len(idx))
-                for i, r, m in zip(idx, res, ms):
-                    out[i], mets[i] = r, m
+                for i, r, m, pair in zip(idx, res, ms, self._tls.canny_pairs):
+                    out[i], mets[i], pairs[i] = r, m, pair
+            self._tls.canny_pairs = pairs
             return (out, mets) if metrics else out
         mask_ls = [hmask.to_l_array(m, im.size) if m is not None else None for m, im in zip(masks, images)] if masks is not None else None
         if outpainted and mask_ls is None:
             mask_ls = [None] * len(images)
         res, omasks = self._batch_job(images, prompts, negative_prompts, sizes[0], mask_ls, margins if outpainted else None, spec, metrics, full,
                                       scalars)
+        self._tls.canny_pairs = res.canny_pairs
         if not metrics:
             return res.images
-        return res.images, self._scores(res.extra, [m is not None for m in omasks])
+        return res.images, self._with_pair(self._scores(res.extra, [m is not None for m in omasks]), res.canny_pairs)
 
     def _batch_job(self, images, prompts, negative_prompts, size, mask_ls, margins, spec, metrics, full, kw, after=None):
         """The single-size tail of edit_batch(): ONE device job for images that share the target `size`.  images: PIL images, or u8 [H, W, 3] tensors
@@ -740,7 +843,8 @@ class FastEditor:
         if kw["seed"] is not None:
             gens = [torch.Generator(device=self.device).manual_seed(kw["seed"]) for _ in images]
         slot = getattr(self._tls, "slot", 0)
-        srcs, ctls = [], []
+        srcs, ctls, pairs = [], [], []
+        density = self._density(kw)
         origs, omasks = ([], []) if metrics or full else (None, None)
         with self.pipe.eager_lock, torch.cuda.stream(self.pipe.slot_stream(slot)):
             if margins is not None:         # the canvases and their masks stand where the images and the masks stood, already on the device
@@ -750,9 +854,11 @@ class FastEditor:
                         images[i], mask_ls[i] = self._outpaint_device(images[i], mask_ls[i], o)
             for im in images:
                 one = [] if metrics or full else None
-                s_dev, c_dev = self._canny_device(im, kw["canny_low_threshold"], kw["canny_high_threshold"], size=size, original=one)
+                s_dev, c_dev = self._canny_device(im, kw["canny_low_threshold"], kw["canny_high_threshold"], size=size, original=one,
+                                                  density=density)
                 srcs.append(s_dev)
                 ctls.append(c_dev)
+                pairs.append(None if density is None else self.pipe.ctx.canny_pair)
                 if one is not None:
                     origs.append(one[0])
             mask_devs = [self._mask_device(m, size, spec, original=omasks) for m in mask_ls] if mask_ls is not None else None
@@ -765,6 +871,7 @@ class FastEditor:
             hook = self._fullres(slot, origs, omasks if spec.paste_back else [None] * len(images), spec.blur, hook)
         res = self.pipe(slot=slot, prompt=list(prompts), negative_prompt=negative_prompts, image=srcs, control_image=ctls, generator=gens,
                         mask_image=mask_devs, after_device=hook, **self._job_keywords(kw, spec, full))
+        res.canny_pairs = pairs                           # per image: an edge-budget Canny's (low, high), or None
         return res, omasks
 
     def _check_tiled(self, resolution, region, outpaint, output_size):

@@ -1,4 +1,4 @@
-// ASan / UBSan driver for the host Canny entry (csrc/canny.cpp): odd sizes, 1-pixel borders, flat and noisy images.
+// ASan / UBSan driver for the host Canny entries (csrc/canny.cpp: the edge map and the edge-budget thresholds): odd sizes, 1-pixel borders, flat and noisy images.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -16,6 +16,13 @@ int main() {
             size_t edges = 0;
             for (size_t i = 0; i < out.size(); i += 3) edges += out[i] == 255;
             printf("%dx%d %s: rc %d, %zu edge pixels\n", h, w, flat ? "flat" : "noise", rc, edges);
+            // the edge-budget thresholds (fie_canny_auto_thresholds_u8): the smallest budget, a middle one and the largest
+            const long long n = (long long)h * w, budgets[3] = {1, n / 50 > 0 ? n / 50 : 1, n / 4 > 0 ? n / 4 : 1};
+            for (const long long b : budgets) {
+                int pair[2] = {-1, -1};
+                const int rc2 = fie_canny_auto_thresholds_u8(rgb.data(), h, w, b, 200, 100, pair);
+                printf("  budget %lld: rc %d, low %d, high %d\n", b, rc2, pair[0], pair[1]);
+            }
         }
     }
     return 0;
