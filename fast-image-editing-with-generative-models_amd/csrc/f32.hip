@@ -29,6 +29,7 @@ struct G32 {
 };
 
 constexpr int T = 64, KB = 16, LDS_LD = 17;
+constexpr long long MAX_M32 = 65535LL * T;            // launch32 puts M / 64 on grid.y: 4 194 240 rows
 
 template <int MODE>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(G32 p) {
@@ -191,6 +192,7 @@ int fie_gemm_f32(fie_ctx* ctx, const float* A1, int64_t lda1, int K1, const floa
                  int64_t sC2) {
     FIE_REQUIRE(ctx && A1 && W && C, "fie_gemm_f32: NULL ctx/A1/W/C");
     FIE_REQUIRE(M > 0 && N > 0 && K > 0 && K1 > 0 && K1 <= K && (K1 == K || A2), "fie_gemm_f32: bad shape M=%d N=%d K=%d K1=%d", M, N, K, K1);
+    FIE_REQUIRE(M <= MAX_M32, "fie_gemm_f32: M=%d rows exceed the %lld one launch covers (65535 row tiles of 64 on grid.y)", M, MAX_M32);
     FIE_REQUIRE(act >= FIE_ACT_NONE && act <= FIE_ACT_RELU && !(act == FIE_ACT_GEGLU && (residual || N % 2)), "fie_gemm_f32: bad epilogue");
     FIE_REQUIRE(nb1 >= 1 && nb2 >= 1 && (int64_t)nb1 * nb2 <= 65535, "fie_gemm_f32: bad batch %d x %d", nb1, nb2);
     FIE_REQUIRE(!rowbias || rows_per_batch > 0, "fie_gemm_f32: rowbias needs rows_per_batch");
@@ -209,7 +211,11 @@ int fie_conv3x3_nhwc_f32(fie_ctx* ctx, const float* X, int B, int H, int W, int 
     FIE_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (stride == 1 || stride == 2) && (pad_mode == 0 || pad_mode == 1) &&
                     act >= FIE_ACT_NONE && act <= FIE_ACT_RELU && act != FIE_ACT_GEGLU && ldw >= 9 * Cin, "fie_conv3x3_nhwc_f32: bad argument");
     const int ups = upsample2x ? 1 : 0, pads = pad_mode == 0 ? 2 : 1;
+    FIE_REQUIRE((H << ups) + pads >= 3 && (W << ups) + pads >= 3, "fie_conv3x3_nhwc_f32: a %d x %d map has no output pixel with pad_mode %d", H << ups, W << ups, pad_mode);
     const int OH = ((H << ups) + pads - 3) / stride + 1, OW = ((W << ups) + pads - 3) / stride + 1;
+    const long long rows = (long long)B * OH * OW;
+    FIE_REQUIRE(rows <= MAX_M32, "fie_conv3x3_nhwc_f32: M=%lld output pixels (B=%d x %d x %d) exceed the %lld one launch covers (65535 row tiles of 64 on grid.y)",
+                rows, B, OH, OW, MAX_M32);
     G32 a = {};
     a.A1 = X; a.H = H; a.W = W; a.Cin = Cin; a.OH = OH; a.OW = OW; a.stride = stride; a.pt = a.pl = pad_mode == 0 ? 1 : 0; a.ups = ups;
     a.Wt = Wkc; a.ldw = ldw; a.C = Y; a.ldc = ldc; a.M = B * OH * OW; a.N = Cout; a.K = 9 * Cin; a.K1 = a.K;

@@ -675,3 +675,83 @@ def test_mask_prep_fill_and_composite(fie):
     want = masked_oracle.composite(dec[..., :3].float().permute(0, 3, 1, 2), s8.numpy(), m.numpy())
     hard = (m.numpy() == 0) | (m.numpy() == 1)
     assert np.array_equal(got[:, :16], s8.numpy()[:, :16]) and np.array_equal(got[hard], want[hard]) and np.abs(got.astype(int) - want.astype(int)).max() <= 1
+
+
+# ------------------------------------------------------------------------------------------------------------------------ fp32 entries (csrc/f32.hip)
+F32 = dict(dtype=torch.float32)
+
+
+@pytest.fixture(scope="module")
+def f32ctx():
+    import fie_amd  # noqa: F401
+    from fie_amd import hip
+    return hip.context(0, torch.float32)
+
+
+def rnd32(*shape, seed=0, scale=1.0):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
+
+
+@pytest.mark.parametrize("m,n,k1,k2", [(67, 40, 17, 23), (130, 65, 16, 1), (3, 200, 72, 8)])
+def test_gemm_f32_strided_operands_and_a_column_range(f32ctx, m, n, k1, k2):
+    """fie_gemm_f32 with A1, A2, the weights, the row bias and the residual each inside its own moat (independent row strides) and the output a column
+    range of a three times wider tensor; the bar of tests/test_fp32_gpu.py (2e-5)."""
+    from fie_amd import hip
+    a1, a2, w = rnd32(m, k1, seed=1), rnd32(m, k2, seed=2), rnd32(n, k1 + k2, seed=3, scale=(k1 + k2) ** -0.5)
+    bias, res, rpb = rnd32(n, seed=4), rnd32(m, n, seed=5), 7
+    rb = rnd32((m + rpb - 1) // rpb, n, seed=6)
+    ref = F.relu(torch.cat([a1, a2], 1) @ w.T + bias + rb.repeat_interleave(rpb, 0)[:m]) * 0.5 + res
+    out = isolated(lambda i, o: f32ctx.gemm_f32(i["a1"], i["w"], n, out=o, a2=i["a2"], bias=i["bias"], rowbias=i["rb"], rows_per_batch=rpb, residual=i["res"],
+                                                scale=0.5, act=hip.ACT_RELU),
+                   {"a1": wide(dev(a1), 64), "a2": wide(dev(a2), 128), "w": wide(dev(w), 32), "bias": dev(bias), "rb": wide(dev(rb), 16), "res": wide(dev(res), 96)},
+                   dict(shape=(m, n), ld=3 * n + 4, **F32))
+    assert rel_err(out, ref) < 2e-5
+
+
+@pytest.mark.parametrize("case,cout", [((2, 9, 7, 8, 24, 1, 0, False), 24), ((2, 9, 7, 24, 65, 2, 1, False), 65), ((1, 4, 5, 8, 3, 1, 0, True), 3)])
+def test_conv3x3_f32_channel_range(f32ctx, case, cout):
+    """fie_conv3x3_nhwc_f32 writing channels of a wider NHWC tensor (the Fire modules' expand branch): two images, so that a padding tap that addresses a
+    neighbour lands in the other image or in the moat."""
+    b, h, w, cin, _, stride, pad_mode, ups = case
+    x, wt, bias = rnd32(b, h, w, cin, seed=1), rnd32(cout, cin, 3, 3, seed=2, scale=(9 * cin) ** -0.5), rnd32(cout, seed=3)
+    xi = x.permute(0, 3, 1, 2)
+    if ups:
+        xi = F.interpolate(xi, scale_factor=2.0, mode="nearest")
+    if pad_mode == 1:
+        xi = F.pad(xi, (0, 1, 0, 1))
+    ref = F.conv2d(xi, wt, bias, stride=stride, padding=1 if pad_mode == 0 else 0).permute(0, 2, 3, 1).contiguous()
+    wp = wt.permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous()
+    out = isolated(lambda i, o: f32ctx.conv3x3_f32(i["x"], i["w"], cout, o, stride=stride, pad_mode=pad_mode, upsample=ups, bias=i["bias"]),
+                   {"x": flat(dev(x)), "w": wide(dev(wp), 32), "bias": dev(bias)}, dict(shape=tuple(ref.shape), ld=cout + 40, **F32))
+    assert rel_err(out, ref) < 2e-5
+
+
+@pytest.mark.parametrize("rows,cols,causal,tq", [(5, 65, False, 1), (130, 200, True, 77), (7, 1025, True, 7)])
+def test_softmax_rows_f32_in_place(f32ctx, rows, cols, causal, tq):
+    from fie_amd import hip
+    s = rnd32(rows, cols, seed=1, scale=3.0)
+    x = s * 0.125
+    if causal:
+        x = x.masked_fill(torch.arange(cols)[None, :] > (torch.arange(rows) % tq)[:, None], float("-inf"))
+    ref = torch.softmax(x, -1)
+
+    def fn(i, o):
+        o.copy_(i["s"])
+        f32ctx.sync_stream()
+        hip._chk(hip.lib().fie_softmax_rows_f32(f32ctx.h, hip._p(o), rows, cols, o.stride(0), 0.125, int(causal), tq))
+
+    out = isolated(fn, {"s": dev(s)}, dict(shape=(rows, cols), ld=cols + 12, **F32))
+    assert rel_err(out, ref) < 2e-5
+
+
+@pytest.mark.parametrize("case", [(2, 3, 77, 77, 64, True), (2, 2, 33, 33, 40, False), (1, 1, 20, 20, 512, False)])
+def test_attention_f32_fused_qkv(f32ctx, case):
+    """The fp32 composition (Q K^T, softmax, P V) on one fused-QKV buffer inside a moat: three column slices with the row stride 3 C + the gap."""
+    b, hn, tq, tk, d, causal = case
+    c = hn * d
+    q, k, v = rnd32(b * tq, c, seed=1), rnd32(b * tk, c, seed=2), rnd32(b * tk, c, seed=3)
+    sp = lambda x, t: x.view(b, t, hn, d).transpose(1, 2)
+    ref = F.scaled_dot_product_attention(sp(q, tq), sp(k, tk), sp(v, tk), is_causal=causal).transpose(1, 2).reshape(b * tq, c)
+    out = isolated(lambda i, o: f32ctx.attention(i["qkv"][:, :c], i["qkv"][:, c:2 * c], i["qkv"][:, 2 * c:], hn, d, tq, tk, b, causal=causal, out=o),
+                   {"qkv": dev(torch.cat([q, k, v], 1))}, dict(shape=(b * tq, c), ld=c + 12, **F32))
+    assert rel_err(out, ref) < 2e-5
