@@ -916,6 +916,25 @@ class Context:
         _chk(lib().fie_mask_ramp_u8(self.h, _p(mask_l), h, w, int(radius), _p(out)))
         return out
 
+    def kv_emphasis(self, x, w, vflags):
+        """Prompt emphasis on a text K | V result, in place (fie_kv_emphasis): x [rows, ncols] in the context's dtype with
+        unit column stride and a row stride that is a multiple of 8; w f32 [rows] on the device, one weight per text row; vflags u8 [ncols / 8]
+        on the device, non-zero over the V columns.  Flagged columns of every row with w != 1 are multiplied by its weight (one fp32 multiply,
+        one rounding); rows of weight 1 and unflagged columns keep their bits.  One launch, no synchronisation.  -> x."""
+        self.sync_stream()
+        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != self.dtype or x.stride(1) != 1:
+            raise ValueError(f"kv_emphasis: a [rows, ncols] {self.dtype} tensor with unit column stride, got {tuple(getattr(x, 'shape', ()))} "
+                             f"{getattr(x, 'dtype', type(x).__name__)}")
+        rows, ncols = x.shape
+        if not torch.is_tensor(w) or w.dtype != torch.float32 or w.dim() != 1 or w.numel() != rows or not w.is_contiguous():
+            raise ValueError(f"kv_emphasis: w must be a contiguous f32 [{rows}] tensor, one weight per row")
+        if not torch.is_tensor(vflags) or vflags.dtype != torch.uint8 or vflags.dim() != 1 or vflags.numel() * 8 != ncols or not vflags.is_contiguous():
+            raise ValueError(f"kv_emphasis: vflags must be a contiguous u8 [{ncols // 8}] tensor, one flag per 8 columns of {ncols}")
+        if w.device != x.device or vflags.device != x.device:
+            raise ValueError("kv_emphasis: w and vflags live on the device of x")
+        _chk(lib().fie_kv_emphasis(self.h, _p(x), x.stride(0), rows, ncols, _p(w), _p(vflags), int(self.f32)))
+        return x
+
     def mask_support(self, levels, out=None):
         """The support of a level map: u8 of any shape (contiguous) -> u8 of that shape, 255 where the level is > 0 (fie_mask_support_u8)."""
         self.sync_stream()

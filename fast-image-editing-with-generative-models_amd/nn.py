@@ -12,7 +12,7 @@ Activations are NHWC fp16 ([B, H, W, C]; token views [B*H*W, C] share the same m
 """
 import torch
 
-from . import hip
+from . import emphasis, hip
 from .presets import time_embed_dim
 
 F16 = torch.float16
@@ -167,6 +167,8 @@ class TBlock:
         self.kv2 = Linear(ctx, None, None, w=self._kv_raw)
         # the net's grouped text K/V projection (_CondNet._finish_kv): this block's columns of the one [2 x 77, sum 2c] result; None: the block projects its own
         self.kv_net, self.kv_slot = None, None
+        # prompt emphasis: the net whose `emph` (begin_image) weighs this block's V rows, and the flag table of its own [K | V]
+        self.emph_net, self.kv_flags = None, None
         self.o2 = Linear(ctx, sd, p + "attn2.to_out.0")
         self.ff1 = Linear(ctx, sd, p + "ff.net.0.proj", geglu=True)
         self.ff2 = Linear(ctx, sd, p + "ff.net.2")
@@ -190,15 +192,23 @@ class TBlock:
         """Cross-attention K | V of the text, [B * 77, 2 c]: invariant over the denoising steps of one image, so computed once per image -- and for ALL blocks
         of the net in ONE GEMM (M = B * 77 rows against the concatenated to_k / to_v matrices: one pass over the weights at HBM rate instead of 20-36 launches
         of 16 us at 0.04 of the MFMA peak); a block takes its column range of the result.  `text` holds the rows of ALL images of the job and so does the
-        cache: a step that runs a leading slice of them (a strength sweep's ragged steps, pipe.py) reads the leading batch * text_len rows."""
+        cache: a step that runs a leading slice of them (a strength sweep's ragged steps, pipe.py) reads the leading batch * text_len rows.
+        Prompt emphasis: where the net carries weights (`emph`, f32 [B * 77] on the device, from begin_image), the V columns of
+        the rows whose weight is not 1 are scaled HERE, once, where the cache is filled (fie_kv_emphasis: one launch on the grouped result, one per
+        block on the per-block path) -- every reader of the cache, the fp8-activation block included, then attends to the weighted V."""
         if self.kv_cache is None:
             net = self.kv_net
+            emph = self.emph_net.emph if self.emph_net is not None else None
             if net is not None and ctx.kv_group and not ctx.calib:
                 if net._kv_out is None:
                     net._kv_out = net.kv_all(ctx, text)
+                    if emph is not None:
+                        ctx.kv_emphasis(net._kv_out, emph, net.kv_flags)
                 self.kv_cache = net._kv_out[:, self.kv_slot[0]:self.kv_slot[1]]
             else:
                 self.kv_cache = self.kv2(ctx, text)
+                if emph is not None:
+                    ctx.kv_emphasis(self.kv_cache, emph, self.kv_flags)
         return self.kv_cache
 
     def _call_a8(self, ctx, h, text, batch, tokens, text_len):
@@ -339,6 +349,14 @@ class _CondNet:
         ctx = self.ctx
         blocks = [b for t in self.transformers() for b in t.blocks]
         self.kv_all, self._kv_out = None, None
+        # prompt emphasis: the per-8-column V flags of the grouped result and of one block's own [K | V] (one table per width), built once
+        self.emph, per_c = None, {}
+        flags = lambda cs: torch.from_numpy(emphasis.v_flags(cs)).to(ctx.device)
+        for b in blocks:
+            if b.c not in per_c:
+                per_c[b.c] = flags([b.c])
+            b.emph_net, b.kv_flags = self, per_c[b.c]
+        self.kv_flags = flags([b.c for b in blocks]) if blocks else None
         if len(blocks) > 1 and not ctx.f32 and not ctx.w8 and all(b._kv_raw is not None for b in blocks):
             self.kv_all = Linear(ctx, None, None, w=torch.cat([b._kv_raw for b in blocks], 0))
             off = 0
@@ -357,9 +375,11 @@ class _CondNet:
             if t:
                 yield t
 
-    def begin_image(self, pooled, time_ids):
-        """Per-image invariants: the text-time addition embedding; drops the cross-attention K/V caches."""
+    def begin_image(self, pooled, time_ids, emph=None):
+        """Per-image invariants: the text-time addition embedding; drops the cross-attention K/V caches.  `emph`: None, or the prompt-emphasis
+        weights of the job's text rows, f32 [B * 77] on the device: the next fill of the caches scales its V rows by them."""
         ctx, cfg = self.ctx, self.cfg
+        self.emph = emph
         b = pooled.shape[0]
         ad = cfg["addition_time_embed_dim"]
         add_in = ctx._alloc((b, cfg["projection_class_embeddings_input_dim"]))

@@ -12,6 +12,7 @@ import torch
 from PIL import Image
 
 from . import cabi, hip
+from . import emphasis as hemph
 from . import mask as hmask
 from .clip import ClipText, eos_positions
 from .lcm import LCMSchedule
@@ -44,6 +45,10 @@ class MaskLevels:
 
 
 class HipImg2ImgPipeline:
+    # [additive] Prompt emphasis: None (off: prompts are tokenised as they are), or the weight in [0, 8] of the words a prompt
+    # marks with [...]; `(words:1.3)` then carries its own.  Read on the host when a job is prepared (FastEditor.set_prompt_emphasis sets it).
+    prompt_emphasis = None
+
     def __init__(self, ctx, cfgs, sds, tokenizers=None, sched_cfg=None, noise_dtype=None, weight_dtype="f16"):
         """cfgs / sds: dicts with keys unet, controlnet, vae, clip_l, clip_g (configs / diffusers-named state dicts).
         weight_dtype "f8e4m3" (BASELINE config 5): the Linear / conv weights of the UNet and the ControlNet are stored as fp8 e4m3
@@ -238,14 +243,27 @@ class HipImg2ImgPipeline:
         u8 = lambda im: im.to(dev).contiguous() if torch.is_tensor(im) else torch.from_numpy(np.array(im.convert("RGB"))).to(dev)
         n_noise = 2 + sum(1 for st in steps if not st["last"])
         nb = 2 if do_cfg else 1
-        ids_g = self.tok_g(texts)
+        # prompt emphasis: None reads no marks -- the prompts go to the tokenizers as they are; a setting tokenises the
+        # prompts with their marks stripped and gives every text row a weight, `emph` f32 [nb * 77], or None when all of them are 1
+        emph = None
+        if self.prompt_emphasis is None:
+            ids_g, ids_l = self.tok_g(texts), self.tok_l(texts)
+        else:
+            setting = hemph.check(self.prompt_emphasis)
+            (ids_g, w_g), (ids_l, w_l) = self.tok_g.weighted(texts, setting), self.tok_l.weighted(texts, setting)
+            if not np.array_equal(w_g, w_l):          # one weight per text row serves the concatenated embedding: both encoders tokenise alike
+                raise ValueError("prompt emphasis: the two tokenizers split the prompt differently")
+            emph = hemph.row_weights(w_l)
         eos = eos_positions(ids_g, self.cfgs["clip_g"]["eos_token_id"])                 # pooled-token column per row
         # the three prompt-dependent int32 tensors travel in ONE host-to-device copy (each pageable copy is a host-synchronous ~40 us); what depends on
         # the size and the step plan only (time ids, timesteps) is uploaded once per (size, plan) and shared by every later job
-        ids_l = self.tok_l(texts).to(torch.int32)
+        ids_l = ids_l.to(torch.int32)
         ids_g32 = ids_g.to(torch.int32)
         eos_rows = (torch.arange(nb) * ids_g.shape[1] + eos).to(torch.int32)
-        packed = torch.cat([ids_l.reshape(-1), ids_g32.reshape(-1), eos_rows.reshape(-1)]).to(dev)
+        parts = [ids_l.reshape(-1), ids_g32.reshape(-1), eos_rows.reshape(-1)]
+        if emph is not None:                              # the weights ride in the same copy, bit-cast
+            parts.append(torch.from_numpy(emph.view(np.int32)))
+        packed = torch.cat(parts).to(dev)
         n_l, n_g = ids_l.numel(), ids_g32.numel()
         ckey = (h, w, nb, tuple(float(st["t"]) for st in steps), str(dev))
         const = self._job_consts.get(ckey)
@@ -255,7 +273,8 @@ class HipImg2ImgPipeline:
             const = self._job_consts[ckey] = (torch.tensor([[h, w, 0, 0, h, w]], dtype=torch.float32).repeat(nb, 1).to(dev),
                                               [torch.full((nb, 1), float(st["t"]), dtype=torch.float32).to(dev) for st in steps])
         return dict(
-            ids_l=packed[:n_l].view(ids_l.shape), ids_g=packed[n_l:n_l + n_g].view(ids_g32.shape), eos_rows=packed[n_l + n_g:],
+            ids_l=packed[:n_l].view(ids_l.shape), ids_g=packed[n_l:n_l + n_g].view(ids_g32.shape), eos_rows=packed[n_l + n_g:n_l + n_g + nb],
+            **({} if emph is None else dict(emph=packed[n_l + n_g + nb:].view(torch.float32))),     # none: the job is what it was
             img_u8=u8(image), ctl_u8=u8(control_image), hw=(h, w), steps=steps, nb=nb,
             guidance=float(guidance_scale), cn_scale=float(controlnet_conditioning_scale),
             time_ids=const[0], t_dev=const[1],
@@ -333,6 +352,9 @@ class HipImg2ImgPipeline:
         for k in ("ids_l", "ids_g", "time_ids"):
             job[k] = torch.cat([j[k] for j in jobs], dim=0)
         job["eos_rows"] = torch.cat([j["eos_rows"] + i * nb * t77 for i, j in enumerate(jobs)])
+        if any(j.get("emph") is not None for j in jobs):  # prompt emphasis: every image its own weights; an image without a weighted token has ones
+            ones = torch.ones(nb * t77, device=self.ctx.device, dtype=torch.float32)
+            job["emph"] = torch.cat([j["emph"] if j.get("emph") is not None else ones for j in jobs])
         job["img_u8"] = torch.stack([j["img_u8"] for j in jobs])
         job["ctl_u8"] = torch.stack([j["ctl_u8"] for j in jobs])
         job["t_dev"] = [t.repeat(n, 1) for t in jobs[0]["t_dev"]]
@@ -424,8 +446,8 @@ class HipImg2ImgPipeline:
             text = torch.cat([pl, pg], dim=1)
             # 6. per-image invariants: nothing here depends on the latents, so the whole block rides on the side stream beside the VAE
             # encode (text-time addition embeddings, the ControlNet's edge-map embedding, the first step's timestep projections)
-            self.unet.begin_image(pooled, job["time_ids"])
-            self.controlnet.begin_image(pooled, job["time_ids"])
+            self.unet.begin_image(pooled, job["time_ids"], emph=job.get("emph"))       # emph: prompt emphasis, the weight of every text row
+            self.controlnet.begin_image(pooled, job["time_ids"], emph=job.get("emph"))
             # the edge-map embedding is the same for the CFG rows of an image: computed once per image, then repeated (upstream runs
             # it on the duplicated batch; the values are identical)
             conds = [ctx.pixels_in(ctls[i], False) for i in range(n)]
@@ -543,8 +565,9 @@ class HipImg2ImgPipeline:
                 pg, pooled = self.clip_g(job["ids_g"], eos_rows=job["eos_rows"])
             # one prompt pair: its nb rows stand for every variant (torch copies, as the CFG repeat of the edge-map embedding is)
             text = torch.cat([pl, pg], dim=1).repeat(k, 1)
+            emph = None if job.get("emph") is None else job["emph"].repeat(k)     # prompt emphasis: the one prompt pair's weights, as its text rows
             for net in (self.unet, self.controlnet):
-                net.begin_image(pooled, job["time_ids"])
+                net.begin_image(pooled, job["time_ids"], emph=emph)
                 net.add_emb = net.add_emb.repeat(k, 1)
             cond_emb = self.controlnet.cond_embedding(ctx.pixels_in(ctl, False)).repeat_interleave(k * nb, dim=0)
             tb0 = (self.unet.time_rowbias(job["t_dev"][0]), self.controlnet.time_rowbias(job["t_dev"][0]))
@@ -703,6 +726,8 @@ class HipImg2ImgPipeline:
                            + (("levels",) if job.get("lvl_lat") is not None else ()),)
         if job.get("sweep"):                             # a strength sweep: + the step counts of its variants
             base = base + (("sweep", job["sweep"]),)
+        if job.get("emph") is not None:                  # prompt emphasis: + one flag (the weights are graph inputs); an un-weighted key is what it was
+            base = base + ("emph",)
         return base
 
     def run_device_graphed(self, job, slot=0):
@@ -752,8 +777,8 @@ class HipImg2ImgPipeline:
         return out
 
     def _tensor_keys(self, job):
-        """The job tensors a graph reads from its static buffers: the mask tensors of a masked job join them."""
-        return self._TENSOR_KEYS + tuple(k for k in self._MASK_KEYS if job.get(k) is not None)
+        """The job tensors a graph reads from its static buffers: the mask tensors of a masked job and the weights of an emphasised prompt join them."""
+        return self._TENSOR_KEYS + tuple(k for k in self._MASK_KEYS + ("emph",) if job.get(k) is not None)
 
     def _capture(self, key, job, slot):
         static = dict(job)

@@ -10,11 +10,18 @@ The CLIP BPE vocabulary is not in the reference tree nor in this image, so two t
                                              ftfy / BasicTokenizer cleaning; on plain prompts such as PIE-Bench's it agrees.)
   * StandInTokenizer                      -- deterministic stand-in (SURVEY 8d "Tokens"): BOS, one id per whitespace
                                              word = crc32(word) mod 49406, EOS, padded to 77.  "synthetic tokenisation".
-Both truncate to 77 and pad with `pad_id` (49407 for encoder 1, 0 for encoder 2)."""
+Both truncate to 77 and pad with `pad_id` (49407 for encoder 1, 0 for encoder 2).
+
+Prompt emphasis: `weighted(texts, w)` is the second entry of both -- the ids of the prompts with their marks stripped
+(fie_amd/emphasis.py: parse) and one weight per token.  A tokenizer normalises first and parses second, so that the character offsets of the marks
+survive the normalisation (lower-casing can change a string's length; the marks are ASCII and normalise to themselves); a token carries the weight of the
+first character of the piece it came from, BOS, EOS and padding carry 1.  `__call__` does not read marks."""
 import json
 import re
 import unicodedata
 import zlib
+
+import numpy as np
 
 try:                    # \p{L} / \p{N} classes need the third-party `regex` module (installed with transformers)
     import regex as _re_u
@@ -40,6 +47,22 @@ class StandInTokenizer:
             ids = [BOS] + [zlib.crc32(w.encode("utf-8")) % BOS for w in t.lower().split()][: MAXLEN - 2] + [EOS]
             out[i, : len(ids)] = torch.tensor(ids)
         return out
+
+    def weighted(self, texts, w):
+        """(ids int64 [n, 77], weights float32 [n, 77] as numpy) under the emphasis setting `w`: ids = self(stripped prompts); a whitespace word
+        carries the weight of its first character."""
+        from . import emphasis
+        if isinstance(texts, str):
+            texts = [texts]
+        out = torch.full((len(texts), MAXLEN), self.pad_id, dtype=torch.int64)
+        wts = np.ones((len(texts), MAXLEN), np.float32)
+        for i, t in enumerate(texts):
+            t, cw = emphasis.parse(t.lower(), w)
+            words = list(re.finditer(r"\S+", t))[: MAXLEN - 2]
+            ids = [BOS] + [zlib.crc32(m.group(0).encode("utf-8")) % BOS for m in words] + [EOS]
+            out[i, : len(ids)] = torch.tensor(ids)
+            wts[i, 1:1 + len(words)] = [cw[m.start()] for m in words]
+        return out, wts
 
 
 def _bytes_to_unicode():
@@ -110,3 +133,28 @@ class BpeTokenizer:
             ids = ids[: MAXLEN - 1] + [self.eos]
             out[i, : len(ids)] = torch.tensor(ids)
         return out
+
+    def weighted(self, texts, w):
+        """(ids int64 [n, 77], weights float32 [n, 77] as numpy) under the emphasis setting `w`: ids = self(stripped prompts); every token of a
+        piece of the split pattern carries the weight of the piece's first character."""
+        from . import emphasis
+        if isinstance(texts, str):
+            texts = [texts]
+        out = torch.full((len(texts), MAXLEN), self.pad_id, dtype=torch.int64)
+        wts = np.ones((len(texts), MAXLEN), np.float32)
+        for i, t in enumerate(texts):
+            t, cw = emphasis.parse(re.sub(r"\s+", " ", unicodedata.normalize("NFC", t)).lower(), w)
+            ids, tw = [self.bos], [1.0]
+            for m in self.pat.finditer(t):
+                tok = m.group(0)
+                if tok in ("<|startoftext|>", "<|endoftext|>"):
+                    piece = [self.vocab.get(tok, self.unk)]
+                else:
+                    tok = "".join(self.b2u[b] for b in tok.encode("utf-8"))
+                    piece = [self.vocab.get(p, self.unk) for p in self._bpe(tok)]
+                ids += piece
+                tw += [cw[m.start()]] * len(piece)
+            ids, tw = ids[: MAXLEN - 1] + [self.eos], tw[: MAXLEN - 1] + [1.0]
+            out[i, : len(ids)] = torch.tensor(ids)
+            wts[i, : len(tw)] = tw
+        return out, wts

@@ -821,6 +821,18 @@ int fie_lpips_layer_f32(fie_ctx* ctx, const float* fa, const float* fb, int P, i
 int fie_sweep_select_u8(fie_ctx* ctx, const void* const* imgs, int k, int64_t bytes, const int64_t* rows, const float* clip_or_null, int rule,
                         double floor, int bg, void* out_img, int32_t* out_idx);
 
+/* ---- Prompt emphasis: the text's cross-attention V rows scaled by one weight per text row, in front of the denoising loop.
+ *   A weight behind the softmax, out = sum_j p_j w_j v_j, is cross-attention on a V whose row j is scaled by w_j; the text's K | V is projected once
+ *   per image and net, so the whole control is this one launch on that result.
+ *   X: row-major [rows, ld], f16 (f32 = 0) or f32 (f32 = 1), 16-byte aligned, ld % 8 == 0, ld >= ncols; ncols % 8 == 0 (so every block's c % 8 == 0).
+ *   w: f32 [rows] ON THE DEVICE (a graph replay reads the weights of the job it replays).  vflags: u8 [ncols / 8] on the device, non-zero where the
+ *   8 columns [8 g, 8 g + 8) are V columns.  For every row r with w[r] != 1 and every flagged g:
+ *       X[r, 8 g + e] = round(f32(X[r, 8 g + e]) * w[r])        one fp32 multiply; f16: one rounding to nearest even (beyond 65504: an infinity)
+ *   A row with w[r] == 1.0f is neither read nor written; unflagged columns, the columns ncols .. ld and everything outside X keep their bits.
+ *   fie_amd/emphasis.py: kv_emphasis_numpy restates it to the bit.  FIE_EINVAL for anything else.  One launch, 16-byte accesses, no atomics, no
+ *   workspace, no block waits for another. */
+int fie_kv_emphasis(fie_ctx* ctx, void* X, int64_t ld, int64_t rows, int64_t ncols, const float* w, const uint8_t* vflags, int f32);
+
 #ifdef __cplusplus
 }
 #endif

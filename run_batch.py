@@ -8,7 +8,8 @@ shards the selected entries image-parallel over N GPUs (fie_amd.dist) and rank 0
 
 Additive flags (the reference has none of them): --strength, --weights_dir, --device, --results_json, --metrics, --clip_score_dir, --dino_dir, --lpips_dir,
 --auto_strength, --min_ssim, --strengths.  FIE_CANNY_DENSITY=d in the environment runs every edit with an edge-budget Canny (FastEditor.set_canny_density;
-DESIGN.md section 22): the pair picked for each image goes into --results_json as canny_low / canny_high.
+DESIGN.md section 22): the pair picked for each image goes into --results_json as canny_low / canny_high.  FIE_PROMPT_EMPHASIS=w in the environment
+reads the [...] marks of the PIE-Bench editing prompts as prompt emphasis of weight w (FastEditor.set_prompt_emphasis).
 """
 import argparse
 import json
@@ -595,6 +596,8 @@ def main(argv=None):
     else:
         say(f"      Canny thresholds: picked per image at density {editor.canny_density:g} (FIE_CANNY_DENSITY), low / high = "
             f"{min(args.canny_low, args.canny_high)} / {max(args.canny_low, args.canny_high)} (each image's pair: --results_json)")
+    if getattr(editor, "prompt_emphasis", None) is not None:
+        say(f"      Prompt emphasis: the [...] marks of the prompts weigh {editor.prompt_emphasis:g} (FIE_PROMPT_EMPHASIS)")
 
     progress = None
     if rank == 0:

@@ -162,9 +162,19 @@ def add_canny_args(p):
     return p
 
 
+def add_emphasis_args(p):
+    """[additive] prompt emphasis, kept apart from build_parser() like add_tile_args."""
+    p.add_argument("--prompt_emphasis", type=float, default=None, metavar="W",
+                   help="[additive] read the marks of --prompt and --negative_prompt: '[words]' (how PIE-Bench writes the words an edit changes) "
+                        "weighs its words by W, 0..8, in every cross-attention, '(words:1.3)' by the written number; the marks are stripped before "
+                        "tokenisation.  Prompt-to-Prompt and front ends use 1.1..2; no weight has been tried on real checkpoints.  Without the "
+                        "flag a prompt is tokenised as it is, brackets included")
+    return p
+
+
 def full_parser():
     """The parser main() reads: build_parser() and every additive group."""
-    return add_canny_args(add_sweep_args(add_tile_args(build_parser())))
+    return add_emphasis_args(add_canny_args(add_sweep_args(add_tile_args(build_parser()))))
 
 
 def save_plot(path, source_img, edited_img, model, prompt):
@@ -211,10 +221,13 @@ def main(argv=None):
     if args.region == "mask" and not masked:
         parser.error("--region mask needs --mask")
     import fie_amd  # noqa: F401
-    from fie_amd import buckets, canny_auto as hcanny, mask as hmask
+    from fie_amd import buckets, canny_auto as hcanny, emphasis as hemph, mask as hmask
     try:
         mask_kw = hmask.cli_keywords(args, masked, "--mask")
         hcanny.check(args.canny_density, args.canny_low, args.canny_high)
+        if args.prompt_emphasis is not None:                            # the marks of both prompts, read before the models load
+            for text in (args.prompt, args.negative_prompt or ""):
+                hemph.parse(text, args.prompt_emphasis)
     except ValueError as e:
         parser.error(str(e))
     if args.resolution != "square":
@@ -280,6 +293,9 @@ def main(argv=None):
         print(f"      Tiles: {args.tiles if args.tiles == 'auto' else '%dx%d' % args.tiles}, overlap {args.tile_overlap} px, {args.tile_batch} per device job")
     if args.canny_density is not None:
         editor.set_canny_density(args.canny_density)
+    if args.prompt_emphasis is not None:
+        editor.set_prompt_emphasis(args.prompt_emphasis)
+        print(f"      Prompt emphasis: [...] weighs {args.prompt_emphasis:g}; the prompt is tokenised as {hemph.parse(args.prompt, args.prompt_emphasis)[0]!r}")
     t0 = time.time()
     variants = None
     if args.sweep:

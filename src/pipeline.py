@@ -51,7 +51,7 @@ class FastEditor:
     def __init__(self, model_name="sdxl", device="cuda", dtype=torch.float16, enable_cpu_offload=True,
                  use_full_precision=False, use_full_controlnet=False, *, weights_dir=None, seed_weights=1234,
                  noise_dtype=None, broadcast_weights=True, weight_dtype="f16", clip_score_dir=None, dino_dir=None, dino_layer=11,
-                 lpips_dir=None, canny_density=None):
+                 lpips_dir=None, canny_density=None, prompt_emphasis=None):
         if model_name not in self.MODEL_CONFIGS and model_name not in self._EXTRA_STACKS:
             raise ValueError(f"Unknown model: {model_name}. Choose from {list(self.MODEL_CONFIGS.keys())}")
         if canny_density is None and os.environ.get("FIE_CANNY_DENSITY"):     # [additive] set_canny_density() from the start; the switch serves run_batch.py
@@ -60,6 +60,12 @@ class FastEditor:
             except ValueError:
                 raise ValueError(f"FIE_CANNY_DENSITY={os.environ['FIE_CANNY_DENSITY']!r}: a number in [0.001, 0.25]") from None
         self.set_canny_density(canny_density)
+        if prompt_emphasis is None and os.environ.get("FIE_PROMPT_EMPHASIS"):  # [additive] set_prompt_emphasis() from the start; the switch serves run_batch.py
+            try:
+                prompt_emphasis = float(os.environ["FIE_PROMPT_EMPHASIS"])
+            except ValueError:
+                raise ValueError(f"FIE_PROMPT_EMPHASIS={os.environ['FIE_PROMPT_EMPHASIS']!r}: a number in [0, 8]") from None
+        self.set_prompt_emphasis(prompt_emphasis)
         self.model_name = model_name
         self.device = device
         self.dtype = torch.float32 if use_full_precision else dtype
@@ -112,6 +118,7 @@ class FastEditor:
             log(f"UNet / ControlNet weights: {weight_dtype} with per-channel scales on the fp8 MFMA (BASELINE config 5)")
         self.weight_dtype = weight_dtype
         self.pipe = HipImg2ImgPipeline(ctx, cfgs, sds, tokenizers=toks, noise_dtype=noise_dtype or self.dtype, weight_dtype=weight_dtype)
+        self.pipe.prompt_emphasis = self.prompt_emphasis
         self.controlnet = self.pipe.controlnet
         self._tls = threading.local()          # .slot: graph slot of the calling worker thread (set_in_flight)
         self._fullres_out = {}                 # (slot, image) -> flat u8 buffer on the device, grown to the largest source: the full-resolution back end's output (output_size="source")
@@ -204,6 +211,26 @@ class FastEditor:
         `canny_high`.  Three more launches in front of the job, no additional host wait (except the tiled edit's).  The setting belongs to the
         editor, not to a thread: set it before the worker threads of `set_in_flight` start.  Returns the value it replaces."""
         before, self.canny_density = self.canny_density, hcanny.check_density(canny_density)
+        return before
+
+    prompt_emphasis = None      # set_prompt_emphasis(): None, or the weight of the words a prompt marks with [...]
+
+    def set_prompt_emphasis(self, prompt_emphasis):
+        """[additive] Prompt emphasis for every later edit(), edit_batch() and edit_sweep() of this editor; None (the default)
+        switches it off again: prompts then go to the tokenizers as they are, brackets included.  `prompt_emphasis` is a float in [0, 8].  With it
+        set, prompt and negative prompt are read for marks: `[words]` -- how PIE-Bench writes the words an edit changes -- gives its words that
+        weight, `(words:1.3)` the written number (at most 8); the marks themselves are stripped before the tokenizers see the prompt, a `[` or `]`
+        that belongs to no mark is a ValueError of the call, parentheses in any other form are text.  Every cross-attention of the UNet and the
+        ControlNet then multiplies the softmax probability of a weighted token by its weight, without renormalising (Prompt-to-Prompt's
+        re-weighting): exactly, the token's row of each block's `attn2.to_v` output is scaled by the weight, once per image and net, in front of the
+        denoising loop (one launch per net).  A weight above 1 strengthens a word, below 1 weakens it, 0 removes its value.  A prompt whose
+        weights are all 1 -- the setting 1.0, or no marks -- is the stripped prompt under None: the same job, graph and bytes.  The CLIP score
+        keeps reading the prompt as passed.  The setting belongs to the editor, not to a thread: set it before the worker threads of `set_in_flight`
+        start.  Returns the value it replaces."""
+        from fie_amd import emphasis as hemph
+        before, self.prompt_emphasis = self.prompt_emphasis, hemph.check(prompt_emphasis)
+        if getattr(self, "pipe", None) is not None:
+            self.pipe.prompt_emphasis = self.prompt_emphasis
         return before
 
     def last_canny_thresholds(self):
