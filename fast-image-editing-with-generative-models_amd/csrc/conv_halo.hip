@@ -47,7 +47,7 @@ constexpr int HP = 18;                          // halo pixels per side of a 16 
 constexpr int HPIECES = (HP * HP + 7) / 8;      // 41 DMA pieces of 8 pixels x 128 B
 constexpr int HALO_B = HPIECES * 1024;          // 41,984 bytes per halo buffer
 constexpr int HSLOTS = 6;                       // halo piece slots per wave and chunk: taps 0..5 issue one each
-constexpr int BNH = 128;                        // output channels per block
+// BNH = 128 output channels per block: gemm_select.h states it, next to the eligibility predicates that ask for whole column tiles
 constexpr int STH = 3;                          // weight stages
 constexpr int WSTAGE_B = BNH * 128;             // 16,384 bytes
 // LDS: [three weight stages][halo 0][halo 1][dump].  The ring comes FIRST so that stage * 16 KiB + fragment * 2 KiB fits the 16-bit offset field of
@@ -1006,47 +1006,6 @@ int fie_conv_halo_init(void) {
         return FIE_EHIP;
     }
     return FIE_OK;
-}
-
-// Shapes the halo-resident kernel takes: the plain same-size conv (stride 1, zero padding 1, no up-sampling gather, no 1x1 side inputs, fp16
-// weights) on maps whose height and width are multiples of 16, Cin % 64 == 0, operands the 32-bit buffer offsets reach (checked by the caller: dma_ok)
-bool fie_conv_halo_ok(const GemmArgs& a) {
-    const bool base = a.stride == 1 && !a.ups && !a.taps2 && !a.oscat && a.pt == 1 && a.pl == 1 && a.H == a.OH && a.W == a.OW && a.OH % 16 == 0 &&
-                      a.OW % 16 == 0 && a.Cin % BK == 0 && a.Cin >= BK && !a.w_scale && !a.out_f8 && a.splitk <= 1;
-    if (!base) return false;
-    if (!a.A2) return !a.A3 && a.K == 9 * a.Cin;
-    // 1x1 side inputs (conv2 + shortcut): the persistent form only, so everything that form asks for
-    return a.C2x % BK == 0 && a.C3x % BK == 0 && a.C2x > 0 && (a.A3 != nullptr) == (a.C3x > 0) && a.K == 9 * a.Cin + a.C2x + a.C3x && a.Cin >= 2 * BK && a.N % BNH == 0 &&
-           !a.res && !a.rowbias && a.act == FIE_ACT_NONE && a.scale == 1.f && a.lda2 * 2 * (int64_t)a.OW * a.OH < (1ll << 31) && a.lda3 * 2 * (int64_t)a.OW * a.OH < (1ll << 31);
-}
-
-// Edge patches (tile code 78): the same conv on maps whose height or width is NOT a multiple of 16 (at least one side; maps of whole patches keep
-// codes 71-76, so no shape changes kernels), in the persistent form only, so everything that form asks for: Cin >= 128, no activation / scale, row bias
-// and residual never together.  N % 64 == 0 (not 128): a wave whose 64 channels lie past N drops its stores per lane like a pixel outside the image;
-// its weight rows are the packing's zero rows (Npad = N rounded up to 128), so every DMA piece is a real load.  No GroupNorm sums (their granules are 32-pixel halves of whole patches)
-bool fie_conv_halo_edge_ok(const GemmArgs& a) {
-    const bool base = a.stride == 1 && !a.ups && !a.taps2 && !a.oscat && a.pt == 1 && a.pl == 1 && a.H == a.OH && a.W == a.OW && a.OH > 0 && a.OW > 0 &&
-                      (a.OH % 16 != 0 || a.OW % 16 != 0) && a.M % (a.OH * a.OW) == 0 && a.Cin % BK == 0 && a.Cin >= 2 * BK && !a.w_scale && !a.out_f8 &&
-                      a.splitk <= 1 && a.N % 64 == 0 && a.ldc >= a.N && !a.gn_partial && !a.gna_tab && a.act == FIE_ACT_NONE && a.scale == 1.f && !(a.rowbias && a.res);
-    if (!base) return false;
-    if (!a.A2) return !a.A3 && a.K == 9 * a.Cin;
-    return a.C2x % BK == 0 && a.C3x % BK == 0 && a.C2x > 0 && (a.A3 != nullptr) == (a.C3x > 0) && a.K == 9 * a.Cin + a.C2x + a.C3x && !a.res && !a.rowbias &&
-           a.lda2 * 2 * (int64_t)a.OW * a.OH < (1ll << 31) && a.lda3 * 2 * (int64_t)a.OW * a.OH < (1ll << 31);
-}
-
-// 16x16 patches of the output (the row blocks of the halo-resident kernels), partial ones at the edges counted
-int64_t fie_conv_halo_patches(const GemmArgs& a) {
-    if (a.OH <= 0 || a.OW <= 0) return 0;
-    return (int64_t)(a.M / (a.OH * a.OW)) * ((a.OH + 15) / 16) * ((a.OW + 15) / 16);
-}
-
-// GNA (the input's GroupNorm + SiLU applied on the resident halo): the persistent form, ONE image, GroupNorm sums armed for the output (every resnet conv
-// of the VAE has them), no row bias, no side inputs, Cin <= 1024 (an 8 KiB coefficient table behind the dump), as many column tiles as fit the grid
-bool fie_conv_halo_gna_ok(const GemmArgs& a) {
-    if (!fie_conv_halo_ok(a) || a.A2 || a.rowbias) return false;
-    const int nbn = (a.N + BNH - 1) / BNH;
-    return a.M == a.OH * a.OW && a.Cin >= 2 * BK && a.Cin <= 1024 && a.N % BNH == 0 && nbn <= 64 && a.act == FIE_ACT_NONE && a.scale == 1.f && a.gn_partial != nullptr &&
-           (a.gn_cg == 4 || a.gn_cg == 8 || a.gn_cg == 16);
 }
 
 // variant: 0 = v1 (one tile per block, code 71), 1 = v1 with stamps (73), 2 = v2: persistent blocks, deferred 16-byte stores issued inside the MFMA

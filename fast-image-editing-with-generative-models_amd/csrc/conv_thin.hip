@@ -140,12 +140,6 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(const GemmArgs p) {
 
 }  // namespace
 
-bool fie_conv_thin_ok(const GemmArgs& a) {
-    return a.N <= 16 && a.N % 4 == 0 && a.ldc % 4 == 0 && a.Cin % 8 == 0 && !a.ups && !a.taps2 && !a.oscat && !a.A2 && !a.w_scale && !a.rowbias && !a.res &&
-           !a.gn_partial && !a.gna_tab && !a.ln_tab && !a.out_f8 && (a.act == FIE_ACT_NONE || a.act == FIE_ACT_SILU) && (a.stride == 1 || a.stride == 2) &&
-           a.ldw >= fie_roundup(a.K, 32) && a.w_bytes >= 16 * a.ldw * 2;
-}
-
 int fie_launch_conv_thin(fie_ctx* ctx, GemmArgs& a) {
     FIE_REQUIRE(fie_conv_thin_ok(a), "thin conv (tile code 77): Cout <= 16, plain bias / SiLU epilogue, f16 weights, no side inputs only");
     const int B = a.M / (a.OH * a.OW);

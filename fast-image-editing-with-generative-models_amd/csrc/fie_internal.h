@@ -72,7 +72,7 @@ struct fie_ctx {
     int splitk_mode = 1;                     // fie_debug_splitk: 0 = never split K, 1 = where the tuner / an override says so
     int autotune = 0;                        // fie_gemm_autotune: time the eligible tiles at a shape's first eager launch
     std::map<fie_tune_key, int> tuned;
-    int tune_exclude[16] = {0};              // fie_debug_tune_exclude: tile codes the tuner must not offer (10000 = every split-K variant); 0-terminated
+    int tune_exclude[16] = {0};              // fie_debug_tune_exclude: tile codes the tuner must not offer (gemm_select.h: Choice::kSplit = every split-K variant); 0-terminated
     void* tune_buf = nullptr;                // scratch output of the timing launches
     void* tune_flush = nullptr;              // 384 MB written between timed launches: cold weights, as inside the network
     size_t tune_bytes = 0;

@@ -1,6 +1,6 @@
 // K1/K2: fp16 MFMA GEMM and 3x3 implicit-GEMM convolution for gfx950 (include/fie.h: fie_gemm_f16, fie_conv3x3_nhwc_f16):
-// the launch table and two of the three kernel families (the third, the 256x256 phased kernel, lives in gemm8.hip; shared
-// pieces in gemm_common.h).
+// two of the three kernel families (the third, the 256x256 phased kernel, lives in gemm8.hip; shared pieces in gemm_common.h), the
+// launchers of the launch table and the launch itself; which tile a launch gets is decided in gemm_select.h.
 //
 //   gemm_kernel<BM,BN,MODE>          register-staged double buffer, 4 waves.  Serves EVERY shape (generic im2col gather with
 //                                    per-lane zero fill): the fallback for operands the LDS-DMA kernels cannot address
@@ -17,6 +17,7 @@
 // Unselected experiments of round 1 (zero-page global_load_lds ring, ping-pong, four-phase, producer waves, halo-reuse conv,
 // 160-wide tiles, column split): measured no better, removed (git history has them; the numbers are in profiles/r01_microbench.md).
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(NW * 64) void gemm3_kernel(GemmArgs p) {
     const unsigned w_step = (unsigned)(NW * 8) * (unsigned)p.ldw * 2u;
 
     const int csteps = MODE == 2 ? p.Cin / BK : 1;
-    const int k1_steps = p.K1 / BK;            // GEMM: K-steps served by A1 (K1 % 64 == 0 and K % 64 == 0 unless K1 == K: launch<0>)
+    const int k1_steps = p.K1 / BK;            // GEMM: K-steps served by A1 (K1 % 64 == 0 and K % 64 == 0 unless K1 == K: dma_ok of gemm_select.h)
     const int nk_all = (p.K + BK - 1) / BK;
     const KSlice ks(nk_all, slice, nsplit, csteps);                    // this block's K-steps: [kbeg, kbeg + nk); all of them without split-K
     const int kbeg = ks.kbeg, nk = ks.nk;
@@ -589,25 +590,15 @@ __global__ __launch_bounds__(NW * 64) void gemm3_kernel(GemmArgs p) {
     }
 }
 
-// ---- the launch table: ONE row per tile code (also the values fie_debug_force_tile / fie_debug_tile_override take; + 1000 / + 2000 force the tile
-// order, n-tiles / m-tiles fastest, plain codes estimate it).  Everything the host knows about a code is in its row; a new tile is one row here
-// (and, for an fp8 kernel, one entry in gemm_tiles.h).
-enum Family { kGeneric, kRing, kPhased, kHalo, kHaloEdge, kThin };      // kGeneric and kThin serve shapes the LDS-DMA kernels cannot address (no dma_ok needed)
-// flags: may split K (ring kernels with <= 16 accumulator fragments per lane, no stamps); writes cycle stamps (fie_debug_gemm_stamps: slower, for
-// tools/kstep_stamps.py only; on a ring row also the kernel's STAMP); no conv-view build; has an LN-folded build (LEAN == 2); ring rows: the kernel's PF / ALT
-enum : unsigned { kSplitK = 1, kStamps = 2, kGemmOnly = 4, kLnFold = 8, kPF = 16, kAlt = 32 };
+// ---- the launcher half of the launch table.  The rows themselves (code, tile, family, flags, fp8 remaps, launcher arguments) are kTiles in
+// gemm_select.h, with everything that decides; kLaunch[i] below is what row i launches, made from the row by its family: nothing is written twice.
 using LaunchFn = int (*)(fie_ctx*, GemmArgs&, dim3 grid);
-struct Tile {
-    int code, bm, bn;
-    Family family;
-    const char* name;               // the kernel family as fie_debug_last_gemm_kernel prints it
-    unsigned flags;
-    int w8, x8;                     // the code that runs in its place with fp8 weights (gemm_w8.hip) / fp8 activations x weights (gemm_x8.hip); 0 = none
+struct Launchers {
     LaunchFn gemm, conv, ln;        // launch in the GEMM view / the conv view / with LayerNorm folded in; null where not built
     hipError_t (*attr)();           // sets the dynamic-LDS attribute of every kernel the row launches; null for the families with an init of their own
 };
 
-// A ring tile: the template arguments of gemm3_kernel are named HERE and nowhere else, so the launches, the lean / non-lean pair, the LN build and
+// A ring tile: the template arguments of gemm3_kernel come from the row HERE and nowhere else, so the launches, the lean / non-lean pair, the LN build and
 // the attribute setter of a row cannot disagree
 template <int BM, int BN, int ST, int NW, unsigned F = 0>
 struct RingTile {
@@ -642,11 +633,11 @@ struct RingTile {
         if constexpr (F & kLnFold) set(kernel<0, 2>());
         return e;
     }
-    static constexpr Tile row(int code, const char* name, int w8, int x8) {
-        Tile t = {code, BM, BN, kRing, name, F, w8, x8, &launch<0>, nullptr, nullptr, &attr};
-        if constexpr (!(F & kGemmOnly)) t.conv = &launch<2>;
-        if constexpr (F & kLnFold) t.ln = &launch<0, true>;
-        return t;
+    static constexpr Launchers launchers() {
+        Launchers l = {&launch<0>, nullptr, nullptr, &attr};
+        if constexpr (!(F & kGemmOnly)) l.conv = &launch<2>;
+        if constexpr (F & kLnFold) l.ln = &launch<0, true>;
+        return l;
     }
 };
 
@@ -656,8 +647,6 @@ int launch_generic(fie_ctx* ctx, GemmArgs& a, dim3 grid) {
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
-template <int BM, int BN>
-constexpr Tile generic_row(int code, int w8, int x8) { return {code, BM, BN, kGeneric, "gemm_kernel", 0, w8, x8, &launch_generic<BM, BN, 0>, &launch_generic<BM, BN, 1>}; }
 // the families with launchers (and attribute setters) of their own: gemm8.hip, conv_halo.hip (by variant number), conv_thin.hip
 template <int CONV, int VARIANT>
 int launch_phased(fie_ctx* ctx, GemmArgs& a, dim3) { return fie_launch_gemm8(ctx, a, CONV, VARIANT); }
@@ -665,210 +654,64 @@ template <int VARIANT>
 int launch_halo(fie_ctx* ctx, GemmArgs& a, dim3) { return fie_launch_conv_halo(ctx, a, VARIANT); }
 int launch_thin(fie_ctx* ctx, GemmArgs& a, dim3) { return fie_launch_conv_thin(ctx, a); }
 
-// Columns: code, bm, bn, family, name, flags, w8, x8, gemm, conv (ln, attr: ring rows only).  With fp8 WEIGHTS every code runs on one of the five W8 tiles
-// (its own shape where that is built, 256x128 otherwise; the halo rows never get there: their eligibility test refuses fp8 weights first); with fp8
-// ACTIVATIONS a code without a stand-in is refused.
-constexpr Tile kTiles[] = {
-    generic_row<128, 128>(1, 62, 43),      // gemm_kernel: any shape
-    generic_row<128, 64>(2, 42, 42),
-    generic_row<64, 64>(3, 43, 43),
-    RingTile<128, 64, 3, 4, kSplitK | kLnFold>::row(42, "gemm3_kernel", 42, 42),      // 128x64 / 64x64, 3 stages, 4 waves (two / three blocks per CU)
-    RingTile<64, 64, 3, 4, kSplitK>::row(43, "gemm3_kernel", 43, 43),
-    RingTile<128, 64, 2, 4, kSplitK>::row(44, "gemm3_kernel", 42, 42),                // the same tiles with 2 stages (three / five blocks per CU)
-    RingTile<64, 64, 2, 4, kSplitK>::row(46, "gemm3_kernel", 43, 43),
-    // 128x96, 3 stages, 4 waves: 224 tiles for M 2048 x N 1280 (one per CU, each streaming a 96-row weight tile: the 32x32-latent convs lose nothing
-    // on cold weights with it, 7-9 % with 128x128)
-    RingTile<128, 96, 3, 4, kSplitK>::row(47, "gemm3_kernel", 62, 47),
-    // 128x80, 3 stages, 4 waves stacked along the rows (wave tile 32x80); M 2048 x N 1280 = 256 tiles, one per CU.  Weight rows past the packed matrix
-    // (80 does not divide Npad) read as zero through the descriptor.  (Its LN-folded build returned wrong values in 16-row x 1-column spots on a loaded
-    // chip, in every form tried, while 42 / 96 / 64 never did, and is NOT built: profiles/r04_ln_fold_tile48_anomaly.md; tests/test_ops_gpu.py screens the three that ship)
-    RingTile<128, 80, 3, 4, kSplitK>::row(48, "gemm3_kernel", 62, 0),
-    RingTile<128, 128, 3, 8, kSplitK>::row(51, "gemm3_kernel", 62, 51),               // 128x128, 3 stages, 8 waves
-    RingTile<128, 128, 2, 8, kSplitK>::row(52, "gemm3_kernel", 52, 52),               // 128x128 / 192x128, 2 stages, 8 waves: two blocks per CU
-    RingTile<192, 128, 2, 8, kSplitK>::row(54, "gemm3_kernel", 54, 54),
-    RingTile<256, 256, 2, 8>::row(61, "gemm3_kernel", 62, 62),                        // 256x256 x 2 stages / 256x128 x 3 stages, 8 waves
-    RingTile<256, 128, 3, 8, kSplitK>::row(62, "gemm3_kernel", 62, 62),
-    // 256x320 x 2 stages, 8 waves (wave tile 128x80): exactly ONE tile per CU for the FF1 projection M 2048 x N 10240 (256 tiles) and two rounds for
-    // M 8192 x N 5120; 142 FLOP per staged byte pair against 85 for 256x128
-    RingTile<256, 320, 2, 8, kGemmOnly>::row(63, "gemm3_kernel", 62, 63),
-    // 63 with the two wave groups taking turns at a K-step's LDS-DMA refill (ALT above): FF1 56.5 us against 59.5-63.4 (the same idea on 256x128 x 3
-    // stages was 3 % SLOWER than 62 and is not built: the barrier still paces both groups by the slower one).  No alternating-refill form of the fp8 kernels
-    RingTile<256, 320, 2, 8, kGemmOnly | kAlt | kLnFold>::row(64, "gemm3_kernel", 62, 63),
-    // 51 / 62 with fragment reads one half K-step ahead of the MFMAs (the 4-wave and 2-stage tiles gain nothing from it)
-    RingTile<128, 128, 3, 8, kPF | kSplitK>::row(95, "gemm3_kernel+prefetch", 62, 51),
-    RingTile<256, 128, 3, 8, kPF | kSplitK | kLnFold>::row(96, "gemm3_kernel+prefetch", 62, 62),
-    // 62 / 96 / 42 with in-kernel cycle stamps.  97 and 94 do NOT prefetch: their printed name is a misnomer of the old `code >= 90` rule that tests,
-    // tools and bench.py parse; fixing it is a change of its own
-    RingTile<256, 128, 3, 8, kStamps>::row(97, "gemm3_kernel+prefetch", 62, 0),
-    RingTile<256, 128, 3, 8, kPF | kStamps>::row(98, "gemm3_kernel+prefetch", 62, 0),
-    RingTile<128, 64, 3, 4, kStamps>::row(94, "gemm3_kernel+prefetch", 62, 0),
-    {81, 256, 256, kPhased, "gemm8_kernel", 0, 62, 62, &launch_phased<0, 0>, &launch_phased<1, 0>},      // gemm8.hip: 256x256 phased
-    {82, 256, 256, kPhased, "gemm8_kernel", 0, 62, 0, &launch_phased<0, 1>, &launch_phased<1, 1>},       // A/B: second DMA piece of each phase inside the MFMA cluster (measured slower)
-    // conv_halo.hip: a 16x16 output patch x 128 channels per block, the patch's 18x18 halo resident in LDS per 64-channel chunk, weights through a ring;
-    // stride-1 same-size convs with H, W % 16 == 0 only (73: with cycle stamps).  K is summed chunk-major (the im2col kernels: tap-major): equal to the
-    // other codes to rounding, not bit for bit
-    {71, 256, 128, kHalo, "conv_halo_kernel", 0, 62, 0, nullptr, &launch_halo<0>},
-    {73, 256, 128, kHalo, "conv_halo_kernel", kStamps, 62, 0, nullptr, &launch_halo<1>},
-    // the same K loop in persistent blocks that prefetch their next tile and defer a tile's stores into the next tile's first chunk (74: with cycle
-    // stamps, 76: the 8-byte-store form, A/B); 72 is THE RULE for eligible convs (heuristic_code)
-    {72, 256, 128, kHalo, "conv_halo2_kernel", 0, 62, 0, nullptr, &launch_halo<2>},
-    {74, 256, 128, kHalo, "conv_halo2_kernel", kStamps, 62, 0, nullptr, &launch_halo<4>},
-    {76, 256, 128, kHalo, "conv_halo2_kernel", 0, 62, 0, nullptr, &launch_halo<5>},
-    // ... with edge patches: maps whose height or width is not a multiple of 16 (the aspect-ratio buckets); the patch grid is rounded up, stores of pixels
-    // outside the image are dropped per lane; no GroupNorm sums.  The rule for eligible convs, under 72's threshold.  Sums chunk-major like 71-76
-    {78, 256, 128, kHaloEdge, "conv_halo2_kernel+edge", 0, 62, 0, nullptr, &launch_halo<6>},
-    {77, 64, 16, kThin, "conv_thin_kernel", 0, 62, 0, &launch_thin, &launch_thin},      // conv_thin.hip: at most 16 output channels, by rule; its launcher refuses GEMM arguments itself
-};
-constexpr const Tile* find_tile(int code) {
-    for (const Tile& t : kTiles)
-        if (t.code == code) return &t;
-    return nullptr;
+template <size_t I>
+constexpr Launchers launchers_of() {
+    constexpr Tile t = kTiles[I];
+    if constexpr (t.family == kRing) return RingTile<t.bm, t.bn, t.p0, t.p1, t.flags>::launchers();
+    else if constexpr (t.family == kGeneric) return {&launch_generic<t.bm, t.bn, 0>, &launch_generic<t.bm, t.bn, 1>};
+    else if constexpr (t.family == kPhased) return {&launch_phased<0, t.p0>, &launch_phased<1, t.p0>};
+    else if constexpr (t.family == kThin) return {&launch_thin, &launch_thin};      // its launcher refuses GEMM arguments itself
+    else return {nullptr, &launch_halo<t.p0>};
 }
-constexpr bool is_family(int code, Family f) { return find_tile(code) && find_tile(code)->family == f; }
+template <size_t... I>
+constexpr std::array<Launchers, sizeof...(I)> all_launchers(std::index_sequence<I...>) { return {{launchers_of<I>()...}}; }
+constexpr auto kLaunch = all_launchers(std::make_index_sequence<std::size(kTiles)>{});
+const Launchers& launchers(const Tile* t) { return kLaunch[t - kTiles]; }
 
-// What the tuner times besides the rule's code, in timing order (the order decides ties): plain tile codes (tune_candidates filters them), then split-K
-// encodings code + 10000 * s (s = 2..4) of the split lists, offered while the tile's grid stays under per_cu blocks per CU
-constexpr int kCandF16[] = {43, 46, 42, 44, 51, 52, 54, 96, 81, 63, 47, 48, 64, 72, 78};      // 47 (128x96): FIE_TUNE_47=0 leaves it out
-constexpr int kCandW8[] = {43, 42, 62, 52, 54};
-constexpr int kCandX8[] = {43, 42, 47, 51, 52, 54, 62, 63};
-struct SplitCand { int code, per_cu; };
-constexpr SplitCand kSplitF16[] = {{96, 1}, {95, 1}, {47, 1}, {54, 2}, {52, 2}};
-constexpr SplitCand kSplitX8[] = {{62, 1}, {51, 1}, {47, 1}, {54, 2}, {52, 2}};
-
-// ---- the checks the hand-kept lists never had: 0, or the number of the first rule the tables break
-template <size_t N>
-constexpr bool f8_built(const fie_f8_tile (&built)[N], int code) {      // a kernel of that precision with the row's tile shape
-    const Tile* t = find_tile(code);
-    for (const fie_f8_tile& b : built)
-        if (t && b.code == code && b.bm == t->bm && b.bn == t->bn) return true;
-    return false;
+// rule 4 of gemm_select.h's table_error, the one that reads the launchers: a missing view is declared (run_code refuses the halo rows' GEMM view by family)
+constexpr bool views_declared() {
+    for (size_t i = 0; i < std::size(kTiles); ++i)
+        if ((!kLaunch[i].conv && !(kTiles[i].flags & kGemmOnly)) || (!kLaunch[i].gemm && kTiles[i].family != kHalo && kTiles[i].family != kHaloEdge)) return false;
+    return true;
 }
-constexpr int table_error() {
-    for (const Tile& t : kTiles) {
-        int n = 0;
-        for (const Tile& u : kTiles) n += u.code == t.code;
-        if (n != 1) return 1;                                                                       // codes are unique
-        if (!f8_built(kFieW8Tiles, t.w8) || (t.x8 && !f8_built(kFieX8Tiles, t.x8))) return 2;       // a remap target is a row with a kernel of that precision
-        if ((t.flags & kSplitK) && t.family != kRing) return 3;                                     // only the ring kernels reduce split K
-        if ((!t.conv && !(t.flags & kGemmOnly)) || (!t.gemm && t.family != kHalo && t.family != kHaloEdge)) return 4;      // a missing view is declared (run_code refuses the halo rows' GEMM view by family)
-    }
-    for (int c : kCandF16) if (!find_tile(c)) return 5;                                                // every candidate is a row, with a kernel of its precision
-    for (int c : kCandW8) if (!f8_built(kFieW8Tiles, c)) return 6;
-    for (int c : kCandX8) if (!f8_built(kFieX8Tiles, c)) return 7;
-    for (const SplitCand& c : kSplitF16) if (!find_tile(c.code) || !(find_tile(c.code)->flags & kSplitK)) return 8;
-    for (const SplitCand& c : kSplitX8) if (!f8_built(kFieX8Tiles, c.code) || !(find_tile(c.code)->flags & kSplitK)) return 9;
-    return 0;
-}
-static_assert(table_error() == 0, "kTiles / candidate lists inconsistent: see table_error for the rule with that number");
+static_assert(views_declared(), "kTiles / kLaunch inconsistent: rule 4, a row lacks a view it does not declare missing");
 
-// Heuristic tile code for a shape (the default; the autotuner below and the debug hooks can replace it).
-template <int MODE>
-int heuristic_code(const fie_ctx* ctx, const GemmArgs& a, bool dma_ok) {
-    auto blocks = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-    const int64_t cus = ctx->num_cus;
-    // Selection: tools/tile_table.py (interleaved rounds per shape, profiles/r02_tile_table.md) + tools/tile_trials.py inside the
-    // UNet.  The K loop is paced by the per-CU global->LDS issue path (~100 cycles per 1 KiB piece), so a tile's FLOP per
-    // staged byte BM*BN/(BM+BN) decides its ceiling -- but only while the grid still fills the CUs: the largest tile that does wins.
-    const int64_t b256 = blocks(256, 256), b62 = blocks(256, 128), b51 = blocks(128, 128), b42 = blocks(128, 64);
-    int code;
-    if (!dma_ok) {
-        code = b42 >= cus ? 2 : 3;
-    } else if (MODE == 1 && fie_conv_halo_ok(a) && 4 * (int64_t)(a.M / 256) * ((a.N + 127) / 128) >= 3 * cus && a.C2x + a.C3x <= 4 * BK &&      // (1x1 side inputs: each 64 channels cost a drained K-step: the rule takes few of them, the tuner may take more)
-               std::find(std::begin(ctx->tune_exclude), std::end(ctx->tune_exclude), 72) == std::end(ctx->tune_exclude)) {      // fie_debug_tune_exclude("72"): the A/B switch
-        // stride-1 same-size convs on maps of whole 16x16 patches with enough (patch, 128-channel) tiles to fill the chip: the halo-resident kernel
-        // (conv_halo.hip; persistent, deferred stores).  Measured against every im2col code on the VAE's and the UNet's 64x64 / 128x128-latent
-        // shapes: -15 to -35 % (profiles/r04_halo_conv.md)
-        code = 72;
-    } else if (MODE == 1 && fie_conv_halo_edge_ok(a) && 4 * fie_conv_halo_patches(a) * ((a.N + 127) / 128) >= 3 * cus && a.C2x + a.C3x <= 4 * BK &&
-               std::find(std::begin(ctx->tune_exclude), std::end(ctx->tune_exclude), 78) == std::end(ctx->tune_exclude)) {      // fie_debug_tune_exclude("78"): the A/B switch
-        // the same kernel on maps with a side that is not a multiple of 16 (the aspect-ratio buckets: 72x56, 152x104, 38x26, ...): partial patches at
-        // the right and bottom edges.  Measured against every im2col code on the buckets' UNet maps (profiles/resolution_buckets.md): 0.84-0.86x the
-        // best on the 640-channel maps, 0.97-0.98x on the 320-channel ones; 1.07-1.14x on the 1280-channel maps, which have 120 tiles and stay under
-        // this threshold (so the rule keeps their im2col code)
-        code = 78;
-    } else if (MODE == 1) {
-        if (!a.A2 && ((b256 >= cus && (a.N % 256 == 0 || (a.N % 128 != 0 && a.K >= 5760))) ||        // 256x256 phased: VAE 256/512-ch maps, 128x128-latent convs into 320 ch (not with 1x1 side inputs: ring kernels only)
-            (a.N % 256 == 0 && a.K >= 8192 && 2 * b256 >= cus))) code = 81;                  // ... and the long-K upsampling convs of the 32x32 level
-        else if (a.N % 128 == 0 && b62 >= 150) code = 96;
-        else if (a.N % 128 == 0 && a.K >= 5760 && b51 >= 100) code = 51;                     // 32x32-latent convs: 160 x (128x128), 8 waves
-        else if (2 * b42 < 3 * cus) code = 43;                                               // stride-2 convs and other small grids
-        else code = 42;
-    } else if (MODE == 0 && a.N % 320 == 0 && a.N >= 5120 && 4 * blocks(256, 320) >= 3 * cus) {
-        // the FF1 projections (M 2048 x N 10240: 256 tiles of 256x320 = one per CU; M 8192 x N 5120: two exact rounds): tile 64 measured 52-58 us
-        // on every box of round 3 against 65-80 us for 96 -- but the cold-timed tuner, starting from 96 as the rule, kept 96 on some boxes (one
-        // profile run of round 4: 79.7 us x 112 launches = +2.4 ms per edit).  As the RULE it needs a 3 % better challenger to be displaced.
-        code = 64;
-    } else if (a.N % 256 == 0 && a.K >= 4096 && b256 >= cus) {
-        code = 81;
-    } else if (a.N % 128 == 0 && b62 >= 150 && (a.N >= 1536 || a.K >= 2048 || a.M >= 16384)) {
-        code = 96;
-    } else if (a.N >= 2048 && a.K >= 1024 && b51 >= cus) {
-        code = 51;
-    } else if (a.K <= 640 && a.N <= 640) {
-        code = 43;                                                                           // 64x64 / 128x128-latent projections: many small tiles
-    } else if (b42 >= cus * 7 / 2 || a.K >= 4096 || (a.K >= 1024 && b42 >= cus)) {
-        code = 42;
-    } else {
-        code = 43;
-    }
-    return code;
+// The context's knobs as the selection reads them; FIE_TUNE_47 is read once per process
+SelectEnv select_env(const fie_ctx* ctx) {
+    static const bool tune47 = !(getenv("FIE_TUNE_47") && getenv("FIE_TUNE_47")[0] == '0');
+    SelectEnv env = {ctx->num_cus, ctx->sk_ws != nullptr, ctx->sk_bytes, ctx->splitk_mode, {}, tune47};
+    static_assert(sizeof(env.tune_exclude) == sizeof(ctx->tune_exclude), "the whole exclusion list");
+    std::copy(std::begin(ctx->tune_exclude), std::end(ctx->tune_exclude), env.tune_exclude);
+    return env;
 }
 
-// One launch of `code` (order: 0 n-tiles fastest, 1 m-tiles fastest, -1 estimate).
-constexpr int64_t kSkTickets = 4096;        // arrival counters at the head of the split-K workspace
-
-// Largest usable split for a tile: a row that may split K (kSplitK), at least 4 K-steps per slice, counters and slabs inside the bound
-// workspace.  Returns 1 when split-K cannot run.
-inline int splitk_fit(const fie_ctx* ctx, const GemmArgs& a, const Tile& t, int want) {
-    const int bm = t.bm, bn = t.bn;
-    if (want <= 1 || !(t.flags & kSplitK) || !ctx->sk_ws || !ctx->splitk_mode || (a.w_scale && a.a_scale == 0.f)) return 1;
-    const int64_t tiles = (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn) * (a.oscat == 2 ? 4 : 1);
-    const int nk = (a.K + BK - 1) / BK / (a.a_scale != 0.f ? 2 : 1);      // fp8 activations: 128 k-values per K-step
-    int s = want;
-    while (s > 1 && (nk / s < 4 || tiles > kSkTickets || (int64_t)(kSkTickets * 4 + tiles * s * bm * bn * 4) > ctx->sk_bytes)) --s;
-    return s;
-}
-
-template <int MODE>
-int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int split = 1) {
+// One launch of the choice `c` (c.order -1: estimated; c.split: as far as it fits).
+int run_code(fie_ctx* ctx, const SelectEnv& env, GemmArgs& a, bool conv, Choice c, bool dma) {
+    int code = c.code, split = c.split;
     const Tile* t = find_tile(code);
     FIE_REQUIRE(t != nullptr, "unknown tile code %d", code);
     const Family fam = t->family;
-    FIE_REQUIRE(fam == kGeneric || fam == kThin || dma_ok, "tile code %d: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0, or A = [A1 | A2] with K1 %% 64 != 0 or K %% 64 != 0)", code);
+    FIE_REQUIRE(fam == kGeneric || fam == kThin || dma, "tile code %d: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0, or A = [A1 | A2] with K1 %% 64 != 0 or K %% 64 != 0)", code);
     FIE_REQUIRE(!(a.taps2 && (fam == kGeneric || a.w_scale)), "tile code %d: the 2x2 parity convs run on the f16 LDS-DMA kernels only", code);
-    FIE_REQUIRE(!(MODE == 1 && a.A2 && (fam == kGeneric || fam == kPhased || a.w_scale)), "tile code %d: conv + 1x1 side inputs run on the f16 ring kernels and the halo-resident kernel (72) only", code);
-    FIE_REQUIRE(!(fam == kHalo && (MODE != 1 || !dma_ok || !fie_conv_halo_ok(a))), "tile code %d (halo-resident conv): stride-1 same-size 3x3 conv with H, W %% 16 == 0, Cin %% 64 == 0, f16 weights only", code);
-    FIE_REQUIRE(!(fam == kHaloEdge && (MODE != 1 || !dma_ok || !fie_conv_halo_edge_ok(a))), "tile code 78 (halo-resident conv, edge patches): stride-1 same-size 3x3 conv with H or W %% 16 != 0, "
+    FIE_REQUIRE(!(conv && a.A2 && (fam == kGeneric || fam == kPhased || a.w_scale)), "tile code %d: conv + 1x1 side inputs run on the f16 ring kernels and the halo-resident kernel (72) only", code);
+    FIE_REQUIRE(!(fam == kHalo && (!conv || !dma || !fie_conv_halo_ok(a))), "tile code %d (halo-resident conv): stride-1 same-size 3x3 conv with H, W %% 16 == 0, Cin %% 64 == 0, f16 weights only", code);
+    FIE_REQUIRE(!(fam == kHaloEdge && (!conv || !dma || !fie_conv_halo_edge_ok(a))), "tile code 78 (halo-resident conv, edge patches): stride-1 same-size 3x3 conv with H or W %% 16 != 0, "
                 "Cin %% 64 == 0, Cin >= 128, N %% 64 == 0, f16 weights, no activation / scale / GroupNorm sums only");
-    if (order < 0) {
-        // Tile order = which operand an XCD re-streams past its 4 MiB L2.  Consecutive tile ids run on one XCD (xcd_remap), so an
-        // XCD owns T/8 consecutive tiles: with n fastest that is `dm` row blocks x up to all column tiles, with m fastest the
-        // transpose.  Fabric bytes per XCD ~ (row blocks touched) x (A bytes per row block) + (column tiles touched) x (W bytes per
-        // column tile); pick the smaller (FF1 at M 2048: 8 XCDs x all 26 MB of W with n fastest, 247 MB measured by PMC in round 1,
-        // against 8 x (3.3 MB of W + all 5.2 MB of A) with m fastest).  The 3x3 im2col view re-reads an input row block ~once.
-        const int64_t nbm = (a.M + t->bm - 1) / t->bm, nbn = (a.N + t->bn - 1) / t->bn;
-        const int64_t per_xcd = (nbm * nbn + 7) / 8;
-        const double a_tile = (double)t->bm * a.K * 2 * (MODE == 1 ? 1.0 / 9 : 1.0), w_tile = (double)t->bn * a.K * 2;
-        auto fabric = [&](int64_t fast, int64_t slow, double fast_tile, double slow_tile) {       // `fast` tiles per row of the id space
-            const int64_t rows = (per_xcd + fast - 1) / fast;                                       // slow-index values an XCD touches
-            return (double)(rows < slow ? rows : slow) * slow_tile + (double)(per_xcd < fast ? per_xcd : fast) * fast_tile;
-        };
-        order = fabric(nbm, nbn, a_tile, w_tile) < fabric(nbn, nbm, w_tile, a_tile) ? 1 : 0;
-    }
+    const int order = c.order < 0 ? tile_order(a, *t, conv) : c.order;
     const bool x8 = a.w_scale && a.a_scale != 0.f;           // e4m3 activations x e4m3 weights (gemm_x8.hip): its own tile set
     if (x8) {
-        FIE_REQUIRE(dma_ok && !a.A2 && !a.taps2, "fp8 activations: plain GEMM / 3x3 conv views on the LDS-DMA kernels only");
+        FIE_REQUIRE(dma && !a.A2 && !a.taps2, "fp8 activations: plain GEMM / 3x3 conv views on the LDS-DMA kernels only");
         FIE_REQUIRE(t->x8 != 0, "tile code %d has no fp8-activation kernel", code);
         t = find_tile(t->x8);
-        if (MODE == 1 && (t->flags & kGemmOnly)) t = find_tile(62);      // the 320-wide tile has no conv view: 256x128 stands in
+        if (conv && (t->flags & kGemmOnly)) t = find_tile(62);      // the 320-wide tile has no conv view: 256x128 stands in
     } else if (a.w_scale) {          // fp8 weights: the W8 ring tiles (gemm_w8.hip)
-        FIE_REQUIRE(dma_ok, "fp8 weights: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0, or A = [A1 | A2] with K1 %% 64 != 0 or K %% 64 != 0)");
+        FIE_REQUIRE(dma, "fp8 weights: shape not eligible for the LDS-DMA kernels (operands >= 2 GiB, Cin %% 64 != 0, or A = [A1 | A2] with K1 %% 64 != 0 or K %% 64 != 0)");
         t = find_tile(t->w8);
     }
     code = t->code;
     a.nbm = (a.M + t->bm - 1) / t->bm;
     a.nbn = (a.N + t->bn - 1) / t->bn;
-    split = splitk_fit(ctx, a, *t, split);
+    split = splitk_fit(env, a, *t, split);
     a.splitk = split;
     a.sk_tickets = static_cast<unsigned*>(ctx->sk_ws);
     a.sk_slabs = reinterpret_cast<float*>(static_cast<char*>(ctx->sk_ws) + kSkTickets * 4);
@@ -877,33 +720,35 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
     a.epi_prefetch = ctx->epi_prefetch;
     a.stamps = (t->flags & kStamps) ? ctx->gemm_stamps : nullptr;
     if (x8) snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm3x8_kernel<%dx%d> (gemm, fp8 activations x fp8 weights, tile code %d)", t->bm, t->bn, code);
-    else if (a.w_scale) snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm3w8_kernel<%dx%d> (%s, fp8 weights, tile code %d)", t->bm, t->bn, MODE == 1 ? "conv3x3" : "gemm", code);
-    else snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "%s<%dx%d> (%s, tile code %d)", t->name, t->bm, t->bn, MODE == 1 ? "conv3x3" : "gemm", code);
+    else if (a.w_scale) snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm3w8_kernel<%dx%d> (%s, fp8 weights, tile code %d)", t->bm, t->bn, conv ? "conv3x3" : "gemm", code);
+    else snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "%s<%dx%d> (%s, tile code %d)", t->name, t->bm, t->bn, conv ? "conv3x3" : "gemm", code);
     if (split > 1) snprintf(ctx->last_kernel + strlen(ctx->last_kernel) - 1, 24, ", split-K %d)", split);
     if (ctx->oplog) {
         // after the flop token: what it takes to rebuild the call (tools/launch_problems.py): batch, padding, side inputs and the A1|A2 seam, the parity
         // view, weight / activation precision, and the epilogue (bias, row bias, residual, act, scale, GroupNorm partial sums, f8 output, LN / GN folds)
         char rebuild[256];
         snprintf(rebuild, sizeof(rebuild), " | b=%d pad=%d C2=%d C3=%d K1=%d parity=%d w8=%d bias=%d rowbias=%d rpb=%d res=%d act=%d scale=%.9g gn=%d gnrows=%d f8out=%d ln=%d gna=%d",
-                 MODE == 1 ? a.M / (a.OH * a.OW) : 1, MODE == 1 && !a.taps2 && a.pt == 0 ? 1 : 0, a.C2x, a.C3x, a.K1, a.taps2, a.w_scale ? (a.a_scale != 0.f ? 2 : 1) : 0,
+                 conv ? a.M / (a.OH * a.OW) : 1, conv && !a.taps2 && a.pt == 0 ? 1 : 0, a.C2x, a.C3x, a.K1, a.taps2, a.w_scale ? (a.a_scale != 0.f ? 2 : 1) : 0,
                  a.bias != nullptr, a.rowbias != nullptr, a.rowbias ? a.rows_per_batch : 0, a.res != nullptr, a.act, (double)a.scale, a.gn_partial ? a.gn_G : 0,
                  a.gn_partial ? a.gn_rows : 0, a.out_f8, a.ln_tab != nullptr, a.gna_tab != nullptr);
-        if (MODE == 1)
+        const int ran = Choice{code, -1, split}.encode();
+        if (conv)
             FIE_DESC(ctx, "conv M=%d N=%d K=%d in=%dx%dx%d s%d u%d%s%s code=%d flop=%.0f%s", a.M * (a.oscat == 2 ? 4 : 1), a.N, a.K, a.H, a.W, a.Cin, a.stride, a.ups,
-                     a.taps2 ? " up2x-parity" : "", a.A2 ? " +1x1" : "", code + 10000 * (split > 1 ? split : 0), 2.0 * a.M * a.N * a.K * (a.oscat == 2 ? 4 : 1), rebuild);
+                     a.taps2 ? " up2x-parity" : "", a.A2 ? " +1x1" : "", ran, 2.0 * a.M * a.N * a.K * (a.oscat == 2 ? 4 : 1), rebuild);
         else
             FIE_DESC(ctx, "gemm M=%d N=%d K=%d act=%d%s%s%s code=%d flop=%.0f%s", a.M, a.N, a.K, a.act, a.res ? " +res" : "", a.ln_tab ? " +ln" : "", a.w_scale ? (a.a_scale != 0.f ? " a8w8" : " w8") : "",
-                     code + 10000 * (split > 1 ? split : 0), 2.0 * a.M * a.N * a.K, rebuild);
+                     ran, 2.0 * a.M * a.N * a.K, rebuild);
     }
-    if (x8) return fie_launch_gemm_x8(ctx, a, code, MODE == 1);
-    if (a.w_scale) return fie_launch_gemm_w8(ctx, a, MODE == 1, code);
+    if (x8) return fie_launch_gemm_x8(ctx, a, code, conv);
+    if (a.w_scale) return fie_launch_gemm_w8(ctx, a, conv, code);
     const dim3 grid((unsigned)(a.nbm * a.nbn * (a.oscat == 2 ? 4 : 1) * split));
+    const Launchers& l = launchers(t);
     if (a.ln_tab) {
-        FIE_REQUIRE(MODE == 0 && t->ln && split == 1, "LayerNorm-folded GEMM: tile code %d not built for it", code);
+        FIE_REQUIRE(!conv && l.ln && split == 1, "LayerNorm-folded GEMM: tile code %d not built for it", code);
         FIE_REQUIRE((code == 64) == (a.act == FIE_ACT_GEGLU), "LayerNorm-folded GEMM: GEGLU runs on tile 64 and nothing else does (code %d, act %d)", code, a.act);
-        return t->ln(ctx, a, grid);
+        return l.ln(ctx, a, grid);
     }
-    const LaunchFn fn = MODE == 1 ? t->conv : t->gemm;
+    const LaunchFn fn = conv ? l.conv : l.gemm;
     FIE_REQUIRE(fn != nullptr, "tile code %d (%dx%d%s) is built for the GEMM view only", code, t->bm, t->bn, (t->flags & kAlt) ? ", alternating refill" : "");
     return fn(ctx, a, grid);
 }
@@ -922,78 +767,31 @@ int run_code(fie_ctx* ctx, GemmArgs& a, int code, int order, bool dma_ok, int sp
 // (tools/cold_weights.py).
 constexpr size_t kFlushBytes = 384u << 20;
 
-// What the tuner times besides the rule's code `guess` (kCandF16 / kCandW8 / kCandX8 and the split lists above, filtered): autotune below times exactly this list; fie_debug_tune_candidates reports it (tests/test_launch_table_gpu.py runs every entry at the product's shapes).
-template <int MODE>
-std::vector<int> tune_candidates(const fie_ctx* ctx, const GemmArgs& a, int guess) {
-    static const bool use47 = !(getenv("FIE_TUNE_47") && getenv("FIE_TUNE_47")[0] == '0');
-    std::vector<int> out;
-    auto blocks = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-    const bool x8 = a.w_scale && a.a_scale != 0.f;
-    const int* cand = x8 ? kCandX8 : a.w_scale ? kCandW8 : kCandF16;
-    const size_t ncand = x8 ? std::size(kCandX8) : a.w_scale ? std::size(kCandW8) : std::size(kCandF16);
-    auto excluded = [&](int c) {
-        for (int e : ctx->tune_exclude)
-            if (e == c) return e != 0;
-        return false;
-    };
-    for (size_t i = 0; i < ncand; ++i) {
-        const int c = cand[i];
-        if (c == guess || excluded(c)) continue;
-        if ((c == 43 || c == 46) && blocks(64, 64) > 64 * ctx->num_cus) continue;       // tens of thousands of tiny tiles: never wins
-        if ((c == 81 || c == 96 || c == 62) && 2 * blocks(256, 128) < ctx->num_cus) continue;
-        if ((c == 63 || c == 64) && (MODE != 0 || a.N % 320 != 0 || 2 * blocks(256, 320) < ctx->num_cus)) continue;
-        if (c == 47 && !use47) continue;
-        if (c == 48 && (a.N % 80 != 0 || blocks(128, 80) > 2 * ctx->num_cus)) continue;      // the exact-fit tile of the N = 1280 projections: small grids only
-        if (x8 && MODE == 1 && c == 63) continue;
-        if (x8 && (c == 62 || c == 51) && 2 * blocks(c == 62 ? 256 : 128, 128) < ctx->num_cus) continue;
-        if (c == 81 && MODE == 1 && a.A2) continue;            // side inputs: ring kernels only
-        if (c == 72 && (MODE != 1 || !fie_conv_halo_ok(a) || 2 * (int64_t)(a.M / 256) * ((a.N + 127) / 128) < ctx->num_cus)) continue;
-        if (c == 78 && (MODE != 1 || !fie_conv_halo_edge_ok(a) || 2 * fie_conv_halo_patches(a) * ((a.N + 127) / 128) < ctx->num_cus)) continue;
-        out.push_back(c);
-    }
-    // split-K: big tiles whose grid leaves CUs idle (the M = 2048 class: 80 tiles of 256x128 on 256 CUs) with the K-steps of a tile dealt
-    // to 2-4 blocks, reduced in the launch (gemm_common.h: splitk_reduce).  Changes the fp32 summation order, so unlike the tile choice
-    // it is visible in the last bit of some f16 outputs; fixed per (shape, choice), hence deterministic within a process.
-    if ((!a.w_scale || x8) && ctx->sk_ws && ctx->splitk_mode && !excluded(10000)) {
-        for (const SplitCand& c : x8 ? kSplitX8 : kSplitF16) {
-            if (excluded(c.code)) continue;
-            const Tile& t = *find_tile(c.code);
-            const int64_t nb = blocks(t.bm, t.bn) * (a.oscat == 2 ? 4 : 1);
-            if (nb >= ctx->num_cus * c.per_cu) continue;                 // the grid already fills the chip
-            for (int sp = 2; sp <= 4; ++sp) {
-                if (nb * sp > (int64_t)ctx->num_cus * c.per_cu * 21 / 20) break;
-                if (splitk_fit(ctx, a, t, sp) != sp) continue;
-                out.push_back(c.code + 10000 * sp);
-            }
-        }
-    }
-    return out;
-}
-
-template <int MODE>
-int autotune(fie_ctx* ctx, GemmArgs& a, int guess, bool dma_ok) {
+// The timing loop: the rule's code `guess`, then gemm_select.h's tune_candidates in order; returns the winner
+Choice autotune(fie_ctx* ctx, const SelectEnv& env, GemmArgs& a, bool conv, int guess, bool dma) {
+    Choice best{guess};
     const size_t bytes = (size_t)a.M * (a.oscat ? 4 : 1) * (size_t)a.ldc * sizeof(half_t);     // a parity conv scatters its M rows over 4 M output rows
     if (bytes > ctx->tune_bytes) {
         if (ctx->tune_buf) (void)hipFree(ctx->tune_buf);
         ctx->tune_buf = nullptr;
         ctx->tune_bytes = 0;
-        if (hipMalloc(&ctx->tune_buf, bytes) != hipSuccess) { (void)hipGetLastError(); return guess; }
+        if (hipMalloc(&ctx->tune_buf, bytes) != hipSuccess) { (void)hipGetLastError(); return best; }
         ctx->tune_bytes = bytes;
     }
-    if (!ctx->tune_flush && hipMalloc(&ctx->tune_flush, kFlushBytes) != hipSuccess) { (void)hipGetLastError(); ctx->tune_flush = nullptr; return guess; }
+    if (!ctx->tune_flush && hipMalloc(&ctx->tune_flush, kFlushBytes) != hipSuccess) { (void)hipGetLastError(); ctx->tune_flush = nullptr; return best; }
     hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return guess;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return best;
     (void)hipDeviceSynchronize();                          // nothing else on the device while the candidates are timed
     GemmArgs t = a;
     t.C = static_cast<half_t*>(ctx->tune_buf);           // a residual that aliases C is still read from the caller's buffer
-    auto time_of = [&](int code, int split = 1) -> float {
+    auto time_of = [&](Choice c) -> float {
         float ms[7];
         for (int rep = -1; rep < 7; ++rep) {               // rep -1: untimed (first use of the kernel)
             (void)hipMemsetAsync(ctx->tune_flush, rep & 1, kFlushBytes, ctx->stream);
             if ((size_t)a.a1_bytes <= kFlushBytes) (void)hipMemcpyAsync(ctx->tune_flush, a.A1, (size_t)a.a1_bytes, hipMemcpyDeviceToDevice, ctx->stream);
             if (a.A2 && a.A2 != a.A1 && (size_t)a.a2_bytes <= kFlushBytes) (void)hipMemcpyAsync(ctx->tune_flush, a.A2, (size_t)a.a2_bytes, hipMemcpyDeviceToDevice, ctx->stream);
             (void)hipEventRecord(e0, ctx->stream);
-            if (run_code<MODE>(ctx, t, code, -1, dma_ok, split) != FIE_OK) return 1e30f;
+            if (run_code(ctx, env, t, conv, c, dma) != FIE_OK) return 1e30f;
             (void)hipEventRecord(e1, ctx->stream);
             if (hipEventSynchronize(e1) != hipSuccess) return 1e30f;
             if (rep >= 0) (void)hipEventElapsedTime(&ms[rep], e0, e1);
@@ -1002,101 +800,73 @@ int autotune(fie_ctx* ctx, GemmArgs& a, int guess, bool dma_ok) {
         return (ms[2] + ms[3] + ms[4]) / 3.f;              // mean of the middle three of seven
     };
     static const bool verbose = getenv("FIE_TUNE_VERBOSE") && getenv("FIE_TUNE_VERBOSE")[0] == '1';
-    const float t_guess = time_of(guess);
-    if (verbose) fprintf(stderr, "[fie tune] %s M=%d N=%d K=%d: rule %d %.1f us", MODE == 1 ? "conv" : "gemm", a.M, a.N, a.K, guess, t_guess * 1e3f);
-    int best = guess;
+    const float t_guess = time_of(best);
+    if (verbose) fprintf(stderr, "[fie tune] %s M=%d N=%d K=%d: rule %d %.1f us", conv ? "conv" : "gemm", a.M, a.N, a.K, guess, t_guess * 1e3f);
     float t_best = t_guess * 0.97f;                          // a challenger has to win by 3 %
-    for (const int enc : tune_candidates<MODE>(ctx, a, guess)) {
-        const int c = enc % 10000, sp = enc / 10000 > 1 ? enc / 10000 : 1;
-        const float tc = time_of(c, sp);
+    for (const int enc : tune_candidates(env, a, conv, guess)) {
+        const Choice c = Choice::decode(enc);
+        const float tc = time_of(c);
         if (verbose) {
-            if (sp > 1) fprintf(stderr, ", %d/s%d %.1f", c, sp, tc * 1e3f);
-            else fprintf(stderr, ", %d %.1f", c, tc * 1e3f);
+            if (c.split > 1) fprintf(stderr, ", %d/s%d %.1f", c.code, c.split, tc * 1e3f);
+            else fprintf(stderr, ", %d %.1f", c.code, tc * 1e3f);
         }
-        if (tc < t_best) { t_best = tc; best = enc; }
+        if (tc < t_best) { t_best = tc; best = c; }
     }
-    if (verbose) fprintf(stderr, " -> %d\n", best);
+    if (verbose) fprintf(stderr, " -> %d\n", best.encode());
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return best;
 }
 
-template <int MODE>
-int launch(fie_ctx* ctx, GemmArgs& a) {
-    // LDS-DMA kernels (codes >= 40): 32-bit buffer offsets (operands < 2 GiB) and K-steps that never straddle a 3x3 tap / the A1|A2 seam
-    // (A = [A1 | A2]: K1 AND K multiples of 64 -- the last, partial K-step of these kernels is issued from A1's descriptor, which is A2's tail there)
-    // ... and an epilogue on 32-bit buffer offsets (gemm_common.h): output / residual spans of at most 1 GiB
-    const int64_t c_span = ((int64_t)((a.oscat ? 4 * (int64_t)a.M : a.M) - 1) * a.ldc + a.N) * 2, r_span = a.res ? ((int64_t)(a.M - 1) * a.ldr + a.N) * 2 : 0;
-    const bool dma_ok = a.a1_bytes < (1ll << 31) && a.a2_bytes < (1ll << 31) && a.w_bytes < (1ll << 31) && c_span <= (1ll << 30) && r_span <= (1ll << 30) &&
-                        (MODE == 1 ? a.Cin % (a.a_scale != 0.f ? 2 * BK : BK) == 0 : (a.K1 == a.K || (a.K1 % BK == 0 && a.K % BK == 0)));
-    FIE_REQUIRE(!(MODE == 1 && a.A2 && !dma_ok), "conv + 1x1 side inputs: tensors too large for the LDS-DMA kernels");
-    if (MODE == 1 && a.gna_tab) {                          // the input's GroupNorm applied on the resident halo: one kernel family, no choice to make
-        FIE_REQUIRE(dma_ok && fie_conv_halo_gna_ok(a), "fie_conv3x3_gn_nhwc_f16: shape / epilogue not built for the fused form (ask fie_conv3x3_gn_ok first)");
-        return run_code<MODE>(ctx, a, 72, -1, dma_ok, 1);
+// overrides / forced tile, then the rule, then the tuner's table, then the fallback of a remembered choice, then run_code
+int launch(fie_ctx* ctx, GemmArgs& a, bool conv) {
+    const bool dma = dma_ok(a, conv);
+    FIE_REQUIRE(!(conv && a.A2 && !dma), "conv + 1x1 side inputs: tensors too large for the LDS-DMA kernels");
+    const SelectEnv env = select_env(ctx);
+    if (conv && a.gna_tab) {                               // the input's GroupNorm applied on the resident halo: one kernel family, no choice to make
+        FIE_REQUIRE(dma && fie_conv_halo_gna_ok(a), "fie_conv3x3_gn_nhwc_f16: shape / epilogue not built for the fused form (ask fie_conv3x3_gn_ok first)");
+        return run_code(ctx, env, a, conv, rule(env, a, conv, dma), dma);
     }
-    if (MODE == 0 && a.ln_tab) {
-        // LayerNorm folded in: four tiles, chosen by rule (no tuner: the choice among them does not change the sums, every one adds K in the same order)
-        FIE_REQUIRE(dma_ok, "fie_gemm_ln_f16: operands too large for the LDS-DMA kernels");
-        auto blocks = [&](int bm, int bn) { return (int64_t)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
-        int code;
-        if (a.act == FIE_ACT_GEGLU) code = 64;
-        else if (a.N % 128 == 0 && blocks(256, 128) >= 150 && (a.N >= 1536 || a.M >= 16384)) code = 96;
-        else code = 42;
-        const int forced = ctx->force_tile % 1000;
-        if (forced && find_tile(forced) && find_tile(forced)->ln && (forced == 64) == (a.act == FIE_ACT_GEGLU)) code = forced;
-        return run_code<MODE>(ctx, a, code, -1, dma_ok, 1);
+    if (!conv && a.ln_tab) {                               // LayerNorm folded in: by rule, or the forced tile where it has an LN build
+        FIE_REQUIRE(dma, "fie_gemm_ln_f16: operands too large for the LDS-DMA kernels");
+        return run_code(ctx, env, a, conv, rule(env, a, conv, dma, Choice::decode(ctx->force_tile).code), dma);
     }
-    int code = heuristic_code<MODE>(ctx, a, dma_ok);
-    int order = -1;                // 0: n-tiles fastest (an XCD owns a range of activation rows), 1: m-tiles fastest; -1: estimate
-    int split = 1;                 // encoded choices: split-K factor * 10000 + (1000 / 2000: forced tile order) + tile code
+    Choice c;
     bool pinned = false;
-    auto decode = [&](int v) { split = v / 10000 > 1 ? v / 10000 : 1; v %= 10000; order = v >= 2000 ? 1 : v >= 1000 ? 0 : -1; code = v % 1000; };
     for (int i = 0; i < ctx->n_overrides; ++i) {
         const fie_tile_override& o = ctx->overrides[i];
-        if (o.mode == (MODE == 1) && o.M == a.M && o.N == a.N && o.K == a.K) { decode(o.code); pinned = true; }
+        if (o.mode == (conv ? 1 : 0) && o.M == a.M && o.N == a.N && o.K == a.K) { c = Choice::decode(o.code); pinned = true; }
     }
-    if (ctx->force_tile) { decode(ctx->force_tile); pinned = true; }
-    // at most 16 output channels (conv_out of the VAE / UNet, the conditioning embedding's first convs): the direct-load strip kernel of conv_thin.hip,
-    // by rule and without the tuner (one kernel family; profiles/r04_conv_thin.md).  fie_debug_tune_exclude("77") is the A/B switch.
-    const fie_tune_key key{MODE, a.M, a.N, a.K, a.K1, MODE == 1 ? a.stride * 2 + a.ups + 8 * a.taps2 + 16 * (a.A2 != nullptr) + 32 * (a.A3 != nullptr) : 0, a.w_scale == nullptr ? 0 : a.a_scale != 0.f ? 2 : 1};
-    // fie_debug_tune_candidates: "rule, then every candidate" of a launch the tuner could decide, in the key format of fie_gemm_autotune_report; the rule's code runs
-    auto note_candidates = [&](int rule, const std::vector<int>& cands) {
-        char line[256];
-        int n = snprintf(line, sizeof(line), "%s M=%d N=%d K=%d K1=%d geom=%d w8=%d rule=%d cands=", MODE == 1 ? "conv" : "gemm", key.M, key.N, key.K, key.K1, key.geom, key.w8, rule);
-        for (size_t i = 0; i < cands.size() && n < (int)sizeof(line) - 8; ++i) n += snprintf(line + n, sizeof(line) - n, i ? ",%d" : "%d", cands[i]);
-        ctx->tune_cands->push_back(line);
-    };
-    if (MODE == 1 && !pinned && !ctx->gemm_probe && fie_conv_thin_ok(a) && a.M >= 131072 &&      // (the 128x128-latent conv_outs, K 2880 / 4608 on few strips: the ring tiles are faster)
-        std::find(std::begin(ctx->tune_exclude), std::end(ctx->tune_exclude), 77) == std::end(ctx->tune_exclude)) {
-        if (ctx->tune_cands) note_candidates(77, {});      // by rule, never tuned
-        return run_code<MODE>(ctx, a, 77, 0, dma_ok, 1);
+    if (ctx->force_tile) { c = Choice::decode(ctx->force_tile); pinned = true; }
+    const bool tunable = !pinned && !ctx->gemm_probe;
+    const Choice guess = rule(env, a, conv, dma, 0, tunable);
+    if (!pinned) c = guess;
+    const fie_tune_key key{conv ? 1 : 0, a.M, a.N, a.K, a.K1, conv ? a.stride * 2 + a.ups + 8 * a.taps2 + 16 * (a.A2 != nullptr) + 32 * (a.A3 != nullptr) : 0, a.w_scale == nullptr ? 0 : a.a_scale != 0.f ? 2 : 1};
+    if (tunable && (ctx->tune_cands || is_family(guess.code, kThin))) {
+        // fie_debug_tune_candidates: "rule, then every candidate" of a launch the tuner could decide, in the key format of fie_gemm_autotune_report; the
+        // rule's code runs.  The thin conv is by rule, never tuned: an empty list
+        if (ctx->tune_cands) {
+            const std::vector<int> cands = dma && !is_family(guess.code, kThin) ? tune_candidates(env, a, conv, guess.code) : std::vector<int>{};
+            char line[256];
+            int n = snprintf(line, sizeof(line), "%s M=%d N=%d K=%d K1=%d geom=%d w8=%d rule=%d cands=", conv ? "conv" : "gemm", key.M, key.N, key.K, key.K1, key.geom, key.w8, guess.code);
+            for (size_t i = 0; i < cands.size() && n < (int)sizeof(line) - 8; ++i) n += snprintf(line + n, sizeof(line) - n, i ? ",%d" : "%d", cands[i]);
+            ctx->tune_cands->push_back(line);
+        }
+        return run_code(ctx, env, a, conv, guess, dma);
     }
-    if (ctx->tune_cands && !pinned && !ctx->gemm_probe) {
-        note_candidates(code, dma_ok ? tune_candidates<MODE>(ctx, a, code) : std::vector<int>{});
-        return run_code<MODE>(ctx, a, code, order, dma_ok, split);
-    }
-    if (ctx->autotune && !pinned && dma_ok && !ctx->gemm_probe) {      // 1: tune shapes not met before, 2: remembered shapes only
+    if (ctx->autotune && tunable && dma) {                 // 1: tune shapes not met before, 2: remembered shapes only
         auto it = ctx->tuned.find(key);
         if (it != ctx->tuned.end()) {
-            decode(it->second);
+            c = Choice::decode(it->second);
         } else if (ctx->autotune == 1 && !ctx->recording) {
             hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(ctx->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
-                const int best = autotune<MODE>(ctx, a, code, dma_ok);
-                ctx->tuned[key] = best;
-                decode(best);
+                c = autotune(ctx, env, a, conv, guess.code, dma);
+                ctx->tuned[key] = c.encode();
             }
         }
     }
-    // tuner keys carry neither the map's height and width nor the epilogue: one key covers 144x112 and 168x96 (M 16128), and 78 refuses GroupNorm
-    // sums and activations.  A remembered halo-resident code the launch is not eligible for (72 met on a map of whole patches, then the same key
-    // on a bucket map; 78 met without sums, then with them) falls back to the rule instead of failing
-    if (MODE == 1 && !pinned && ((is_family(code, kHalo) && !fie_conv_halo_ok(a)) || (is_family(code, kHaloEdge) && !fie_conv_halo_edge_ok(a)))) {
-        code = heuristic_code<MODE>(ctx, a, dma_ok);
-        order = -1;
-        split = 1;
-    }
-    return run_code<MODE>(ctx, a, code, order, dma_ok, split);
+    return run_code(ctx, env, a, conv, eligible_or_rule(env, a, conv, dma, c, pinned), dma);
 }
 
 int check_epilogue(const char* who, int N, int64_t ldc, const void* res, int64_t ldr, int act) {
@@ -1138,8 +908,8 @@ __global__ void pack_conv_kernel(const half_t* src, int Cout, int Cin, int cin_p
 
 int fie_gemm_init(void) {
     hipError_t e = hipSuccess;
-    for (const Tile& t : kTiles)
-        if (e == hipSuccess && t.attr) e = t.attr();
+    for (const Launchers& l : kLaunch)
+        if (e == hipSuccess && l.attr) e = l.attr();
     if (e != hipSuccess) {
         fie_set_error("gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         return FIE_EHIP;
@@ -1342,7 +1112,7 @@ static int gemm_impl(const char* who, fie_ctx* ctx, const void* A1, int64_t lda1
     a.a2_bytes = A2 ? ((int64_t)(M - 1) * lda2 + (K - K1)) * 2 : 0;
     a.w_bytes = fie_roundup(N, 128) * ldw * (w_scale ? 1 : 2);
     if (int rc = take_gn_target(who, gn, a)) return rc;
-    return launch<0>(ctx, a);
+    return launch(ctx, a, false);
 }
 
 int fie_gemm_f16(fie_ctx* ctx, const void* A1, int64_t lda1, int K1, const void* A2, int64_t lda2,
@@ -1371,7 +1141,7 @@ int fie_gemm_ln_f16(fie_ctx* ctx, const void* X, int64_t ldx, const void* Wfolde
     a.a1_bytes = ((int64_t)(M - 1) * ldx + K) * 2;
     a.w_bytes = fie_roundup(N, 128) * ldw * 2;
     a.ln_tab = ln_tab; a.ln_eps = eps;
-    return launch<0>(ctx, a);
+    return launch(ctx, a, false);
 }
 
 int fie_gemm_w8_f16(fie_ctx* ctx, const void* A1, int64_t lda1, int K1, const void* A2, int64_t lda2, const void* W8packed,
@@ -1406,7 +1176,7 @@ int fie_gemm_x8_f16(fie_ctx* ctx, const void* A8, int64_t lda, const void* W8pac
     a.out_f8 = out_f8; a.out_inv_scale = out_inv_scale;
     a.a1_bytes = (int64_t)(M - 1) * lda + K;
     a.w_bytes = fie_roundup(N, 128) * ldw;
-    return launch<0>(ctx, a);
+    return launch(ctx, a, false);
 }
 
 static int conv_impl(const char* who, fie_ctx* ctx, const void* X, int B, int H, int W, int Cin, int upsample2x, int stride, int pad_mode,
@@ -1449,7 +1219,7 @@ static int conv_impl(const char* who, fie_ctx* ctx, const void* X, int B, int H,
     a.w_bytes = fie_roundup(Cout, 128) * ldw * (w_scale ? 1 : 2);
     a.gna_tab = gna_tab; a.gna_silu = gna_silu;
     if (int rc = take_gn_target(who, gn, a)) return rc;
-    return launch<1>(ctx, a);
+    return launch(ctx, a, true);
 }
 
 // 3x3 conv on e4m3 activations (written by fie_groupnorm_nhwc_f16_o8 / fie_groupnorm_stats_nhwc_f16_o8) and e4m3 weights (fie_pack_conv3x3_f8 with
@@ -1480,7 +1250,7 @@ int fie_conv3x3_x8_nhwc_f16(fie_ctx* ctx, const void* X8, int B, int H, int W, i
     a.a1_bytes = (int64_t)B * H * W * Cin;
     a.w_bytes = fie_roundup(Cout, 128) * ldw;
     if (int rc = take_gn_target(who, gn, a)) return rc;
-    return launch<1>(ctx, a);
+    return launch(ctx, a, true);
 }
 
 // GroupNorm (+ SiLU) -> conv3x3 in ONE launch: the conv reads the UN-normalised tensor and applies y = silu(x * sc[c] + sh[c]) to every halo chunk while it
@@ -1560,9 +1330,9 @@ int fie_conv_up2x_nhwc_f16(fie_ctx* ctx, const void* X, int B, int H, int W, int
         a.gn_partial = gn; a.gn_rows = H * W; a.gn_G = gn_groups; a.gn_cg = Cout / gn_groups;
         a.gn_nch = (int)(gn_rows / 32);
     }
-    const bool dma_ok = a.a1_bytes < (1ll << 31) && a.w_bytes < (1ll << 31) && ((int64_t)(4ll * a.M - 1) * ldc + Cout) * 2 <= (1ll << 30);
-    FIE_REQUIRE(dma_ok, "%s: tensors too large for the LDS-DMA kernels (use fie_conv3x3_nhwc_f16 with upsample2x)", who);
-    if (int rc = launch<1>(ctx, a)) return rc;
+    const bool fits = a.a1_bytes < (1ll << 31) && a.w_bytes < (1ll << 31) && ((int64_t)(4ll * a.M - 1) * ldc + Cout) * 2 <= (1ll << 30);
+    FIE_REQUIRE(fits, "%s: tensors too large for the LDS-DMA kernels (use fie_conv3x3_nhwc_f16 with upsample2x)", who);
+    if (int rc = launch(ctx, a, true)) return rc;
     return FIE_OK;
 }
 

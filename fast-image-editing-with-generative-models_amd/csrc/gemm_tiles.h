@@ -1,6 +1,6 @@
 // The fp8 ring tiles, one list per kernel family: X(code, BM, BN, ST, NW).  gemm_w8.hip / gemm_x8.hip generate their attribute setters AND their launch
-// switches from these lists (so the two cannot disagree), and the launch table of gemm_conv.hip checks its fp8 remap columns against them at compile
-// time.  A new fp8 tile is one X(...) here plus the w8 / x8 column of the rows of gemm_conv.hip that should run on it.
+// switches from these lists (so the two cannot disagree), and the launch table of gemm_select.h checks its fp8 remap columns against them at compile
+// time.  A new fp8 tile is one X(...) here plus the w8 / x8 column of the rows of gemm_select.h that should run on it.
 #pragma once
 // gemm3w8_kernel (fp16 activations x e4m3 weights): 256x128 x 3 stages, 192x128 / 128x128 x 2 stages (8 waves: two and more blocks per CU), 128x64 / 64x64 (4 waves)
 #define FIE_W8_TILES(X) X(62, 256, 128, 3, 8) X(54, 192, 128, 2, 8) X(52, 128, 128, 2, 8) X(42, 128, 64, 3, 4) X(43, 64, 64, 3, 4)
