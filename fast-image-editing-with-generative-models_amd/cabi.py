@@ -343,6 +343,7 @@ def run_edit(pipe, job, step_cache=True):
         raise NotImplementedError(f"run_edit: blend={job['blend'][0]!r} is not part of the C-ABI walk")
     if job.get("lvl_lat") is not None:
         raise NotImplementedError("run_edit: a soft mask (mask_mode='levels' / mask_ramp) is not part of the C-ABI walk")
+    from .pipe import _latent_prep, _lcm_step          # the choice among the plain and masked entries (pipe imports this module)
     ctx = pipe.ctx
     dev = ctx.device
     h, w = job["hw"]
@@ -358,11 +359,8 @@ def run_edit(pipe, job, step_cache=True):
     latents = torch.empty((hw, 4), device=dev, dtype=torch.float32)
     model_in = torch.empty((nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
     mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")
-    if mask_lat is None:
-        ctx.latent_prep(moments, job["noises"][0], job["noises"][1], hw, sf, steps[0]["sqrt_ab"], steps[0]["sqrt_1mab"], latents, model_in)
-    else:
-        z0 = torch.empty((hw, 4), device=dev, dtype=torch.float32)
-        ctx.latent_prep_src(moments, job["noises"][0], job["noises"][1], hw, sf, steps[0]["sqrt_ab"], steps[0]["sqrt_1mab"], latents, model_in, z0)
+    z0 = None if mask_lat is None else torch.empty((hw, 4), device=dev, dtype=torch.float32)
+    _latent_prep(ctx, job, moments, job["noises"][:2], steps[0], latents, model_in, z0, 0, sf)
     cond = ctx.pixels_in(job["ctl_u8"], False).repeat(nb, 1, 1, 1).contiguous()       # upstream runs the ControlNet on the duplicated control image
     decode_in = torch.empty((1, lh, lw, 8), device=dev, dtype=ctx.dtype)
     if step_cache:                      # what does not change over the steps (text K / V, conditioning embedding) is computed by the first forward only
@@ -373,12 +371,7 @@ def run_edit(pipe, job, step_cache=True):
         downs, mid = controlnet_forward(pipe.controlnet, pre + "controlnet.", model_in, t_dev, text, pooled, job["time_ids"], cond, job["cn_scale"])
         eps = unet_forward(pipe.unet, pre + "unet.", model_in, t_dev, text, pooled, job["time_ids"], downs, mid)
         z = None if st["last"] else job["noises"][next_noise]
-        if mask_lat is None:
-            ctx.lcm_step(eps, nb, job["guidance"], latents, z, hw, st["sqrt_ab"], st["sqrt_1mab"], st["c_skip"], st["c_out"], st["sqrt_ab_prev"],
-                         st["sqrt_1mab_prev"], model_in, 1.0 / sf, decode_in)
-        else:
-            ctx.lcm_step_masked(eps, nb, job["guidance"], latents, z, hw, st["sqrt_ab"], st["sqrt_1mab"], st["c_skip"], st["c_out"],
-                                st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in, 1.0 / sf, decode_in, mask_lat[0], z0, job["noises"][1])
+        _lcm_step(ctx, job, eps, st, z, job["noises"][1], latents, model_in, decode_in, z0, 0, sf)
         next_noise += 1
     if step_cache:
         step_cache_end(pipe.unet, pre + "unet.")

@@ -1,10 +1,10 @@
-// Masked-content modes of a mask-restricted edit (include/fie.h: fie_mask_fill_rgb_u8, fie_latent_prep_src_content).
+// Masked-content modes of a mask-restricted edit (include/fie.h: fie_mask_fill_rgb_u8).  The latent modes are
+// fie_latent_prep_src_content's (csrc/lcm.hip).
 //   fill          the hole m = (L >= 128) of a u8 RGB image replaced by a smooth continuation of its surroundings: a push-pull pyramid in
 //                 integer arithmetic.  Push: per level the sums S[c] of the known pixels' values and their count w, over 2x2 children, sizes
 //                 ceil-halved down to 1x1.  Pull, from the top: a cell with w > 0 resolves to its mean in 1/256 units, one without takes the
 //                 9-3-3-1 bilinear tap of the resolved level above (32768 at the top: nothing known at all).  Known pixels keep their bytes.
 //   edge clear    the ControlNet's edge map set to 0 inside the hole (the last pass of the same op, or that pass alone with out == NULL).
-//   latent prep   fie_latent_prep_src, then a select over the latent pixels inside the mask: the init noise itself, or sqrt_1mab * noise.
 // Levels are ordered by kernel boundaries (and, inside the one-block kernel that owns every level of <= 1024 cells, by __syncthreads):
 // no block waits for another, nothing synchronises with the host, every launch goes through fie_launch.
 #include "image_ops.h"
@@ -174,39 +174,8 @@ __global__ __launch_bounds__(256) void fill_final_kernel(const uint8_t* __restri
     }
 }
 
-// the select of the latent modes, over what fie_latent_prep_src has just written: only latent pixels inside the mask are touched
-template <typename T>
-__global__ __launch_bounds__(256) void latent_content_kernel(const uint8_t* __restrict__ m_lat, const float* __restrict__ noise, int64_t HW,
-                                                             float sqrt_1mab, int nothing, float* __restrict__ lat, T* __restrict__ model_in, int copies) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < HW; i += (int64_t)gridDim.x * blockDim.x) {
-        if (!m_lat[i]) continue;
-        float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float z = noise[c * HW + i];
-            o[c] = nothing ? sqrt_1mab * z : z;          // add_noise of the zero latent: one product, nothing to fuse it with
-        }
-        *reinterpret_cast<float4*>(lat + i * 4) = make_float4(o[0], o[1], o[2], o[3]);
-        for (int k = 0; k < copies; ++k) fie_store8(model_in + ((int64_t)k * HW + i) * 8, o);
-    }
-}
-
 using fie_img::grid_1d;
 using fie_img::kPointwiseBlocks;
-
-template <typename T>
-int latent_prep_src_content_t(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW, float sf, float sqrt_ab,
-                              float sqrt_1mab, float* latents_out, void* model_in, int copies, float* z0_out, const uint8_t* mask_lat, int mode) {
-    FIE_REQUIRE(mode >= FIE_CONTENT_ORIGINAL && mode <= FIE_CONTENT_LATENT_NOTHING, "fie_latent_prep_src_content: mode %d outside [0, 3]", mode);
-    FIE_REQUIRE(mask_lat, "fie_latent_prep_src_content: mask_lat is required");
-    const int rc = sizeof(T) == 2 ? fie_latent_prep_src(ctx, moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab, latents_out, model_in, copies, z0_out)
-                                  : fie_latent_prep_src_f32(ctx, moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab, latents_out, model_in, copies, z0_out);
-    if (rc != FIE_OK || mode < FIE_CONTENT_LATENT_NOISE) return rc;
-    fie_launch(ctx, latent_content_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, mask_lat, noise, HW, sqrt_1mab,
-               mode == FIE_CONTENT_LATENT_NOTHING ? 1 : 0, latents_out, (T*)model_in, copies);
-    FIE_LAUNCH_CHECK();
-    return FIE_OK;
-}
 
 }  // namespace
 
@@ -248,19 +217,6 @@ int fie_mask_fill_rgb_u8(fie_ctx* ctx, const uint8_t* src, const uint8_t* mask_l
                (const uint4*)(out && p.K > 0 ? ws + p.off[1] : nullptr), p.K > 0 ? p.h[1] : 0, p.K > 0 ? p.w[1] : 0, out, ctl_in, ctl_out);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
-}
-
-int fie_latent_prep_src_content(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW, float scaling_factor,
-                                float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in, int copies, float* z0_out,
-                                const uint8_t* mask_lat, int mode) {
-    return latent_prep_src_content_t<half_t>(ctx, moments, eps_post, noise, HW, scaling_factor, sqrt_ab, sqrt_1mab, latents_out, model_in, copies,
-                                             z0_out, mask_lat, mode);
-}
-int fie_latent_prep_src_content_f32(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW, float scaling_factor,
-                                    float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in, int copies, float* z0_out,
-                                    const uint8_t* mask_lat, int mode) {
-    return latent_prep_src_content_t<float>(ctx, moments, eps_post, noise, HW, scaling_factor, sqrt_ab, sqrt_1mab, latents_out, model_in, copies,
-                                            z0_out, mask_lat, mode);
 }
 
 }  // extern "C"

@@ -1,6 +1,5 @@
-// K7-K10, K12-embed: small element-wise kernels of the denoising loop (include/fie.h).  All are latency/HBM-bound;
-// scheduler scalars are computed on the host in fp32/fp64 and passed by value (c_skip ~ 1e-8 underflows
-// in fp16, so the LCM update is done in fp32 on an fp32 master copy of the latents).
+// K7, K10, K12-embed: the embed, pixel and utility kernels around the denoising loop (include/fie.h).  All are latency/HBM-bound.  The two
+// per-latent-pixel ops of the loop, latent prep (K9) and the LCM step (K8), are csrc/lcm.hip.
 #include "image_ops.h"
 
 namespace {
@@ -171,66 +170,6 @@ __global__ void pixels_out_kernel(const T* src, int64_t ld, int64_t npix, uint8_
     }
 }
 
-template <typename T>
-__global__ void latent_prep_kernel(const T* moments, const float* eps_post, const float* noise, int64_t HW, float sf,
-                                   float sqrt_ab, float sqrt_1mab, float* lat, T* model_in, int copies) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < HW; i += (int64_t)gridDim.x * blockDim.x) {
-        float m[8], o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        fie_load8(moments + i * 8, m);
-        float4 l;
-        float* lp = &l.x;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float logvar = fminf(fmaxf(m[4 + c], -30.f), 20.f);
-            const float z0 = (m[c] + fie_expf(0.5f * logvar) * eps_post[c * HW + i]) * sf;
-            const float x = sqrt_ab * z0 + sqrt_1mab * noise[c * HW + i];
-            lp[c] = x;
-            o[c] = x;
-        }
-        *reinterpret_cast<float4*>(lat + i * 4) = l;
-        for (int k = 0; k < copies; ++k) fie_store8(model_in + ((int64_t)k * HW + i) * 8, o);
-    }
-}
-
-template <typename T>
-struct LcmArgs {
-    const T* eps; int64_t ld_eps; int nb; float guidance;
-    float* lat; const float* noise; int64_t HW;
-    float sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p;
-    T* model_in; int copies; float inv_sf; T* decode_in;
-};
-
-template <typename T>
-__global__ void lcm_step_kernel(LcmArgs<T> p) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < p.HW; i += (int64_t)gridDim.x * blockDim.x) {
-        float e0[4], e1[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            e0[c] = (float)p.eps[i * p.ld_eps + c];
-            e1[c] = p.nb == 2 ? (float)p.eps[(p.HW + i) * p.ld_eps + c] : e0[c];
-        }
-        float4 l = *reinterpret_cast<const float4*>(p.lat + i * 4);
-        float* lp = &l.x;
-        float o[8] = {0, 0, 0, 0, 0, 0, 0, 0}, od[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float e = e0[c];
-            if (p.nb == 2) e = e + p.guidance * (e1[c] - e);              // eps_u + g (eps_c - eps_u)
-            const float x = lp[c];
-            const float x0 = (x - p.s1mab_t * e) / p.sab_t;
-            float den = p.c_out * x0 + p.c_skip * x;
-            if (p.noise) den = p.sab_p * den + p.s1mab_p * p.noise[c * p.HW + i];
-            lp[c] = den;
-            o[c] = den;
-            od[c] = den * p.inv_sf;
-        }
-        *reinterpret_cast<float4*>(p.lat + i * 4) = l;
-        if (p.model_in)
-            for (int k = 0; k < p.copies; ++k) fie_store8(p.model_in + ((int64_t)k * p.HW + i) * 8, o);
-        if (p.decode_in) fie_store8(p.decode_in + i * 8, od);
-    }
-}
-
 using fie_img::grid_1d;
 using fie_img::kPointwiseBlocks;
 
@@ -267,30 +206,6 @@ int pixels_out_t(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, uin
     FIE_REQUIRE(ctx && src && dst && H > 0 && W > 0 && ld_in >= 3, "fie_pixels_out: bad argument");
     const int64_t n = (int64_t)H * W;
     fie_launch(ctx, pixels_out_kernel<T>, dim3(grid_1d(n, kPointwiseBlocks)), dim3(256), 0, (const T*)src, ld_in, n, dst);
-    FIE_LAUNCH_CHECK();
-    return FIE_OK;
-}
-
-template <typename T>
-int latent_prep_t(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW, float sf, float sqrt_ab,
-                  float sqrt_1mab, float* latents_out, void* model_in, int copies) {
-    FIE_REQUIRE(ctx && moments && eps_post && noise && latents_out && model_in && HW > 0 && copies > 0, "fie_latent_prep: bad argument");
-    fie_launch(ctx, latent_prep_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, (const T*)moments, eps_post, noise, HW, sf, sqrt_ab, sqrt_1mab, latents_out, (T*)model_in, copies);
-    FIE_LAUNCH_CHECK();
-    return FIE_OK;
-}
-
-template <typename T>
-int lcm_step_t(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents, const float* noise, int64_t HW,
-               float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out, float sqrt_ab_prev, float sqrt_1mab_prev, void* model_in,
-               int copies, float inv_scaling, void* decode_in) {
-    FIE_REQUIRE(ctx && eps && latents && HW > 0, "fie_lcm_step: bad argument");
-    FIE_REQUIRE(nb == 1 || nb == 2, "fie_lcm_step: nb=%d (1 or 2)", nb);
-    FIE_REQUIRE(ld_eps % 4 == 0 && ld_eps >= 4, "fie_lcm_step: ld_eps must be a multiple of 4");
-    FIE_REQUIRE(sqrt_ab_t > 0.f, "fie_lcm_step: sqrt(alpha_bar_t) must be positive");
-    LcmArgs<T> p = {(const T*)eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out,
-                    sqrt_ab_prev, sqrt_1mab_prev, (T*)model_in, copies, inv_scaling, (T*)decode_in};
-    fie_launch(ctx, lcm_step_kernel<T>, dim3(grid_1d(HW, kPointwiseBlocks)), dim3(256), 0, p);
     FIE_LAUNCH_CHECK();
     return FIE_OK;
 }
@@ -423,26 +338,6 @@ int fie_pixels_out_f16_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, i
 }
 int fie_pixels_out_f32_u8(fie_ctx* ctx, const void* src, int64_t ld_in, int H, int W, uint8_t* dst) {
     return pixels_out_t<float>(ctx, src, ld_in, H, W, dst);
-}
-int fie_latent_prep(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW,
-                    float scaling_factor, float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in, int copies) {
-    return latent_prep_t<half_t>(ctx, moments, eps_post, noise, HW, scaling_factor, sqrt_ab, sqrt_1mab, latents_out, model_in, copies);
-}
-int fie_latent_prep_f32(fie_ctx* ctx, const void* moments, const float* eps_post, const float* noise, int64_t HW,
-                        float scaling_factor, float sqrt_ab, float sqrt_1mab, float* latents_out, void* model_in, int copies) {
-    return latent_prep_t<float>(ctx, moments, eps_post, noise, HW, scaling_factor, sqrt_ab, sqrt_1mab, latents_out, model_in, copies);
-}
-int fie_lcm_step(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents, const float* noise, int64_t HW,
-                 float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out, float sqrt_ab_prev, float sqrt_1mab_prev,
-                 void* model_in, int copies, float inv_scaling, void* decode_in) {
-    return lcm_step_t<half_t>(ctx, eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out, sqrt_ab_prev,
-                              sqrt_1mab_prev, model_in, copies, inv_scaling, decode_in);
-}
-int fie_lcm_step_f32(fie_ctx* ctx, const void* eps, int64_t ld_eps, int nb, float guidance, float* latents, const float* noise,
-                     int64_t HW, float sqrt_ab_t, float sqrt_1mab_t, float c_skip, float c_out, float sqrt_ab_prev,
-                     float sqrt_1mab_prev, void* model_in, int copies, float inv_scaling, void* decode_in) {
-    return lcm_step_t<float>(ctx, eps, ld_eps, nb, guidance, latents, noise, HW, sqrt_ab_t, sqrt_1mab_t, c_skip, c_out, sqrt_ab_prev,
-                             sqrt_1mab_prev, model_in, copies, inv_scaling, decode_in);
 }
 
 }  // extern "C"

@@ -1458,54 +1458,54 @@ class Context:
         low, high = pair.cpu().tolist()
         return low, high
 
-    def latent_prep(self, moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in):
+    def _latent_prep(self, entry, moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in, *tail):
+        """The fie_latent_prep* entry `entry` (its _f32 twin in an fp32 context): the arguments all three share, then the entry's own."""
         self.sync_stream()
-        _chk((lib().fie_latent_prep_f32 if self.f32 else lib().fie_latent_prep)(self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab),
-                                   float(sqrt_1mab), _p(latents), _p(model_in), model_in.shape[0]))
+        _chk(getattr(lib(), entry + ("_f32" if self.f32 else ""))(
+            self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab), float(sqrt_1mab), _p(latents), _p(model_in),
+            model_in.shape[0], *tail))
+
+    def latent_prep(self, moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in):
+        self._latent_prep("fie_latent_prep", moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in)
 
     def latent_prep_src(self, moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in, z0):
         """latent_prep() that also stores the clean source latent z0 (f32 [hw, 4]) for a masked edit."""
-        self.sync_stream()
-        _chk((lib().fie_latent_prep_src_f32 if self.f32 else lib().fie_latent_prep_src)(
-            self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab), float(sqrt_1mab), _p(latents), _p(model_in),
-            model_in.shape[0], _p(z0)))
+        self._latent_prep("fie_latent_prep_src", moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in, _p(z0))
 
     def latent_prep_src_content(self, moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in, z0, mask_lat, mode):
         """latent_prep_src() with a masked-content mode (fie_amd/mask.py: CONTENT_MODES names them): where mask_lat != 0 the initial latent is
         the init noise itself ("latent_noise") or sqrt_1mab * noise ("latent_nothing"); everything else keeps latent_prep_src's bits."""
         from . import mask as hmask
+        self._latent_prep("fie_latent_prep_src_content", moments, eps_post, noise, hw, sf, sqrt_ab, sqrt_1mab, latents, model_in, _p(z0),
+                          _p(mask_lat), hmask.CONTENT_CODES[mode])
+
+    def _lcm_step(self, entry, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in, inv_sf, decode_in,
+                  *tail):
+        """The fie_lcm_step* entry `entry` (its _f32 twin in an fp32 context): the arguments all three share, then the entry's own."""
         self.sync_stream()
-        _chk((lib().fie_latent_prep_src_content_f32 if self.f32 else lib().fie_latent_prep_src_content)(
-            self.h, _p(moments), _p(eps_post), _p(noise), hw, float(sf), float(sqrt_ab), float(sqrt_1mab), _p(latents), _p(model_in),
-            model_in.shape[0], _p(z0), _p(mask_lat), hmask.CONTENT_CODES[mode]))
+        _chk(getattr(lib(), entry + ("_f32" if self.f32 else ""))(
+            self.h, _p(eps), eps.shape[-1], nb, float(guidance), _p(latents), _p(noise), hw, float(sab_t), float(s1mab_t), float(c_skip),
+            float(c_out), float(sab_p), float(s1mab_p), _p(model_in), model_in.shape[0] if model_in is not None else 0, float(inv_sf),
+            _p(decode_in), *tail))
+
+    def lcm_step(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
+                 inv_sf, decode_in):
+        self._lcm_step("fie_lcm_step", eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
+                       inv_sf, decode_in)
 
     def lcm_step_masked(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
                         inv_sf, decode_in, mask_lat, z0, noise_init):
         """lcm_step() followed, in the same pass, by the blend of a masked edit: latent pixels with mask_lat == 0 take
         sab_p z0 + s1mab_p noise_init (z0 on the last step, noise None)."""
-        self.sync_stream()
-        _chk((lib().fie_lcm_step_masked_f32 if self.f32 else lib().fie_lcm_step_masked)(
-            self.h, _p(eps), eps.shape[-1], nb, float(guidance), _p(latents), _p(noise), hw, float(sab_t), float(s1mab_t), float(c_skip),
-            float(c_out), float(sab_p), float(s1mab_p), _p(model_in), model_in.shape[0] if model_in is not None else 0, float(inv_sf),
-            _p(decode_in), _p(mask_lat), _p(z0), _p(noise_init)))
+        self._lcm_step("fie_lcm_step_masked", eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
+                       inv_sf, decode_in, _p(mask_lat), _p(z0), _p(noise_init))
 
     def lcm_step_levels(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
                         inv_sf, decode_in, lvl_lat, z0, noise_init, steps, step):
         """lcm_step_masked() of a soft mask: lvl_lat u8 [hw] holds levels 0 .. 255, `step` is this step's place among
         the `steps` of the edit; a latent pixel of level v is inside iff v * steps > 255 * (steps - 1 - step)."""
-        self.sync_stream()
-        _chk((lib().fie_lcm_step_levels_f32 if self.f32 else lib().fie_lcm_step_levels)(
-            self.h, _p(eps), eps.shape[-1], nb, float(guidance), _p(latents), _p(noise), hw, float(sab_t), float(s1mab_t), float(c_skip),
-            float(c_out), float(sab_p), float(s1mab_p), _p(model_in), model_in.shape[0] if model_in is not None else 0, float(inv_sf),
-            _p(decode_in), _p(lvl_lat), _p(z0), _p(noise_init), int(steps), int(step)))
-
-    def lcm_step(self, eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
-                 inv_sf, decode_in):
-        self.sync_stream()
-        _chk((lib().fie_lcm_step_f32 if self.f32 else lib().fie_lcm_step)(self.h, _p(eps), eps.shape[-1], nb, float(guidance), _p(latents), _p(noise), hw,
-                                float(sab_t), float(s1mab_t), float(c_skip), float(c_out), float(sab_p),
-                                float(s1mab_p), _p(model_in), model_in.shape[0] if model_in is not None else 0,
-                                float(inv_sf), _p(decode_in)))
+        self._lcm_step("fie_lcm_step_levels", eps, nb, guidance, latents, noise, hw, sab_t, s1mab_t, c_skip, c_out, sab_p, s1mab_p, model_in,
+                       inv_sf, decode_in, _p(lvl_lat), _p(z0), _p(noise_init), int(steps), int(step))
 
 
 def canny_rgb(rgb_u8, low=100, high=200):

@@ -44,6 +44,32 @@ class MaskLevels:
         self.support, self.levels = support, levels
 
 
+def _latent_prep(ctx, job, moments, noises, first_step, latents, rows, z0, image, sf):
+    """The latent prep of one image (or sweep variant) of `job`: plain; with a mask the one that keeps z0; with a latent
+    content mode (section 14) that one and the mode's select.  noises: (posterior draw, init noise); rows: the image's model_in rows; image: its
+    place among the job's masks."""
+    head = (moments, noises[0], noises[1], latents.shape[0], sf, first_step["sqrt_ab"], first_step["sqrt_1mab"], latents, rows)
+    if job.get("mask_lat") is None:
+        ctx.latent_prep(*head)
+    elif job.get("content_lat") is None:
+        ctx.latent_prep_src(*head, z0)
+    else:
+        ctx.latent_prep_src_content(*head, z0, job["content_lat"][image], job["content"])
+
+
+def _lcm_step(ctx, job, eps_rows, st, z, noise_init, latents, rows, decode_row, z0, image, sf):
+    """The LCM step `st` of one image (or sweep variant) of `job`: plain; with a mask the one that blends towards z0 at the step's noise level;
+    with a soft mask the one that compares the latent levels with the step's place st["index"] among st["count"]."""
+    head = (eps_rows, job["nb"], job["guidance"], latents, z, latents.shape[0], st["sqrt_ab"], st["sqrt_1mab"], st["c_skip"], st["c_out"],
+            st["sqrt_ab_prev"], st["sqrt_1mab_prev"], rows, 1.0 / sf, decode_row)
+    if job.get("mask_lat") is None:
+        ctx.lcm_step(*head)
+    elif job.get("lvl_lat") is None:
+        ctx.lcm_step_masked(*head, job["mask_lat"][image], z0, noise_init)
+    else:
+        ctx.lcm_step_levels(*head, job["lvl_lat"][image], z0, noise_init, st["count"], st["index"])
+
+
 class HipImg2ImgPipeline:
     # [additive] Prompt emphasis (DESIGN.md section 23): None (off: prompts are tokenised as they are), or the weight in [0, 8] of the words a prompt
     # marks with [...]; `(words:1.3)` then carries its own.  Read on the host when a job is prepared (FastEditor.set_prompt_emphasis sets it).
@@ -460,7 +486,6 @@ class HipImg2ImgPipeline:
         # 1024^2 VAE tensors of a batch would cross the 2 GiB operand limit of the buffer-load kernels, and gain nothing)
         per = len(job["noises"]) // n                     # noise tensors per image
         mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")     # a masked edit
-        lvl_lat = job.get("lvl_lat")                      # a soft mask's latent levels: the masked step's twin reads them
         latents = torch.empty((n, hw, 4), device=dev, dtype=torch.float32)
         z0 = torch.empty((n, hw, 4), device=dev, dtype=torch.float32) if mask_lat is not None else None
         model_in = torch.empty((n * nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
@@ -468,15 +493,8 @@ class HipImg2ImgPipeline:
         for i in range(n):
             x_img = ctx.pixels_in(srcs[i], True)
             moments = cabi.vae_encode(self.vae, x_img) if self.cpp_walks else self.vae.encode_moments(x_img)[0]
-            if mask_lat is None:
-                ctx.latent_prep(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
-                                steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb])
-            elif job.get("content_lat") is None:
-                ctx.latent_prep_src(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
-                                    steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb], z0[i])
-            else:
-                ctx.latent_prep_src_content(moments, job["noises"][i * per], job["noises"][i * per + 1], hw, sf, steps[0]["sqrt_ab"],
-                                            steps[0]["sqrt_1mab"], latents[i], model_in[i * nb:(i + 1) * nb], z0[i], job["content_lat"][i], content)
+            _latent_prep(ctx, job, moments, job["noises"][i * per:i * per + 2], steps[0], latents[i], model_in[i * nb:(i + 1) * nb],
+                         None if z0 is None else z0[i], i, sf)
         next_noise = 2
         main.wait_stream(side)
         self._mark("clip+vae_encode")
@@ -499,18 +517,8 @@ class HipImg2ImgPipeline:
             self._mark("unet_dec")
             for i in range(n):
                 z = None if st["last"] else job["noises"][i * per + next_noise]
-                if mask_lat is None:
-                    ctx.lcm_step(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
-                                 st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
-                                 1.0 / sf, decode_in[i:i + 1])
-                elif lvl_lat is None:
-                    ctx.lcm_step_masked(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
-                                        st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
-                                        1.0 / sf, decode_in[i:i + 1], mask_lat[i], z0[i], job["noises"][i * per + 1])
-                else:
-                    ctx.lcm_step_levels(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
-                                        st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
-                                        1.0 / sf, decode_in[i:i + 1], lvl_lat[i], z0[i], job["noises"][i * per + 1], st["count"], st["index"])
+                _lcm_step(ctx, job, eps[i * nb:(i + 1) * nb], st, z, job["noises"][i * per + 1], latents[i], model_in[i * nb:(i + 1) * nb],
+                          decode_in[i:i + 1], None if z0 is None else z0[i], i, sf)
             next_noise += 1
             self._mark("lcm_step")
         # 8-9. decode + postprocess
@@ -572,7 +580,7 @@ class HipImg2ImgPipeline:
             cond_emb = self.controlnet.cond_embedding(ctx.pixels_in(ctl, False)).repeat_interleave(k * nb, dim=0)
             tb0 = (self.unet.time_rowbias(job["t_dev"][0]), self.controlnet.time_rowbias(job["t_dev"][0]))
         text_len = text.shape[0] // (k * nb)
-        mask_lat, mask_px, lvl_lat = job.get("mask_lat"), job.get("mask_px"), job.get("lvl_lat")
+        mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")
         latents = torch.empty((k, hw, 4), device=dev, dtype=torch.float32)
         z0 = torch.empty((hw, 4), device=dev, dtype=torch.float32) if mask_lat is not None else None
         model_in = torch.empty((k * nb, lh, lw, 8), device=dev, dtype=ctx.dtype)
@@ -582,13 +590,7 @@ class HipImg2ImgPipeline:
         moments = cabi.vae_encode(self.vae, x_img) if self.cpp_walks else self.vae.encode_moments(x_img)[0]
         for i, p in enumerate(plans):                     # z0 does not depend on the variant: every variant writes the same values
             rows = model_in[i * nb:(i + 1) * nb]
-            if mask_lat is None:
-                ctx.latent_prep(moments, noises[0], noises[1], hw, sf, p[0]["sqrt_ab"], p[0]["sqrt_1mab"], latents[i], rows)
-            elif job.get("content_lat") is None:
-                ctx.latent_prep_src(moments, noises[0], noises[1], hw, sf, p[0]["sqrt_ab"], p[0]["sqrt_1mab"], latents[i], rows, z0)
-            else:
-                ctx.latent_prep_src_content(moments, noises[0], noises[1], hw, sf, p[0]["sqrt_ab"], p[0]["sqrt_1mab"], latents[i], rows, z0,
-                                            job["content_lat"][0], content)
+            _latent_prep(ctx, job, moments, noises[:2], p[0], latents[i], rows, z0, 0, sf)
         main.wait_stream(side)
         self._mark("clip+vae_encode")
         decode_in = torch.empty((k, lh, lw, 8), device=dev, dtype=ctx.dtype)
@@ -608,18 +610,8 @@ class HipImg2ImgPipeline:
             self._mark("unet_dec")
             for i, st, zi in active:
                 z = None if zi is None else noises[zi]
-                if mask_lat is None:
-                    ctx.lcm_step(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
-                                 st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
-                                 1.0 / sf, decode_in[i:i + 1])
-                elif lvl_lat is None:
-                    ctx.lcm_step_masked(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
-                                        st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
-                                        1.0 / sf, decode_in[i:i + 1], mask_lat[0], z0, noises[1])
-                else:                                     # the variant's own K and j: it releases a level by its own step count
-                    ctx.lcm_step_levels(eps[i * nb:(i + 1) * nb], nb, job["guidance"], latents[i], z, hw, st["sqrt_ab"], st["sqrt_1mab"],
-                                        st["c_skip"], st["c_out"], st["sqrt_ab_prev"], st["sqrt_1mab_prev"], model_in[i * nb:(i + 1) * nb],
-                                        1.0 / sf, decode_in[i:i + 1], lvl_lat[0], z0, noises[1], st["count"], st["index"])
+                # st is the variant's own step record: with a soft mask it releases a level by its own step count
+                _lcm_step(ctx, job, eps[i * nb:(i + 1) * nb], st, z, noises[1], latents[i], model_in[i * nb:(i + 1) * nb], decode_in[i:i + 1], z0, 0, sf)
             self._mark("lcm_step")
         dec = (lambda z: cabi.vae_decode(self.vae, z)) if self.cpp_walks else self.vae.decode
         if job.get("blend"):

@@ -1,5 +1,5 @@
 """The references, bounds and builders of tests/test_pointwise_gpu.py (tests/pointwise_check.py) on fp32 emulations of the kernels of
-csrc/pointwise.hip: a straight emulation (torch fp32, one rounding per operation, no fused multiply-add) stays inside every bound with no
+csrc/pointwise.hip and csrc/lcm.hip: a straight emulation (torch fp32, one rounding per operation, no fused multiply-add) stays inside every bound with no
 mismatch, and every defect model is flagged on the builders' data.  The sizes are the GPU module's small ones; the large ones differ only
 in the number of elements.
 

@@ -1,4 +1,4 @@
-"""The pointwise kernels of the denoising loop (csrc/pointwise.hip) per element, on the f16 context and, wherever an _f32 entry exists, on an
+"""The pointwise kernels of the denoising loop (csrc/pointwise.hip, csrc/lcm.hip) per element, on the f16 context and, wherever an _f32 entry exists, on an
 fp32 context: float64 references on the stored inputs, bounds derived from the fp32 arithmetic of each expression and the builders of
 tests/pointwise_check.py (tests/test_pointwise_check_cpu.py shows on the CPU that a straight fp32 emulation passes every check and which
 defects each one flags).  No assertion is normalised by a tensor's maximum; every message names the first bad elements.
