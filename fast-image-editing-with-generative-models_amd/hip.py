@@ -103,6 +103,11 @@ class UnetConfig(ctypes.Structure):
     _fields_ = header.STRUCTS["fie_unet_config"]
 
 
+class ControlTable(ctypes.Structure):
+    """include/fie.h: fie_control_table (the segments of one fie_control_add launch)."""
+    _fields_ = header.STRUCTS["fie_control_table"]
+
+
 class Program:
     """A recorded launch program (include/fie.h, fie_program_*).  `keep` holds every tensor the op wrappers allocated while it
     was recorded: the program references their memory by raw pointer."""
@@ -934,6 +939,74 @@ class Context:
             raise ValueError("kv_emphasis: w and vflags live on the device of x")
         _chk(lib().fie_kv_emphasis(self.h, _p(x), x.stride(0), rows, ncols, _p(w), _p(vflags), int(self.f32)))
         return x
+
+    def control_pyramid(self, e, a, binary, levels=3, out=None):
+        """The control weights of one image (fie_control_pyramid_u8): e a contiguous u8 [H, W] tensor on the device, H, W
+        multiples of 8 in 8 .. 2048 -- an L mask (binary=True: read as 255 where >= 128) or a level map (binary=False); a in 0 .. 255, the
+        integer of `in_mask`.  -> f32 [P_tot], the weights of `levels` pyramid levels, finest first (fie_amd/control.py: weights_numpy);
+        `out`: a contiguous f32 [P_tot] tensor to write.  One launch, no synchronisation."""
+        from . import control
+        self.sync_stream()
+        if not torch.is_tensor(e) or e.dim() != 2 or e.dtype != torch.uint8 or not e.is_contiguous():
+            raise ValueError(f"control_pyramid: a contiguous u8 [H, W] map, got {tuple(getattr(e, 'shape', ()))} {getattr(e, 'dtype', type(e).__name__)}")
+        if isinstance(a, bool) or not isinstance(a, numbers.Integral) or not 0 <= a <= 255:
+            raise ValueError(f"control_pyramid: a={a!r}: an integer in 0 .. 255")
+        h, w = e.shape
+        if h > 2048 or w > 2048:
+            raise ValueError(f"control_pyramid: a map of {w}x{h} is above 2048")
+        p_tot = sum(hl * wl for hl, wl in control.level_dims(h, w, levels))         # a ValueError for a size that is no multiple of 8
+        if out is None:
+            out = self._alloc((p_tot,), torch.float32)
+        elif not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (p_tot,) or not out.is_contiguous() or out.device != e.device:
+            raise ValueError(f"control_pyramid: out must be a contiguous f32 [{p_tot}] tensor on the device of e")
+        _chk(lib().fie_control_pyramid_u8(self.h, _p(e), h, w, int(levels), int(a), int(bool(binary)), _p(out)))
+        return out
+
+    def control_add(self, segments, w, rows_per_image, outs=None):
+        """out_i = u_i + (s_i * w[p]) * t_i for all residuals of one evaluation in one launch (fie_control_add).  segments:
+        1 .. 16 tuples (u, t, P, woff, s) -- u, t contiguous tensors of one shape [..., C] in the context's dtype, C % 8 == 0, whose rows are B
+        batch rows of P latent positions; woff: where the level of the residual starts in a row of w; s: its scale.  w: contiguous f32
+        [images, P_tot] on the device; batch row b reads image b // rows_per_image.  -> the list of fresh output tensors, shaped like u.
+        Where s * w is 0 the output is u's bits and t is not read.  `outs`: one contiguous tensor per segment to write, shaped like its u and
+        no operand.  No synchronisation."""
+        self.sync_stream()
+        segments = list(segments)
+        if outs is not None and len(outs) != len(segments):
+            raise ValueError(f"control_add: {len(outs)} outs for {len(segments)} segments")
+        n_max = header.DEFINES["CONTROL_MAX_SEGMENTS"]
+        if not 1 <= len(segments) <= n_max:
+            raise ValueError(f"control_add: {len(segments)} segments, 1 .. {n_max}")
+        if not torch.is_tensor(w) or w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous() or w.device.type != self.device.type:
+            raise ValueError("control_add: w must be a contiguous f32 [images, P_tot] tensor on the device")
+        if isinstance(rows_per_image, bool) or not isinstance(rows_per_image, numbers.Integral) or rows_per_image < 1:
+            raise ValueError(f"control_add: rows_per_image={rows_per_image!r}: a positive integer")
+        images, p_tot = w.shape
+        tab, made = ControlTable(), []
+        tab.count = len(segments)
+        for i, (u, t, p, woff, s) in enumerate(segments):
+            ok = (torch.is_tensor(u) and torch.is_tensor(t) and u.dtype == self.dtype == t.dtype and u.dim() >= 2 and u.shape == t.shape
+                  and u.is_contiguous() and t.is_contiguous() and u.device == w.device == t.device and u.numel() > 0)
+            if not ok:
+                raise ValueError(f"control_add: segment {i}: u and t are contiguous {self.dtype} tensors of one shape on the device of w")
+            c, rows = u.shape[-1], u.numel() // u.shape[-1]
+            if c % 8 or p < 1 or rows % p or woff < 0 or woff + p > p_tot:
+                raise ValueError(f"control_add: segment {i}: C = {c} (C % 8 == 0), {rows} rows of P = {p} positions, weights {woff} .. {woff + p} of {p_tot}")
+            if -(-(rows // p) // rows_per_image) > images:
+                raise ValueError(f"control_add: segment {i}: {rows // p} batch rows at {rows_per_image} per image are more than the {images} images of w")
+            if not isinstance(s, numbers.Real) or s != s:
+                raise ValueError(f"control_add: segment {i}: s={s!r}: a number")
+            if outs is None:
+                out = self._alloc(tuple(u.shape))
+            else:
+                out = outs[i]
+                if not (torch.is_tensor(out) and out.dtype == u.dtype and out.shape == u.shape and out.is_contiguous() and out.device == u.device
+                        and out.data_ptr() not in (u.data_ptr(), t.data_ptr())):
+                    raise ValueError(f"control_add: segment {i}: out must be a contiguous {self.dtype} tensor of u's shape, and a tensor of its own")
+            made.append(out)
+            tab.C[i], tab.P[i], tab.woff[i], tab.rows[i], tab.s[i] = c, p, woff, rows, float(s)
+            tab.u[i], tab.t[i], tab.out[i] = _p(u), _p(t), _p(out)
+        _chk(lib().fie_control_add(self.h, ctypes.byref(tab), _p(w), p_tot, int(rows_per_image), int(self.f32)))
+        return made
 
     def mask_support(self, levels, out=None):
         """The support of a level map: u8 of any shape (contiguous) -> u8 of that shape, 255 where the level is > 0 (fie_mask_support_u8)."""

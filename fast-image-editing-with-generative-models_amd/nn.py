@@ -507,3 +507,58 @@ class ControlNet(_CondNet):
         b, h, w, c = mid.shape
         m = self.zero_mid(ctx, mid.view(-1, c), scale=scale, residual=unet_mid.view(-1, c)).view(b, h, w, c)
         return out, m
+
+    @property
+    def n_out(self):
+        """The residuals the net hands over: one per skip tensor and the mid block's."""
+        return len(self.zero) + 1
+
+    def residual_levels(self):
+        """The pyramid level of every residual, the mid block's last: 0 at the latent size, one more behind each down-sampler."""
+        lv = [0]
+        for i, (layers, ds) in enumerate(self.down):
+            lv += [i] * len(layers) + ([i + 1] if ds is not None else [])
+        return lv + [lv[-1]]
+
+    def add_residuals_weighted(self, skips, mid, scales, unet_skips, unet_mid, w=None, rows_per_image=1):
+        """add_residuals() under control weights.  scales: one s_i per residual, the mid block's last
+        (fie_amd/control.py: layer_scales).  w None -- the scalar path: every zero-conv runs as in add_residuals() with scale = s_i, the same
+        kernels.  w f32 [images, P_tot] on the device, the weights of every latent position of every pyramid level -- the map path: the zero-convs
+        write the bare residuals (scale 1, nothing added) and ONE fie_control_add gives every out_i = u_i + (s_i w[p]) t_i; batch row b reads the
+        weights of image b // rows_per_image.  Either way a residual with s_i == 0 launches nothing: the UNet's tensor is passed through."""
+        ctx = self.ctx
+        us = list(unet_skips) + [unet_mid]
+        cs = list(skips) + [mid]
+        zs = self.zero + [self.zero_mid]
+        if not len(scales) == len(us) == len(cs) == len(zs):
+            raise ValueError(f"add_residuals_weighted: {len(scales)} scales for the {len(zs)} residuals of the net")
+        out = [passed_through(u) if s == 0 else None for u, s in zip(us, scales)]
+        on = [i for i, s in enumerate(scales) if s != 0]
+        if w is None:
+            for i in on:
+                b, h, ww, c = cs[i].shape
+                out[i] = zs[i](ctx, cs[i].view(-1, c), scale=scales[i], residual=us[i].view(-1, c)).view(b, h, ww, c)
+        elif on:
+            levels, dims, offs = self.residual_levels(), [], []
+            for i in range(len(cs)):               # the level sizes as the net's own tensors have them
+                if levels[i] == len(dims):
+                    offs.append(sum(hh * ww for hh, ww in dims))
+                    dims.append(tuple(cs[i].shape[1:3]))
+            if w.shape[1] != sum(hh * ww for hh, ww in dims):
+                raise ValueError(f"add_residuals_weighted: w has {w.shape[1]} weights per image, the net's levels {dims} have {sum(hh * ww for hh, ww in dims)}")
+            segs = []
+            for i in on:
+                b, h, ww, c = cs[i].shape
+                if (h, ww) != dims[levels[i]]:
+                    raise ValueError(f"add_residuals_weighted: residual {i} is {h}x{ww}, its level {dims[levels[i]]}")
+                t = zs[i](ctx, cs[i].view(-1, c)).view(b, h, ww, c)
+                segs.append((us[i], t, h * ww, offs[levels[i]], scales[i]))
+            for i, o in zip(on, ctx.control_add(segs, w, rows_per_image)):
+                out[i] = o
+        return out[:-1], out[-1]
+
+
+def passed_through(u):
+    """A UNet tensor that takes a residual's place unchanged, as a tensor object of its own: like a zero-conv's output it carries no GroupNorm
+    partial sums of a producer (hip.py: _gn_stats_arm), so its readers take the path they take behind add_residuals()."""
+    return u.view(u.shape)

@@ -2,6 +2,7 @@
 StableDiffusionXLControlNetImg2ImgPipeline call at /root/reference/src/pipeline.py:261-272, but every stage
 (CLIP text, VAE encode, ControlNet + UNet evaluations, CFG + LCM step, VAE decode, pixel conversion) runs in the
 hand-written HIP kernels of csrc/ (call order: SURVEY.md 3.2 steps 1-9)."""
+import gc
 import itertools
 import os
 import threading
@@ -12,11 +13,12 @@ import torch
 from PIL import Image
 
 from . import cabi, hip
+from . import control as hctl
 from . import emphasis as hemph
 from . import mask as hmask
 from .clip import ClipText, eos_positions
 from .lcm import LCMSchedule
-from .nn import ControlNet, UNet
+from .nn import ControlNet, UNet, passed_through
 from .presets import LCM_SCHED
 from .tokenizer import StandInTokenizer
 from .vae import VAE
@@ -74,6 +76,10 @@ class HipImg2ImgPipeline:
     # [additive] Prompt emphasis: None (off: prompts are tokenised as they are), or the weight in [0, 8] of the words a prompt
     # marks with [...]; `(words:1.3)` then carries its own.  Read on the host when a job is prepared (FastEditor.set_prompt_emphasis sets it).
     prompt_emphasis = None
+    # [additive] Control weights: None (off: the ControlNet's residuals are added at `controlnet_conditioning_scale`, at
+    # every step, everywhere), or a fie_amd/control.py Setting (layers, steps, in_mask) as check() returns it.  Read on the host when a job is
+    # prepared (FastEditor.set_control_weights sets it).
+    control_weights = None
 
     def __init__(self, ctx, cfgs, sds, tokenizers=None, sched_cfg=None, noise_dtype=None, weight_dtype="f16"):
         """cfgs / sds: dicts with keys unet, controlnet, vae, clip_l, clip_g (configs / diffusers-named state dicts).
@@ -206,14 +212,16 @@ class HipImg2ImgPipeline:
         return self._prepare(prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                              controlnet_conditioning_scale, generator, mask_image, spec)
 
-    def _mask_job(self, mask_image, spec, h, w):
+    def _mask_job(self, mask_image, spec, h, w, ctl_a=None):
         """Mask tensors of one image under its MaskSpec: (mask_lat u8 [1, h/8 * w/8], mask_px f32 [1, h, w] or None without paste-back, the
         edit-size L mask u8 [1, h, w], lvl_lat u8 [1, h/8 * w/8] or None), made on the device on the current stream, in front of the job:
         the optional grow (fie_mask_grow_u8), a soft mask's level map V -- the mask itself ("levels"), fie_mask_ramp_u8 of the grown mask, or a
         MaskLevels pair's -- and its support, which is the L mask returned, then fie_mask_prep on that; lvl_lat holds V's latent levels
-        (fie_mask_levels_u8), which the latent step alone reads (DESIGN.md sections 8, 16, 21)."""
+        (fie_mask_levels_u8), which the latent step alone reads (DESIGN.md sections 8, 16, 21).  `ctl_a`: None, or the integer of the control
+        weights' `in_mask`: a fifth entry then holds the weights of every latent position of every pyramid level, f32
+        [1, P_tot], made by fie_control_pyramid_u8 from the level map, or from the L mask behind the grow."""
         if mask_image is None:
-            return None, None, None, None
+            return (None,) * (4 if ctl_a is None else 5)
         pair = isinstance(mask_image, MaskLevels)         # support and levels as the caller resized them: nothing to grow, ramp or derive
         if pair:
             if spec.mode != "levels":
@@ -239,7 +247,31 @@ class HipImg2ImgPipeline:
                     lm = self.ctx.mask_support(lv)
             m_px, m_lat = self.ctx.mask_prep(lm, spec.blur)
             lvl = self.ctx.mask_levels(lv, m_lat) if lv is not None else None
-        return m_lat[None], (m_px[None] if spec.paste_back else None), lm[None], None if lvl is None else lvl[None]
+            if ctl_a is not None:                         # after grow and ramp: the control map moves with the mask
+                ctl_w = self.ctx.control_pyramid(lm if lv is None else lv, ctl_a, binary=lv is None, levels=self._ctl_levels())
+        out = m_lat[None], (m_px[None] if spec.paste_back else None), lm[None], None if lvl is None else lvl[None]
+        return out if ctl_a is None else out + (ctl_w[None],)
+
+    def _ctl_levels(self):
+        """The pyramid levels of the ControlNet's residuals; more than the weight pyramid has is a ValueError."""
+        levels = max(self.controlnet.residual_levels()) + 1
+        if levels > hctl.MAX_LEVELS:
+            raise ValueError(f"control weights: `in_mask` serves ControlNets of up to {hctl.MAX_LEVELS} resolution levels, this one has {levels}")
+        return levels
+
+    def _ctl_job(self, cn_scale, steps, ctl_w=None):
+        """The job entries of the control weights; none with the setting at None, whose job is what it was.  ctl_layers: the
+        scale of every residual; ctl_keep: whether each loop step runs the ControlNet (no step does when every scale is 0); ctl_w: with `in_mask`
+        and a mask, the weights of the latent positions, f32 [1, P_tot]."""
+        ctl = self.control_weights
+        if ctl is None:
+            return {}
+        scales = hctl.layer_scales(cn_scale, ctl.layers, self.controlnet.n_out)
+        live = any(s != 0 for s in scales)
+        out = dict(ctl_layers=scales, ctl_keep=tuple(k and live for k in hctl.keep(len(steps), ctl.steps)))
+        if ctl_w is not None:
+            out["ctl_w"] = ctl_w
+        return out
 
     def _prepare(self, prompt, negative_prompt, image, control_image, strength, num_inference_steps, guidance_scale,
                  controlnet_conditioning_scale, generator, mask_image, spec):
@@ -257,7 +289,11 @@ class HipImg2ImgPipeline:
         w, h = size_of(image)
         if h % 8 or w % 8:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {h} and {w}.")
-        mask_lat, mask_px, mask_l, lvl_lat = self._mask_job(mask_image, spec, h, w)
+        ctl, ctl_w = self.control_weights, None
+        if ctl is not None and ctl.in_mask is not None and mask_image is not None:     # `in_mask` without a mask has nothing to weigh: the scalar job
+            mask_lat, mask_px, mask_l, lvl_lat, ctl_w = self._mask_job(mask_image, spec, h, w, hctl.mask_a(ctl.in_mask))
+        else:
+            mask_lat, mask_px, mask_l, lvl_lat = self._mask_job(mask_image, spec, h, w)
         steps = self.scheduler.plan(num_inference_steps, strength)
         if not steps:
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of "
@@ -307,7 +343,8 @@ class HipImg2ImgPipeline:
             noises=[self._randn((1, 4, lh, lw), generator) for _ in range(n_noise)],
             mask_lat=mask_lat, mask_px=mask_px, mask_cfg=None if mask_lat is None else (spec.blur, spec.paste_back),
             **({} if lvl_lat is None else dict(lvl_lat=lvl_lat)),         # a soft mask's latent levels; none: the job is what it was
-            **self._content_job(spec, mask_l, mask_lat), **self._blend_job(spec, mask_l))
+            **self._content_job(spec, mask_l, mask_lat), **self._blend_job(spec, mask_l),
+            **self._ctl_job(controlnet_conditioning_scale, steps, ctl_w))   # control weights; none: the job is what it was
 
     @staticmethod
     def _blend_job(spec, blend_l):
@@ -381,6 +418,9 @@ class HipImg2ImgPipeline:
         if any(j.get("emph") is not None for j in jobs):  # prompt emphasis: every image its own weights; an image without a weighted token has ones
             ones = torch.ones(nb * t77, device=self.ctx.device, dtype=torch.float32)
             job["emph"] = torch.cat([j["emph"] if j.get("emph") is not None else ones for j in jobs])
+        if any(j.get("ctl_w") is not None for j in jobs):  # control weights: every image its own mask's; an image without a mask has ones
+            ones = torch.ones_like(next(j["ctl_w"] for j in jobs if j.get("ctl_w") is not None))
+            job["ctl_w"] = torch.cat([j["ctl_w"] if j.get("ctl_w") is not None else ones for j in jobs])
         job["img_u8"] = torch.stack([j["img_u8"] for j in jobs])
         job["ctl_u8"] = torch.stack([j["ctl_u8"] for j in jobs])
         job["t_dev"] = [t.repeat(n, 1) for t in jobs[0]["t_dev"]]
@@ -399,7 +439,12 @@ class HipImg2ImgPipeline:
         UNet and the ControlNet run each loop step on the rows of the variants that have joined the loop by then -- a leading slice, rows being
         image-major as in prepare_batch().  One generator: variant i consumes the noise a single call with that generator and strength draws (its
         stream is a prefix of the longest variant's).  A soft mask's level map is shared: its support does not depend on the step count, and every
-        variant releases a level by its own K.  The other arguments are prepare()'s.  A sweep of ONE variant is the single-image job."""
+        variant releases a level by its own K.  The other arguments are prepare()'s.  A sweep of ONE variant is the single-image job.
+        Control weights: `layers` and `in_mask` work, every variant reading the image's one weight vector; a `steps`
+        window is a ValueError here -- the variants share their loop steps, and diffusers' rule counts each variant's own."""
+        if self.control_weights is not None and self.control_weights.steps is not None:
+            raise ValueError(f"control weights: steps={self.control_weights.steps} does not combine with a strength sweep (the variants share "
+                             "their loop steps, the window counts each variant's own)")
         spec = hmask.MaskSpec.check(mask_blur, paste_back, masked_content, blend, blend_levels, mask_grow, mask_mode, mask_ramp,
                                     have_mask=mask_image is not None, paste_later=paste_later)
         from . import sweep as hsweep
@@ -473,14 +518,17 @@ class HipImg2ImgPipeline:
             # 6. per-image invariants: nothing here depends on the latents, so the whole block rides on the side stream beside the VAE
             # encode (text-time addition embeddings, the ControlNet's edge-map embedding, the first step's timestep projections)
             self.unet.begin_image(pooled, job["time_ids"], emph=job.get("emph"))       # emph: prompt emphasis, the weight of every text row
-            self.controlnet.begin_image(pooled, job["time_ids"], emph=job.get("emph"))
-            # the edge-map embedding is the same for the CFG rows of an image: computed once per image, then repeated (upstream runs
-            # it on the duplicated batch; the values are identical)
-            conds = [ctx.pixels_in(ctls[i], False) for i in range(n)]
-            cond_emb = self.controlnet.cond_embedding(conds[0] if n == 1 else torch.cat(conds, dim=0))
-            if nb > 1:
-                cond_emb = cond_emb.repeat_interleave(nb, dim=0)
-            tb0 = (self.unet.time_rowbias(job["t_dev"][0]), self.controlnet.time_rowbias(job["t_dev"][0]))
+            # control weights: ctl_keep says which steps run the ControlNet; None: all of them, as ever
+            ctl_s, ctl_keep = job.get("ctl_layers"), job.get("ctl_keep")
+            if ctl_keep is None or any(ctl_keep):
+                self.controlnet.begin_image(pooled, job["time_ids"], emph=job.get("emph"))
+                # the edge-map embedding is the same for the CFG rows of an image: computed once per image, then repeated (upstream runs
+                # it on the duplicated batch; the values are identical)
+                conds = [ctx.pixels_in(ctls[i], False) for i in range(n)]
+                cond_emb = self.controlnet.cond_embedding(conds[0] if n == 1 else torch.cat(conds, dim=0))
+                if nb > 1:
+                    cond_emb = cond_emb.repeat_interleave(nb, dim=0)
+            tb0 = (self.unet.time_rowbias(job["t_dev"][0]), self.controlnet.time_rowbias(job["t_dev"][0]) if ctl_keep is None or ctl_keep[0] else None)
         text_len = text.shape[0] // (n * nb)
         # 3. pixels, 5. prepare_latents: VAE posterior sample (draw #1), init noise (draw #2), add_noise -- per image (the
         # 1024^2 VAE tensors of a batch would cross the 2 GiB operand limit of the buffer-load kernels, and gain nothing)
@@ -502,17 +550,25 @@ class HipImg2ImgPipeline:
         self._mark("cond_embed")
         # 7. denoising loop
         for k, (st, t_dev) in enumerate(zip(steps, job["t_dev"])):
-            tb_u, tb_c = tb0 if k == 0 else (self.unet.time_rowbias(t_dev), self.controlnet.time_rowbias(t_dev))
+            cn_on = ctl_keep is None or ctl_keep[k]       # a dropped step issues nothing of the ControlNet: no time projections, no trunk, no fork
+            tb_u, tb_c = tb0 if k == 0 else (self.unet.time_rowbias(t_dev), self.controlnet.time_rowbias(t_dev) if cn_on else None)
             self._mark("embed")
             # UNet encoder and ControlNet trunk are independent until the zero-conv adds: two HIP streams, so their
             # small-grid kernels (32x32 latent level: <= 1 block per CU each) share the 256 CUs
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                c_skips, c_mid = self.controlnet.encode_cond(model_in, cond_emb, tb_c, text, text_len)
+            if cn_on:
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    c_skips, c_mid = self.controlnet.encode_cond(model_in, cond_emb, tb_c, text, text_len)
             skips, mid = self.unet.encode(self.unet.conv_in(ctx, model_in), tb_u, text, text_len)
-            main.wait_stream(side)
+            if cn_on:
+                main.wait_stream(side)
             self._mark("unet_enc+controlnet")
-            skips, mid = self.controlnet.add_residuals(c_skips, c_mid, job["cn_scale"], skips, mid)
+            if ctl_s is None:
+                skips, mid = self.controlnet.add_residuals(c_skips, c_mid, job["cn_scale"], skips, mid)
+            elif cn_on:
+                skips, mid = self.controlnet.add_residuals_weighted(c_skips, c_mid, ctl_s, skips, mid, w=job.get("ctl_w"), rows_per_image=nb)
+            else:                                         # the UNet decodes on its own skips
+                skips, mid = [passed_through(s) for s in skips], passed_through(mid)
             eps = self.unet.decode(mid, skips, tb_u, text, text_len)
             self._mark("unet_dec")
             for i in range(n):
@@ -533,6 +589,8 @@ class HipImg2ImgPipeline:
         out_u8 = outs[0] if n == 1 else torch.stack(outs)
         self._mark("vae_decode")
         self.last_stats = dict(unet_evals=len(steps), cfg_batch=nb, latent_hw=(lh, lw), images=n)
+        if ctl_keep is not None:
+            self.last_stats["control_steps_kept"] = sum(ctl_keep)
         self._latents = latents
         job["_result"] = dict(stats=dict(self.last_stats), latents=latents)     # what THIS job produced (graph entries keep theirs)
         if z0 is not None:
@@ -574,11 +632,15 @@ class HipImg2ImgPipeline:
             # one prompt pair: its nb rows stand for every variant (torch copies, as the CFG repeat of the edge-map embedding is)
             text = torch.cat([pl, pg], dim=1).repeat(k, 1)
             emph = None if job.get("emph") is None else job["emph"].repeat(k)     # prompt emphasis: the one prompt pair's weights, as its text rows
-            for net in (self.unet, self.controlnet):
+            # control weights: the scales, and whether the ControlNet runs at all (a sweep has no window: every scale 0 or none)
+            ctl_s, ctl_keep = job.get("ctl_layers"), job.get("ctl_keep")
+            cn_on = ctl_keep is None or any(ctl_keep)
+            for net in (self.unet, self.controlnet) if cn_on else (self.unet,):
                 net.begin_image(pooled, job["time_ids"], emph=emph)
                 net.add_emb = net.add_emb.repeat(k, 1)
-            cond_emb = self.controlnet.cond_embedding(ctx.pixels_in(ctl, False)).repeat_interleave(k * nb, dim=0)
-            tb0 = (self.unet.time_rowbias(job["t_dev"][0]), self.controlnet.time_rowbias(job["t_dev"][0]))
+            if cn_on:
+                cond_emb = self.controlnet.cond_embedding(ctx.pixels_in(ctl, False)).repeat_interleave(k * nb, dim=0)
+            tb0 = (self.unet.time_rowbias(job["t_dev"][0]), self.controlnet.time_rowbias(job["t_dev"][0]) if cn_on else None)
         text_len = text.shape[0] // (k * nb)
         mask_lat, mask_px = job.get("mask_lat"), job.get("mask_px")
         latents = torch.empty((k, hw, 4), device=dev, dtype=torch.float32)
@@ -597,15 +659,22 @@ class HipImg2ImgPipeline:
         self._mark("cond_embed")
         for step, (active, t_dev) in enumerate(zip(sched, job["t_dev"])):
             r = len(active) * nb                          # the rows of this step: the variants that have joined the loop
-            tb_u, tb_c = tb0 if step == 0 else (self.unet.time_rowbias(t_dev), self.controlnet.time_rowbias(t_dev))
+            tb_u, tb_c = tb0 if step == 0 else (self.unet.time_rowbias(t_dev), self.controlnet.time_rowbias(t_dev) if cn_on else None)
             self._mark("embed")
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                c_skips, c_mid = self.controlnet.encode_cond(model_in[:r], cond_emb[:r], tb_c, text, text_len)
+            if cn_on:
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    c_skips, c_mid = self.controlnet.encode_cond(model_in[:r], cond_emb[:r], tb_c, text, text_len)
             skips, mid = self.unet.encode(self.unet.conv_in(ctx, model_in[:r]), tb_u, text, text_len)
-            main.wait_stream(side)
+            if cn_on:
+                main.wait_stream(side)
             self._mark("unet_enc+controlnet")
-            skips, mid = self.controlnet.add_residuals(c_skips, c_mid, job["cn_scale"], skips, mid)
+            if ctl_s is None:
+                skips, mid = self.controlnet.add_residuals(c_skips, c_mid, job["cn_scale"], skips, mid)
+            elif cn_on:                                   # every variant is the one image: all rows read its one weight vector
+                skips, mid = self.controlnet.add_residuals_weighted(c_skips, c_mid, ctl_s, skips, mid, w=job.get("ctl_w"), rows_per_image=k * nb)
+            else:
+                skips, mid = [passed_through(s) for s in skips], passed_through(mid)
             eps = self.unet.decode(mid, skips, tb_u, text, text_len)
             self._mark("unet_dec")
             for i, st, zi in active:
@@ -720,6 +789,8 @@ class HipImg2ImgPipeline:
             base = base + (("sweep", job["sweep"]),)
         if job.get("emph") is not None:                  # prompt emphasis: + one flag (the weights are graph inputs); an un-weighted key is what it was
             base = base + ("emph",)
+        if job.get("ctl_layers") is not None:            # control weights: + the scales and the kept steps (the position weights are graph inputs)
+            base = base + (("ctl", job["ctl_layers"], job["ctl_keep"], job.get("ctl_w") is not None),)
         return base
 
     def run_device_graphed(self, job, slot=0):
@@ -769,8 +840,9 @@ class HipImg2ImgPipeline:
         return out
 
     def _tensor_keys(self, job):
-        """The job tensors a graph reads from its static buffers: the mask tensors of a masked job and the weights of an emphasised prompt join them."""
-        return self._TENSOR_KEYS + tuple(k for k in self._MASK_KEYS + ("emph",) if job.get(k) is not None)
+        """The job tensors a graph reads from its static buffers: the mask tensors of a masked job, the weights of an emphasised prompt and the control
+        weights of a mask join them."""
+        return self._TENSOR_KEYS + tuple(k for k in self._MASK_KEYS + ("emph", "ctl_w") if job.get(k) is not None)
 
     def _capture(self, key, job, slot):
         static = dict(job)
@@ -792,9 +864,22 @@ class HipImg2ImgPipeline:
         # its split-K workspace can be bound BEFORE the capture: allocated inside, its torch.zeros became a 96 MB memset node that every
         # replay of the slot's first graph re-ran
         cap = self.ctx.capture_stream()
-        # thread_local: other worker threads keep replaying / allocating on their own streams during this capture
-        with torch.cuda.graph(graph, pool=pool, stream=cap, capture_error_mode="thread_local"):
-            out = self.run_device(static)
+        # No pass of Python's cycle collector inside the capture.  A capturing thread may not call the runtime's unsafe entries (free, event query,
+        # synchronise), and a collector pass that starts between two launches runs the finalisers of whatever dead cycles the process has
+        # gathered -- device and pinned buffers, events, launch programs of objects long out of use -- from this very thread; an error raised in
+        # such a finaliser ends the process (seen once: "Fatal Python error: Aborted ... Garbage-collecting" under hip.py: attention, in this
+        # captured pass).  torch.cuda.graph() used to collect on entry and, since 2.10, no longer does (torch.compiler.config.force_cudagraph_gc).
+        # So: collect here, in front of the capture, and keep the collector off until it has ended.  Reference counts free as ever.
+        gc_was_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        try:
+            # thread_local: other worker threads keep replaying / allocating on their own streams during this capture
+            with torch.cuda.graph(graph, pool=pool, stream=cap, capture_error_mode="thread_local"):
+                out = self.run_device(static)
+        finally:
+            if gc_was_on:
+                gc.enable()
         self.ctx.ws_tag = 0
         self.timing = timing
         self._graphs[key] = (graph, static, out)

@@ -833,6 +833,38 @@ int fie_sweep_select_u8(fie_ctx* ctx, const void* const* imgs, int k, int64_t by
  *   workspace, no block waits for another. */
 int fie_kv_emphasis(fie_ctx* ctx, void* X, int64_t ld, int64_t rows, int64_t ncols, const float* w, const uint8_t* vflags, int f32);
 
+/* ---- Control weights: the ControlNet's residuals weighed per latent position, so that a mask can let go of the edge map.
+ *   fie_control_pyramid_u8   e u8 [H, W] on the device, 8-byte aligned: the edit-ness of every edit-size pixel -- binary = 1: an L mask, read as
+ *      255 (e >= 128); binary = 0: a level map, read as it is.  H, W multiples of 8 in 8 .. 2048; levels in 1 .. 3; a in 0 .. 255.
+ *      Level l has h_l x w_l positions, h_0 = H / 8, h_{l+1} = ceil(h_l / 2) (w alike), and blocks of side s = 8 * 2^l pixels clipped at the image:
+ *      E = the integer sum of e over the block, cnt = its pixels,
+ *          out[off_l + y w_l + x] = (float)(255 cnt 256 - (256 - a) E) / (float)(255 cnt 256)      off_l = sum of h_k w_k over k < l
+ *      one IEEE f32 division of two int32 converted to f32.  out: f32 [sum h_l w_l], every element written.  One launch, integer sums in a fixed
+ *      order, no atomics, no workspace.  fie_amd/control.py: weights_numpy(pyramid_numpy(...)) restates it to the byte.
+ *   fie_control_add   all residuals of one evaluation in ONE launch.  The table (read on the host when the call is issued, passed to the kernel
+ *      by value) holds `count` in 1 .. 16 segments: u, t, out row-major [rows, C] f16 (f32 = 0) or f32 (f32 = 1), contiguous, 16-byte aligned, out
+ *      a tensor of its own; C % 8 == 0; rows = B * P: B batch rows of P latent positions; woff: where the segment's level starts in the weights;
+ *      s: its scale.  w: f32 [images, p_tot] ON THE DEVICE (a graph replay reads the weights of the job it replays); batch row b belongs to image
+ *      b / rows_per_image.  For every element of row r = b P + p:
+ *          c = s * w[(b / rows_per_image) p_tot + woff + p]                f32
+ *          out = c == 0 ? u : round(f32(u) + c * f32(t))                   product and sum rounded separately; f16: one conversion, nearest even
+ *      Where c == 0, out holds u's bits and t is not read.  The caller keeps b / rows_per_image below the images of w.  fie_amd/control.py:
+ *      add_numpy restates it to the bit.  One launch, 16-byte accesses, one writer per element, no atomics, no workspace.
+ *   FIE_EINVAL for anything else, before any launch. */
+#define FIE_CONTROL_MAX_SEGMENTS 16
+#define FIE_CONTROL_MAX_LEVELS 3
+typedef struct fie_control_table {
+    int count;
+    int C[16], P[16], woff[16];
+    int64_t rows[16];
+    float s[16];
+    const void* u[16];
+    const void* t[16];
+    void* out[16];
+} fie_control_table;
+int fie_control_pyramid_u8(fie_ctx* ctx, const uint8_t* e, int H, int W, int levels, int a, int binary, float* out);
+int fie_control_add(fie_ctx* ctx, const fie_control_table* table, const float* w, int64_t p_tot, int rows_per_image, int f32);
+
 #ifdef __cplusplus
 }
 #endif

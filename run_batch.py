@@ -10,6 +10,8 @@ Additive flags (the reference has none of them): --strength, --weights_dir, --de
 --auto_strength, --min_ssim, --strengths.  FIE_CANNY_DENSITY=d in the environment runs every edit with an edge-budget Canny (FastEditor.set_canny_density;
 DESIGN.md section 22): the pair picked for each image goes into --results_json as canny_low / canny_high.  FIE_PROMPT_EMPHASIS=w in the environment
 reads the [...] marks of the PIE-Bench editing prompts as prompt emphasis of weight w (FastEditor.set_prompt_emphasis).
+FIE_CONTROL_WEIGHTS="layers=prompt;steps=0:0.5;in_mask=0" (any subset of the three) runs every edit under those control weights
+(FastEditor.set_control_weights).
 """
 import argparse
 import json
@@ -598,6 +600,8 @@ def main(argv=None):
             f"{min(args.canny_low, args.canny_high)} / {max(args.canny_low, args.canny_high)} (each image's pair: --results_json)")
     if getattr(editor, "prompt_emphasis", None) is not None:
         say(f"      Prompt emphasis: the [...] marks of the prompts weigh {editor.prompt_emphasis:g} (FIE_PROMPT_EMPHASIS)")
+    if getattr(editor, "control_weights", None) is not None:
+        say(f"      Control weights: {editor.control_weights} (FIE_CONTROL_WEIGHTS)")
 
     progress = None
     if rank == 0:

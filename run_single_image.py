@@ -172,9 +172,35 @@ def add_emphasis_args(p):
     return p
 
 
+def add_control_args(p):
+    """[additive] control weights, kept apart from build_parser() like add_emphasis_args."""
+    p.add_argument("--control_layers", default=None, metavar="PRESET|N,N,...",
+                   help="[additive] a factor on --control_scale for each of the ControlNet's residuals (SDXL / SSD-1B: 10, the mid block's last): "
+                        "'balanced', 'prompt' (0.825 ** (9 - i): the prompt matters more), 'guess' (diffusers' guess_mode ramp), or comma-separated "
+                        "numbers in [0, 2]")
+    p.add_argument("--control_steps", default=None, metavar="A:B",
+                   help="[additive] diffusers' control_guidance_start:control_guidance_end in [0, 1], over the steps that run after --strength; a "
+                        "step outside the window runs no ControlNet")
+    p.add_argument("--control_in_mask", type=float, default=None, metavar="X",
+                   help="[additive] scale the ControlNet's residuals inside --mask by X in [0, 1] relative to outside: 0 lets go of the edge map "
+                        "where the edit happens.  No preset, window or value has been tried on real checkpoints.  Without the three flags nothing changes")
+    return p
+
+
+def control_keywords(args):
+    """The keywords of FastEditor.set_control_weights from the three flags, checked for a 10-residual ControlNet; {} without them.  ValueError."""
+    from fie_amd import control as hctl
+    parts = [f"{k}={v}" for k, v in (("layers", args.control_layers), ("steps", args.control_steps), ("in_mask", args.control_in_mask)) if v is not None]
+    if not parts:
+        return {}
+    kw = hctl.parse_env(";".join(parts))
+    hctl.check(kw.get("layers"), kw.get("steps"), kw.get("in_mask"), 10)
+    return kw
+
+
 def full_parser():
     """The parser main() reads: build_parser() and every additive group."""
-    return add_emphasis_args(add_canny_args(add_sweep_args(add_tile_args(build_parser()))))
+    return add_control_args(add_emphasis_args(add_canny_args(add_sweep_args(add_tile_args(build_parser())))))
 
 
 def save_plot(path, source_img, edited_img, model, prompt):
@@ -228,6 +254,7 @@ def main(argv=None):
         if args.prompt_emphasis is not None:                            # the marks of both prompts, read before the models load
             for text in (args.prompt, args.negative_prompt or ""):
                 hemph.parse(text, args.prompt_emphasis)
+        control_kw = control_keywords(args)                             # the three control flags, read before the models load
     except ValueError as e:
         parser.error(str(e))
     if args.resolution != "square":
@@ -296,6 +323,9 @@ def main(argv=None):
     if args.prompt_emphasis is not None:
         editor.set_prompt_emphasis(args.prompt_emphasis)
         print(f"      Prompt emphasis: [...] weighs {args.prompt_emphasis:g}; the prompt is tokenised as {hemph.parse(args.prompt, args.prompt_emphasis)[0]!r}")
+    if control_kw:
+        editor.set_control_weights(**control_kw)
+        print(f"      Control weights: {editor.control_weights}")
     t0 = time.time()
     variants = None
     if args.sweep:

@@ -51,9 +51,21 @@ class FastEditor:
     def __init__(self, model_name="sdxl", device="cuda", dtype=torch.float16, enable_cpu_offload=True,
                  use_full_precision=False, use_full_controlnet=False, *, weights_dir=None, seed_weights=1234,
                  noise_dtype=None, broadcast_weights=True, weight_dtype="f16", clip_score_dir=None, dino_dir=None, dino_layer=11,
-                 lpips_dir=None, canny_density=None, prompt_emphasis=None):
+                 lpips_dir=None, canny_density=None, prompt_emphasis=None, control_weights=None):
         if model_name not in self.MODEL_CONFIGS and model_name not in self._EXTRA_STACKS:
             raise ValueError(f"Unknown model: {model_name}. Choose from {list(self.MODEL_CONFIGS.keys())}")
+        # [additive] set_control_weights() from the start: a dict of its keywords; FIE_CONTROL_WEIGHTS ("layers=prompt;steps=0:0.5;in_mask=0") serves run_batch.py
+        from fie_amd import control as hctl
+        if control_weights is None and os.environ.get("FIE_CONTROL_WEIGHTS"):
+            try:
+                control_weights = hctl.parse_env(os.environ["FIE_CONTROL_WEIGHTS"])
+            except ValueError as e:
+                raise ValueError(f"FIE_CONTROL_WEIGHTS: {e}") from None
+        if control_weights is not None and not (isinstance(control_weights, dict) and set(control_weights) <= {"layers", "steps", "in_mask"}):
+            raise ValueError(f"control_weights={control_weights!r}: None, or a dict of set_control_weights()'s keywords layers, steps, in_mask")
+        cn_cfg = stack.stack_configs(model_name, use_full_controlnet)["controlnet"]
+        self._ctl_n_out = 2 + sum(cn_cfg["layers_per_block"] + (i != len(cn_cfg["block_out_channels"]) - 1) for i in range(len(cn_cfg["block_out_channels"])))
+        self.set_control_weights(**(control_weights or {}))
         if canny_density is None and os.environ.get("FIE_CANNY_DENSITY"):     # [additive] set_canny_density() from the start; the switch serves run_batch.py
             try:
                 canny_density = float(os.environ["FIE_CANNY_DENSITY"])
@@ -120,6 +132,8 @@ class FastEditor:
         self.pipe = HipImg2ImgPipeline(ctx, cfgs, sds, tokenizers=toks, noise_dtype=noise_dtype or self.dtype, weight_dtype=weight_dtype)
         self.pipe.prompt_emphasis = self.prompt_emphasis
         self.controlnet = self.pipe.controlnet
+        self._ctl_n_out = self.controlnet.n_out            # the loaded net's own count (a weights directory brings its config)
+        self.set_control_weights(**(self.control_weights or {}))
         self._tls = threading.local()          # .slot: graph slot of the calling worker thread (set_in_flight)
         self._fullres_out = {}                 # (slot, image) -> flat u8 buffer on the device, grown to the largest source: the full-resolution back end's output (output_size="source")
         self._tile_bufs = {}                   # (slot, tiles, th, tw) -> u8 [tiles, th, tw, 3] on the device: where the tile results of a tiled edit meet (tiles=...)
@@ -232,6 +246,46 @@ class FastEditor:
         if getattr(self, "pipe", None) is not None:
             self.pipe.prompt_emphasis = self.prompt_emphasis
         return before
+
+    control_weights = None      # set_control_weights(): None, or the dict of its three keywords as normalised
+
+    def set_control_weights(self, layers=None, steps=None, in_mask=None):
+        """[additive] Control weights for every later edit(), edit_batch() and edit_sweep() of this editor: how much of the
+        ControlNet's edge guidance reaches the UNet, per residual, per step and inside the mask.  All three at None (the default) switch it off.
+        `layers`: one factor in [0, 2] on top of `controlnet_conditioning_scale` for each of the ControlNet's residuals -- 10 for SDXL / SSD-1B:
+        the nine skip tensors, finest first, and the mid block's last -- or a preset: "balanced" (all 1), "prompt" (0.825 ** (9 - i): the front
+        ends' "My prompt is more important") or "guess" (10 ** (-1 + i / 9): diffusers' guess_mode ramp).  A factor of 0 skips that zero-conv.
+        `steps`: (start, end) in [0, 1], diffusers' control_guidance_start / control_guidance_end over the K loop steps that run after
+        `strength`: step k keeps the ControlNet unless k / K < start or (k + 1) / K > end; a dropped step runs no ControlNet kernel at all.  It
+        does not combine with edit_sweep (a ValueError there: the variants share their loop steps, the rule counts each variant's own).
+        `in_mask`: a number in [0, 1] that scales the residuals inside the mask relative to outside -- 0 lets go of the edge map where the edit
+        happens and keeps it everywhere else.  A latent position's weight is 1 - (1 - in_mask) * the mean of the mask over its pixels (a level map's
+        greys count as fractions), per resolution level, made on the device from the mask behind `mask_grow` / `mask_ramp`; a call without a
+        mask has nothing to weigh and runs as without `in_mask`.  Neutral values -- all layers 1, steps (0, 1), in_mask 1 -- are None: the same
+        job, graph and bytes.  fp16, fp32 and fp8-weight editors alike (the zero-convs write fp16 there too); the C-ABI model forwards do not
+        read the setting.  No preset, window or `in_mask` value has been tried on real checkpoints.  With `metrics=True` the dict gains
+        `control_steps_kept`.  The setting belongs to the editor, not to a thread: set it before the worker threads of `set_in_flight` start.
+        Returns the setting it replaces: None, or a dict of the three keywords."""
+        from fie_amd import control as hctl
+        new = hctl.check(layers, steps, in_mask, self._ctl_n_out)
+        before, self.control_weights = self.control_weights, None if new is None else new._asdict()
+        if getattr(self, "pipe", None) is not None:
+            self.pipe.control_weights = new
+        return before
+
+    _ctl_n_out = 10             # the ControlNet's residuals (SDXL / SSD-1B and the test stacks: 9 skips + mid); __init__ reads the model's own
+
+    def _with_control(self, dicts, kw, strength=None):
+        """The metric dicts with `control_steps_kept` -- the loop steps of the edit that ran the ControlNet -- while control weights are set.  kw: the
+        scalar keywords of the call (_scalars); `strength`: one variant's, for a sweep."""
+        ctl = self.control_weights
+        if ctl is not None:
+            from fie_amd import control as hctl
+            steps = len(self.pipe.scheduler.plan(kw["num_inference_steps"], kw["strength"] if strength is None else strength))
+            live = any(s != 0 for s in hctl.layer_scales(kw["controlnet_conditioning_scale"], ctl["layers"], self._ctl_n_out))
+            for d in dicts:
+                d["control_steps_kept"] = sum(hctl.keep(steps, ctl["steps"])) if live else 0
+        return dicts
 
     def last_canny_thresholds(self):
         """[additive] Per image of the calling thread's last edit(), edit_batch() or edit_sweep(): the (low, high) its edge-budget Canny picked, or
@@ -376,6 +430,8 @@ class FastEditor:
                                    scalars)
             if metrics and pair is not None:
                 res[1].update(canny_low=pair[0], canny_high=pair[1])
+            if metrics:
+                self._with_control([res[1]], scalars)
             self._tls.canny_pairs = [pair]
             return res
         if region is not None and margins is not None:            # a region crops on the host: the canvas comes back once, the rest is the call on it
@@ -397,7 +453,7 @@ class FastEditor:
         self._tls.canny_pairs = [res.canny_pair]
         if not metrics:
             return res.images[0]
-        return res.images[0], self._with_pair(self._scores(res.extra, [masked]), [res.canny_pair])[0]
+        return res.images[0], self._with_control(self._with_pair(self._scores(res.extra, [masked]), [res.canny_pair]), scalars)[0]
 
     @staticmethod
     def _scalars(strength, num_inference_steps, guidance_scale, controlnet_conditioning_scale, canny_low_threshold, canny_high_threshold, seed):
@@ -566,6 +622,8 @@ class FastEditor:
         extra, ihost = res.extra if select is not None else (res.extra, None)
         variants = [{"strength": list(v[1]), "steps": v[0], **d}
                     for v, d in zip(vs, self._with_pair(self._scores(extra, [masked] * k), [res.canny_pair] * k))]
+        for v, d in zip(vs, variants):                    # control weights: a sweep has no window, every variant keeps all of its own steps
+            self._with_control([d], scalars, strength=v[1][0])
         if select is None:
             return res.images, variants
         index = int(ihost[0])
@@ -858,7 +916,7 @@ class FastEditor:
         self._tls.canny_pairs = res.canny_pairs
         if not metrics:
             return res.images
-        return res.images, self._with_pair(self._scores(res.extra, [m is not None for m in omasks]), res.canny_pairs)
+        return res.images, self._with_control(self._with_pair(self._scores(res.extra, [m is not None for m in omasks]), res.canny_pairs), scalars)
 
     def _batch_job(self, images, prompts, negative_prompts, size, mask_ls, margins, spec, metrics, full, kw, after=None):
         """The single-size tail of edit_batch(): ONE device job for images that share the target `size`.  images: PIL images, or u8 [H, W, 3] tensors
