@@ -62,15 +62,17 @@ class FieError(RuntimeError):
 
 def fold_layernorm_tables(w, bias, gamma, beta, geglu=False):
     """LayerNorm folded into the Linear that consumes it:  LN(x) W^T + b = rstd * (x Wf^T - mean * S) + b'  with Wf = f16(W * gamma), S[n] = sum_k Wf[n, k]
-    (over the ROUNDED folded weights, so that x Wf^T - mean * S is exactly (x - mean) Wf^T), b' = W beta + b in fp32.  Returns (Wf [N, K] f16,
+    (over the ROUNDED folded weights, so that x Wf^T - mean * S is exactly (x - mean) Wf^T), b' = W beta + b.  Both are summed in float64 and rounded
+    once to fp32: the kernel multiplies S by the row mean, and an S a few fp32 ulps off costs, at a row offset of 300 sigma, what the kernel's whole fp32
+    budget is (tests/test_host_cpu.py, profiles/ln_fold_pins.md).  Returns (Wf [N, K] f16,
     table [N, 2] fp32 = (S, b')), the table's rows in the packed column order (GEGLU: value / gate rows interleaved, as fie_pack_rows_f16 with interleave2)."""
     w = w.float()
     n = w.shape[0]
     wf = (w * gamma.float()[None, :]).to(torch.float16)
-    b = w @ beta.float()
+    b = w.double() @ beta.double()
     if bias is not None:
-        b = b + bias.float()
-    tab = torch.stack([wf.float().sum(1), b], 1)
+        b = b + bias.double()
+    tab = torch.stack([wf.double().sum(1), b], 1).float()
     if geglu:
         tab = torch.stack([tab[: n // 2], tab[n // 2:]], 1).reshape(n, 2)
     return wf, tab.contiguous()

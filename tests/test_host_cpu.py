@@ -159,3 +159,20 @@ def test_layernorm_fold_tables_reproduce_layernorm_plus_linear(geglu):
     assert (folded - ref).abs().max() < 1e-5                                          # the table is fp32
     plain = F.layer_norm(xd, (k,), gamma.double(), beta.double(), 1e-5) @ w.double().t() + b.double()
     assert (folded - plain[:, order]).abs().max() / plain.abs().max() < 2e-3          # what rounding W * gamma to f16 costs
+
+
+@pytest.mark.parametrize("n,k,geglu", [(64, 128, False), (320, 1280, False), (640, 2560, True)])
+def test_layernorm_fold_tables_are_rounded_once(n, k, geglu):
+    """S = sum_k Wf[n, k] and b' = W beta + bias are the float64 sums rounded ONCE to fp32.  At a 300-sigma row offset the kernel multiplies S by a mean
+    300 sigma large: an S summed in fp32, a few ulps off, costs as much as the kernel's whole fp32 budget (tests/ln_fold_check.py)."""
+    import torch
+    from fie_amd.hip import fold_layernorm_tables
+    g = torch.Generator().manual_seed(11)
+    w, b = (torch.randn(n, k, generator=g) / k ** 0.5 + 0.02).half(), (torch.randn(n, generator=g) * 0.1).half()
+    gamma, beta = (1 + 0.2 * torch.randn(k, generator=g)).half(), (0.1 * torch.randn(k, generator=g) + 0.05).half()
+    wf, tab = fold_layernorm_tables(w, b, gamma, beta, geglu=geglu)
+    order = torch.stack([torch.arange(n // 2), torch.arange(n // 2) + n // 2], 1).reshape(-1) if geglu else torch.arange(n)
+    assert torch.equal(wf, (w.float() * gamma.float()[None, :]).half())
+    s64 = wf.double().sum(1)[order]
+    b64 = (w.double() @ beta.double() + b.double())[order]
+    assert torch.equal(tab[:, 0], s64.float()) and torch.equal(tab[:, 1], b64.float())
